@@ -18,28 +18,35 @@ N*B-block timeline; it builds and quantises ONLY those blocks and learns its car
 bytes per channel that every rank publishes about its own range (gpsiq_shard_carry/_seed: one
 all-gather at set-up).  No collective touches the data path (weak scaling: per-GPU work is fixed).
 
+A plain run sets up, warms up, times --steps steps and prints the line; only figures that come from
+that timed run are in it (roofline, counters, config).  --full adds every other leg below (marked
+[full]): they take runs of their own.  --dump-outputs DIR writes, after the timed steps, a fixed sample
+of the IQ blocks the last step left in the device ring (DIR/iq.npy, float32, and DIR/iq_blocks.npy,
+their timeline block numbers; rank 0): the same arguments give the same inputs in every run.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline     — algorithmic IQ bytes per launch / mean launch duration (HIP events on the launch
                  stream) against the 8 TB/s HBM peak,
   counters     — instruction-mix-independent fractions of the dominant kernel from committed rocprofv3 PMC passes of this
                  command (profiles/pmc_counters.json): VALU issue fraction, LDS busy, LDS bank-conflict ratio
                  (+ own_stream_efficiency: the kernel against the cost of its own instruction stream; not a roofline),
-  exact_mode_value / _roofline / _bound — the model whose output IS the reference's (GPSIQ_NCO_REFERENCE), whole
+  exact_mode_value / _roofline / _bound — [full] the model whose output IS the reference's (GPSIQ_NCO_REFERENCE), whole
                  gpsiq_generate_batch call at the headline workload, beside `value`,
-  reference_nco — that mode in detail: the call at the headline workload and at 25 Msps, the same with the carrier chain on host
+  reference_nco — [full] that mode in detail: the call at the headline workload and at 25 Msps, the same with the carrier chain on host
                  threads, the chain's parts (level 1 kernels on the device, level 2 link on the host, blocks linked / walked,
                  equality with the serial chain), evaluation alone, kernel alone, which side bounds it; at N > 1 the mode
                  time-sharded over the ranks (chain by time),
   placement    — (N > 1) where every rank runs: host, device ordinal, PCI bus id, CPUs granted, GPSIQ_THREADS,
-  cpu_baseline — the reference's own loop (oracle/_ref, kind "reference") or our port of it
+  cpu_baseline — [full] the reference's own loop (oracle/_ref, kind "reference") or our port of it
                  (oracle/, kind "port") timed on this host, 1 core, bounded sample (N = 1 only),
-  end_to_end   — the same per-GPU block count from scratch on every rank: host refresh of its own
+  end_to_end   — [full] the same per-GPU block count from scratch on every rank: host refresh of its own
                  blocks (gpsiq_refresh_epochs) -> quantise -> carrier seed exchange -> upload -> kernel,
                  once as one serial batch and once as a stream of rounds with the host side of the next
                  round overlapping the kernel of this one (end_to_end.streamed, with every rank's host and kernel
                  time per round and which of the two it is bound by),
-  extra        — short legs for the other BASELINE configs (each with its own roofline), the
-                 host-destination and single-block drop-in calls, GPSIQ_NCO_REFERENCE, first-launch times.
+  extra        — [full] short legs for the other BASELINE configs (each with its own roofline), the
+                 host-destination and single-block drop-in calls, GPSIQ_NCO_REFERENCE, first-launch times,
+                 the RCCL self-test of the N > 1 code path (N = 1).
 """
 import argparse
 import json
@@ -73,16 +80,24 @@ def parse():
     ap.add_argument("--launches", type=int, default=18, help="launches (of --blocks distinct blocks each) per step")
     ap.add_argument("--variant", type=str, default="auto")
     ap.add_argument("--seed", type=int, default=20250215)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (other configs, drop-in calls)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg outside the timed headline: CPU baseline, first-launch times, end-to-end legs, extra legs, "
+                         "RCCL self-test (N = 1), time-sharded GPSIQ_NCO_REFERENCE leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the IQ blocks the last step computed to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs (other configs, drop-in calls)")
     ap.add_argument("--cpu-blocks", type=int, default=299, help="blocks of the CPU baseline sample (299 = 30 s, config 1)")
     ap.add_argument("--rounds", type=int, default=16, help="rounds of the streamed end-to-end leg")
     ap.add_argument("--sweep", action="store_true", help="also time every kernel variant (extra stderr lines)")
     ap.add_argument("--exact-leg-only", action="store_true", help="only the GPSIQ_NCO_REFERENCE batch call at the headline size, one JSON line "
-                                                                   "(the default run starts this with GPSIQ_THREADS=2 for reference_nco.two_host_threads)")
+                                                                   "(the --full run starts this with GPSIQ_THREADS=2 for reference_nco.two_host_threads)")
     ap.add_argument("--dry-run", action="store_true",
                     help="host side only (launch logic, rendezvous, sharded refresh/quantise, seed exchange); no device, value null")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def effective_cpus():
@@ -201,6 +216,25 @@ def _cpu_worker(a):
         for b in range(len(d)):
             orc.block_float(d[b], nsamp, fs, sample_size)
     return len(d)
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this many bytes of float32 samples
+
+
+def dump_outputs(dirname, ring, nblocks, stride, blk_bytes, ss, block0, seed):
+    """--dump-outputs: what the last timed step left in the device ring, i.e. its last launch's blocks (timeline blocks
+    block0 .. block0 + nblocks - 1 in ring slots 0 .. nblocks - 1).  A fixed sample of those blocks (drawn with `seed`,
+    at most DUMP_BYTES of float32) -> DIR/iq.npy [blocks][2 * nsamp] interleaved I/Q sample values as the caller reads
+    them (int8 or int16, converted exactly), DIR/iq_blocks.npy their timeline block numbers (float64)."""
+    import torch
+    per_block = min(blk_bytes // ss, DUMP_BYTES // 4)          # IQ elements kept of each block
+    nsel = max(1, min(nblocks, 16, DUMP_BYTES // (4 * per_block)))
+    slots = np.sort(np.random.default_rng(seed).choice(nblocks, size=nsel, replace=False))
+    rows = torch.stack([ring[int(k) * stride: int(k) * stride + per_block * ss] for k in slots]).cpu().numpy()
+    iq = rows.view(np.int8 if ss == 1 else np.int16).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "iq.npy"), iq)
+    np.save(os.path.join(dirname, "iq_blocks.npy"), (block0 + slots).astype(np.float64))
 
 
 def roofline_obj(alg_bytes, launch_ms, traffic=None):
@@ -333,10 +367,10 @@ def main():
     L = max(1, args.launches)
     B = nblocks * L                                   # blocks per GPU per step
 
-    # CPU baseline first (rank 0, N = 1 only): it forks worker processes for the all-cores
+    # CPU baseline first (--full, rank 0, N = 1 only): it forks worker processes for the all-cores
     # figure, which must happen before this process holds a GPU context
     cpu_base = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and not dry:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and not dry:
         from gpsiq.scenario import synth_blocks as _sb
         pat = _sb(64, nchan, seed=args.seed)
         d_cpu = np.concatenate([pat] * (-(-args.cpu_blocks // 64)))[: args.cpu_blocks]
@@ -416,7 +450,7 @@ def main():
         ctx.set_descriptors(q)
         ring = torch.empty(nblocks * stride, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream().cuda_stream
-        if rank == 0:
+        if rank == 0 and args.full:
             # cold figures, before anything warms the device up: the very first launch (module load, clock
             # ramp) and the mean of the next five -- what a caller that launches once in a while sees
             torch.cuda.synchronize()
@@ -462,118 +496,121 @@ def main():
     t_max = max_over_ranks(t_local, dist, device=xdev)
     if not dry:
         launch_ms = e0.elapsed_time(e1) / (args.steps * L)       # HIP events on the launch stream
+    if args.dump_outputs and not dry and rank == 0:
+        # before any other leg: they all render into the same ring
+        dump_outputs(args.dump_outputs, ring, nblocks, stride, blk_bytes, ss, b0 + (L - 1) * nblocks, args.seed)
 
-    # ---- end to end: the same per-GPU block count from nothing, host side sharded as well ---------------
-    import tempfile
-    e2e = None
-    with tempfile.TemporaryDirectory() as td:
-        scen = Scenario(nchan, td)
-        nb_e = nblocks
-        g0, g1 = shard_range(nb_e * world, rank, world)
-        best = None
-        for _ in range(2):                                # the second pass has warm thread pools and buffers
-            gc.collect()
-            gc.disable()
-            sync_all()
-            ta = time.perf_counter()
-            q_e = scen.quantised(g0, g1, fs, nsamp)
-            tb = time.perf_counter()
-            q_e = seed_own_shard(q_e, nsamp, rank, world, gather)
-            tc = time.perf_counter()
-            if not dry:
-                ctx.set_descriptors(q_e)
-                td_ = time.perf_counter()
-                ctx.launch(0, nb_e, nsamp, ss, ring.data_ptr(), stride, stream=stream, variant=variant)
-                torch.cuda.synchronize()
-            else:
-                td_ = time.perf_counter()
-            te = time.perf_counter()
-            gc.enable()
-            parts = (tb - ta, tc - tb, td_ - tc, te - td_)
-            tot = max_over_ranks(te - ta, dist, device=xdev)
-            if best is None or tot < best[0]:
-                best = (tot, [max_over_ranks(p, dist, device=xdev) for p in parts])
-        tot, parts = best
-        e2e = {"value": None if dry else round(nb_e * world * nsamp / tot / 1e6, 1), "unit": "Msamples/s",
-               "blocks_per_gpu": nb_e, "channels": len(scen.svs), "seconds": round(tot, 5),
-               "x_realtime": None if dry else round(nb_e * world * 0.1 / tot, 1),
-               "host_refresh_and_quantise_ms": round(parts[0] * 1e3, 2), "seed_exchange_ms": round(parts[1] * 1e3, 2),
-               "validate_upload_ms": round(parts[2] * 1e3, 2), "kernel_ms": round(parts[3] * 1e3, 2),
-               "host_cpus": effective_cpus(),
-               "what": "static receiver (BASELINE config 1/2 geometry), RINEX-derived ephemeris; per rank: RunAhead.seek to its first block, "
-                       "nav words rolled over its 30 s epochs (gpsiq_nav_roll), gpsiq_refresh_epochs_quantized of its own blocks only "
-                       "(refresh and quantiser in one pass), 32 B/channel carrier-seed all-gather, gpsiq_set_descriptors, one gpsiq_launch; slowest rank, best of 2 passes"}
-        # ---- the same chain as a stream of rounds: round m gives this rank the blocks after rank-1's of round m
-        # and after all of round m-1; launches are asynchronous, so the host side of round m+1 (refresh, quantise,
-        # seed exchange on a gloo group, validate + upload into the other descriptor buffer) runs while the GPU is
-        # busy with round m.  What a long scenario costs per block once it is running.
-        R = args.rounds
-        side = None
-        cpu_gather = gather
-        exchange = backend if dist is not None else None
-        if dist is not None:                              # always a side group (also under gloo): one code path, tested on CPU
-            try:                                          # 32 B per channel of host data: a CPU collective, so that it
-                side = dist.new_group(backend="gloo")     # does not queue behind the kernels on the device
-                cpu_gather = torch_all_gather_bytes(dist, "cpu", group=side)
-                exchange = "gloo"
-            except Exception as ex:                       # no gloo here: the RCCL group still gives the right answer
-                print(f"[bench] no gloo side group ({ex}); seed exchange of the streamed leg over RCCL", file=sys.stderr)
-        best_s = None
-        passes_s = []
-        for _ in range(4):
-            ra, hist = scen.runahead(), []
-            gc.collect()                                   # as timeit does: a full collection takes 35 ms in this process and,
-            gc.disable()                                   # left to itself, lands in the middle of the second pass
-            sync_all()
-            ta = time.perf_counter()
-            host_busy = 0.0
-            for m in range(R):
-                th = time.perf_counter()
-                g0 = (m * world + rank) * nb_e
-                q_e = seed_own_shard(scen.quantised(g0, g0 + nb_e, fs, nsamp, ra=ra), nsamp, rank, world, cpu_gather, history=hist)
-                host_busy += time.perf_counter() - th
+    # ---- [full] end to end: the same per-GPU block count from nothing, host side sharded as well --------
+    e2e = ref_sharded = None
+    if args.full:
+        import tempfile
+        with tempfile.TemporaryDirectory() as td:
+            scen = Scenario(nchan, td)
+            nb_e = nblocks
+            g0, g1 = shard_range(nb_e * world, rank, world)
+            best = None
+            for _ in range(2):                                # the second pass has warm thread pools and buffers
+                gc.collect()
+                gc.disable()
+                sync_all()
+                ta = time.perf_counter()
+                q_e = scen.quantised(g0, g1, fs, nsamp)
+                tb = time.perf_counter()
+                q_e = seed_own_shard(q_e, nsamp, rank, world, gather)
+                tc = time.perf_counter()
                 if not dry:
                     ctx.set_descriptors(q_e)
+                    td_ = time.perf_counter()
                     ctx.launch(0, nb_e, nsamp, ss, ring.data_ptr(), stride, stream=stream, variant=variant)
+                    torch.cuda.synchronize()
+                else:
+                    td_ = time.perf_counter()
+                te = time.perf_counter()
+                gc.enable()
+                parts = (tb - ta, tc - tb, td_ - tc, te - td_)
+                tot = max_over_ranks(te - ta, dist, device=xdev)
+                if best is None or tot < best[0]:
+                    best = (tot, [max_over_ranks(p, dist, device=xdev) for p in parts])
+            tot, parts = best
+            e2e = {"value": None if dry else round(nb_e * world * nsamp / tot / 1e6, 1), "unit": "Msamples/s",
+                   "blocks_per_gpu": nb_e, "channels": len(scen.svs), "seconds": round(tot, 5),
+                   "x_realtime": None if dry else round(nb_e * world * 0.1 / tot, 1),
+                   "host_refresh_and_quantise_ms": round(parts[0] * 1e3, 2), "seed_exchange_ms": round(parts[1] * 1e3, 2),
+                   "validate_upload_ms": round(parts[2] * 1e3, 2), "kernel_ms": round(parts[3] * 1e3, 2),
+                   "host_cpus": effective_cpus(),
+                   "what": "static receiver (BASELINE config 1/2 geometry), RINEX-derived ephemeris; per rank: RunAhead.seek to its first block, "
+                           "nav words rolled over its 30 s epochs (gpsiq_nav_roll), gpsiq_refresh_epochs_quantized of its own blocks only "
+                           "(refresh and quantiser in one pass), 32 B/channel carrier-seed all-gather, gpsiq_set_descriptors, one gpsiq_launch; slowest rank, best of 2 passes"}
+            # ---- the same chain as a stream of rounds: round m gives this rank the blocks after rank-1's of round m
+            # and after all of round m-1; launches are asynchronous, so the host side of round m+1 (refresh, quantise,
+            # seed exchange on a gloo group, validate + upload into the other descriptor buffer) runs while the GPU is
+            # busy with round m.  What a long scenario costs per block once it is running.
+            R = args.rounds
+            side = None
+            cpu_gather = gather
+            exchange = backend if dist is not None else None
+            if dist is not None:                              # always a side group (also under gloo): one code path, tested on CPU
+                try:                                          # 32 B per channel of host data: a CPU collective, so that it
+                    side = dist.new_group(backend="gloo")     # does not queue behind the kernels on the device
+                    cpu_gather = torch_all_gather_bytes(dist, "cpu", group=side)
+                    exchange = "gloo"
+                except Exception as ex:                       # no gloo here: the RCCL group still gives the right answer
+                    print(f"[bench] no gloo side group ({ex}); seed exchange of the streamed leg over RCCL", file=sys.stderr)
+            best_s = None
+            passes_s = []
+            for _ in range(4):
+                ra, hist = scen.runahead(), []
+                gc.collect()                                   # as timeit does: a full collection takes 35 ms in this process and,
+                gc.disable()                                   # left to itself, lands in the middle of the second pass
+                sync_all()
+                ta = time.perf_counter()
+                host_busy = 0.0
+                for m in range(R):
+                    th = time.perf_counter()
+                    g0 = (m * world + rank) * nb_e
+                    q_e = seed_own_shard(scen.quantised(g0, g0 + nb_e, fs, nsamp, ra=ra), nsamp, rank, world, cpu_gather, history=hist)
+                    host_busy += time.perf_counter() - th
+                    if not dry:
+                        ctx.set_descriptors(q_e)
+                        ctx.launch(0, nb_e, nsamp, ss, ring.data_ptr(), stride, stream=stream, variant=variant)
+                if not dry:
+                    torch.cuda.synchronize()
+                tot_s = max_over_ranks(time.perf_counter() - ta, dist, device=xdev)
+                gc.enable()
+                passes_s.append(round(tot_s, 5))
+                if best_s is None or tot_s < best_s[0]:
+                    best_s = (tot_s, max_over_ranks(host_busy, dist, device=xdev), host_busy)
+            # which side every rank is bound by: its own host time per round (refresh + quantise + seed exchange, with the
+            # threads it was given) against its kernel time per round
+            mine = {"rank": rank, "host_ms_per_round": round(best_s[2] / R * 1e3, 3),
+                    "kernel_ms_per_round": None if dry else round(launch_ms * nb_e / nblocks, 3),
+                    "threads": int(os.environ.get("GPSIQ_THREADS", "0")) or effective_cpus()}
+            mine["bound"] = None if dry else ("host" if mine["host_ms_per_round"] > mine["kernel_ms_per_round"] else "kernel")
+            per_rank = [json.loads(b.decode()) for b in gather(json.dumps(mine).ljust(200).encode())]
+            e2e["streamed"] = {"value": None if dry else round(R * nb_e * world * nsamp / best_s[0] / 1e6, 1), "unit": "Msamples/s",
+                               "per_rank": per_rank,
+                               "bound": None if dry else ("host" if any(r["bound"] == "host" for r in per_rank) else "kernel"),
+                               "rounds": R, "blocks_per_gpu_per_round": nb_e, "seconds": round(best_s[0], 5), "seconds_each_pass": passes_s,
+                               "x_realtime": None if dry else round(R * nb_e * world * 0.1 / best_s[0], 1),
+                               "host_refresh_and_quantise_ms_per_round": round(best_s[1] / R * 1e3, 2), "seed_exchange": exchange,
+                               "what": "the chain above over one continuous timeline in rounds, launches asynchronous: the host side of round "
+                                       "m+1 overlaps the kernel of round m (double-buffered descriptor sets); slowest rank, best of 4 passes"}
+            # the refresh needs ~6 host threads per GPU to stay under the kernel: what this host grants per rank
+            thr = int(os.environ.get("GPSIQ_THREADS", "0")) or effective_cpus()
+            e2e["streamed"]["expected_bound_at_this_host"] = {"threads_per_rank": thr, "threads_needed_per_gpu": 6,
+                                                               "expected": "kernel" if thr >= 6 else "host", "host_share_of_kernel_rate": round(min(1.0, thr / 6.0), 2)}
+            # what the rounds of a long run are bound by on the slowest rank (the serial batch above is host + kernel by construction)
+            e2e["bound"] = e2e["streamed"]["bound"]
+            if world > 1 and not args.no_extra:
+                ref_sharded = reference_sharded_leg(ctx, ring, stream, args, rank, world, dist, cpu_gather, dry, xdev)
             if not dry:
-                torch.cuda.synchronize()
-            tot_s = max_over_ranks(time.perf_counter() - ta, dist, device=xdev)
-            gc.enable()
-            passes_s.append(round(tot_s, 5))
-            if best_s is None or tot_s < best_s[0]:
-                best_s = (tot_s, max_over_ranks(host_busy, dist, device=xdev), host_busy)
-        # which side every rank is bound by: its own host time per round (refresh + quantise + seed exchange, with the
-        # threads it was given) against its kernel time per round
-        mine = {"rank": rank, "host_ms_per_round": round(best_s[2] / R * 1e3, 3),
-                "kernel_ms_per_round": None if dry else round(launch_ms * nb_e / nblocks, 3),
-                "threads": int(os.environ.get("GPSIQ_THREADS", "0")) or effective_cpus()}
-        mine["bound"] = None if dry else ("host" if mine["host_ms_per_round"] > mine["kernel_ms_per_round"] else "kernel")
-        per_rank = [json.loads(b.decode()) for b in gather(json.dumps(mine).ljust(200).encode())]
-        e2e["streamed"] = {"value": None if dry else round(R * nb_e * world * nsamp / best_s[0] / 1e6, 1), "unit": "Msamples/s",
-                           "per_rank": per_rank,
-                           "bound": None if dry else ("host" if any(r["bound"] == "host" for r in per_rank) else "kernel"),
-                           "rounds": R, "blocks_per_gpu_per_round": nb_e, "seconds": round(best_s[0], 5), "seconds_each_pass": passes_s,
-                           "x_realtime": None if dry else round(R * nb_e * world * 0.1 / best_s[0], 1),
-                           "host_refresh_and_quantise_ms_per_round": round(best_s[1] / R * 1e3, 2), "seed_exchange": exchange,
-                           "what": "the chain above over one continuous timeline in rounds, launches asynchronous: the host side of round "
-                                   "m+1 overlaps the kernel of round m (double-buffered descriptor sets); slowest rank, best of 4 passes"}
-        # the refresh needs ~6 host threads per GPU to stay under the kernel: what this host grants per rank
-        thr = int(os.environ.get("GPSIQ_THREADS", "0")) or effective_cpus()
-        e2e["streamed"]["expected_bound_at_this_host"] = {"threads_per_rank": thr, "threads_needed_per_gpu": 6,
-                                                           "expected": "kernel" if thr >= 6 else "host", "host_share_of_kernel_rate": round(min(1.0, thr / 6.0), 2)}
-        # what the rounds of a long run are bound by on the slowest rank (the serial batch above is host + kernel by construction)
-        e2e["bound"] = e2e["streamed"]["bound"]
-        ref_sharded = None
-        if world > 1 and not args.no_extra:
-            ref_sharded = reference_sharded_leg(ctx, ring, stream, args, rank, world, dist, cpu_gather, dry, xdev)
-        if not dry:
-            ctx.set_descriptors(q)
+                ctx.set_descriptors(q)
 
     extra = {}
-    if not dry and rank == 0 and world == 1 and not args.no_extra:
+    if args.full and not dry and rank == 0 and world == 1 and not args.no_extra:
         extra = extra_legs(ctx, ring, stream, args, first)
-    if not dry and world == 1 and os.environ.get("GPSIQ_BENCH_NO_RCCL_SELFTEST", "0") in ("", "0"):
-        # also under --no-extra: the driver's N = 1 run must have executed the collective stack of its N > 1 runs
+    if args.full and not dry and world == 1 and os.environ.get("GPSIQ_BENCH_NO_RCCL_SELFTEST", "0") in ("", "0"):
+        # also under --no-extra: the driver's N = 1 --full run must have executed the collective stack of its N > 1 runs
         extra["rccl_selftest"] = rccl_selftest(dev)
         # and the library still works next to an initialised-and-destroyed RCCL: one more launch, timed
         ctx.set_descriptors(q)                            # the extra legs left their own sets resident
@@ -605,8 +642,9 @@ def main():
                        "host_threads_per_rank": int(os.environ.get("GPSIQ_THREADS", "0")) or effective_cpus(),
                        "preheat_launches": PREHEAT_LAUNCHES, "x_realtime": None if dry else round(value * 1e6 / fs, 1),
                        "host_quantise_own_shard_ms": round(t_q * 1e3, 1)},
-            "end_to_end": e2e,
         }
+        if e2e is not None:
+            out["end_to_end"] = e2e
         if dry:
             out["dry_run"] = True
         else:

@@ -5,7 +5,7 @@ import sys
 
 j = json.loads([ln for ln in open(sys.argv[1]) if ln.startswith("{")][-1])
 n = j["n_gpus"]
-print(f"{n} ranks on ONE MI355X over gloo (GPSIQ_BENCH_SHARE_GPU=1 GPSIQ_BENCH_BACKEND=gloo python bench.py --gpus {n} ...): the N > 1 code path at current code,")
+print(f"{n} ranks on ONE MI355X over gloo (GPSIQ_BENCH_SHARE_GPU=1 GPSIQ_BENCH_BACKEND=gloo python bench.py --full --gpus {n} ...): the N > 1 code path at current code,")
 print("the host side as it is on such a box (every rank its share of the CPU quota), the kernels of the ranks taking turns on the one device --")
 print("readiness evidence, NOT a scaling curve: `value` and every kernel time below are those of a shared device.")
 print(f"value {j['value']} {j['unit']} aggregate, {j['ms_per_step']} ms per step; host threads per rank {j['config']['host_threads_per_rank']}")

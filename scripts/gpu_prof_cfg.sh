@@ -7,7 +7,7 @@ for cfg in "cfg3 10000000" "cfg5 25000000"; do
   set -- $cfg; name=$1; fs=$2
   OUT=$REPO/gpurun_out/prof_$name
   mkdir -p $OUT
-  BENCH="python $REPO/bench.py --no-cpu-baseline --no-extra --launches 6 --steps 10 --fs $fs --sample-size 2"
+  BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-extra --launches 6 --steps 10 --fs $fs --sample-size 2"
   $BENCH > $OUT/bench.json 2> $OUT/bench.err; tail -1 $OUT/bench.json | cut -c1-300
   rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
   rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/pmc_write.log 2>&1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""From a rocprofv3 --kernel-trace of `bench.py --no-cpu-baseline --no-extra --rounds R`: the gaps between the kernels of the
+"""From a rocprofv3 --kernel-trace of `bench.py --full --no-cpu-baseline --no-extra --rounds R`: the gaps between the kernels of the
 streamed end-to-end leg (the last R dispatches of the run = its second pass), i.e. how much of that leg the GPU was busy.
 usage: streamed_gaps.py <dir with kt*/ *.db> <rounds> <tag>"""
 import glob

@@ -89,11 +89,12 @@ def test_iq_buf_layout_is_the_references_field_for_field(tmp_path):
     """gpsiq_iq_buf_t is cast to and from struct iq_buf in the binding (the two fifo
     callbacks): every field must sit where the reference's header (fifo.h:19-25) puts it, and the fifo.h this
     repository ships for C hosts (host/fifo.h) must agree as well.  Compile-time assertions against the
-    reference's own header where it is present."""
+    reference's own header where the oracle build has placed it (oracle/_ref/include/fifo.h)."""
     fields = ["data8", "data16", "totalLength", "validLength", "next"]
     headers = [os.path.join(ROOT, "multi-sdr-gps-sim_amd", "host")]
-    if os.path.exists("/root/reference/fifo.h"):
-        headers.append("/root/reference")
+    ref_inc = os.path.join(ROOT, "oracle", "_ref", "include")
+    if os.path.exists(os.path.join(ref_inc, "fifo.h")):
+        headers.append(ref_inc)
     for k, inc in enumerate(headers):
         src = tmp_path / f"layout{k}.c"
         src.write_text('#include <stddef.h>\n#include "fifo.h"\n#include "gpsiq.h"\n' +

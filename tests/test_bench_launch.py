@@ -18,7 +18,7 @@ def run(args, env_extra=None, timeout=300):
 
 
 def test_gpus_2_starts_two_ranks_by_itself():
-    r = run(["--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--blocks", "30", "--launches", "2"])
+    r = run(["--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "1", "--blocks", "30", "--launches", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                              # rank 0 only
@@ -29,6 +29,22 @@ def test_gpus_2_starts_two_ranks_by_itself():
     e = out["end_to_end"]
     assert e["blocks_per_gpu"] == 30 and e["channels"] == 16 and e["host_refresh_and_quantise_ms"] > 0.0
     assert e["streamed"]["rounds"] == 16 and e["streamed"]["blocks_per_gpu_per_round"] == 30 and e["streamed"]["seconds"] > 0.0
+
+
+def test_plain_run_is_the_timed_steps_only():
+    """Without --full the line holds the headline and what the timed steps give, none of the legs that take runs of their own."""
+    r = run(["--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--blocks", "30", "--launches", "2"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0.0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    for k in ("end_to_end", "cpu_baseline", "extra", "reference_nco"):
+        assert k not in out
+    r = run(["--gpus", "1", "--dry-run", "--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
 
 
 def test_world_size_must_agree_with_gpus():
@@ -49,7 +65,7 @@ def test_more_ranks_than_gpus_is_an_error():
 def test_gpus_8_dry_run_is_one_line_from_eight_ranks():
     """The pre-flight for the driver's 8-GPU run: 8 gloo ranks on this host's cores, one JSON line, n_gpus 8, every rank's
     share of the host threads and its own host time per round reported."""
-    r = run(["--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "1", "--blocks", "24", "--launches", "2", "--rounds", "3"], timeout=600)
+    r = run(["--gpus", "8", "--dry-run", "--full", "--steps", "2", "--warmup", "1", "--blocks", "24", "--launches", "2", "--rounds", "3"], timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -76,7 +92,7 @@ def test_gpus_8_dry_run_is_one_line_from_eight_ranks():
 
 
 def test_collective_selftest_statements_run_over_gloo():
-    """bench.py's default N = 1 run executes rccl_selftest(): the collective stack of its N > 1 branch as a world of one
+    """bench.py's N = 1 --full run executes rccl_selftest(): the collective stack of its N > 1 branch as a world of one
     rank over RCCL, after gpsiq.Context exists.  Here the same statements over gloo (no GPU): init with an explicit
     tcp://127.0.0.1 rendezvous, all_reduce(MAX) float64, all_gather uint8, barrier, a gloo side group, destroy."""
     import sys

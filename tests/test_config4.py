@@ -11,6 +11,7 @@ and all 5 999 blocks; so does the library's OWN host chain (host/gpsiq_runahead.
 words, per-block refresh, every step a C-ABI call) in the same NCO model; in the fixed-point model the run equals the
 oracle and differs from the reference in a counted handful of blocks."""
 import hashlib
+import json
 import os
 import subprocess
 
@@ -41,11 +42,11 @@ def start_time(eph):
 
 
 def test_the_fixture_track_is_the_references_file(cfg4, tmp_path):
-    src = "/root/reference/circle.csv"
-    if not os.path.exists(src):
-        pytest.skip("no /root/reference here")
+    # the reference's circle.csv, recorded as its length and SHA-256 (tests/golden/circle_csv.json)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "circle_csv.json")))
     csv = write_motion_csv(str(tmp_path / "circle.csv"), cfg4["mm"][:cfg4["rows"]])
-    assert open(csv, "rb").read() == open(src, "rb").read()
+    got = open(csv, "rb").read()
+    assert len(got) == want["bytes"] and hashlib.sha256(got).hexdigest() == want["sha256"]
     # and the library's reader gives the doubles readUserMotion's sscanf gives (strtod both: correctly rounded)
     xyz = gpsiq.motion_read_csv(csv, 4000)
     assert xyz.shape == (3000, 3) and np.array_equal(xyz, cfg4["mm"][:3000] / 1000.0)

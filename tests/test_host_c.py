@@ -157,7 +157,7 @@ def test_fifo_header_matches_reference_api():
     for field in ("signed char  *data8", "signed short *data16", "unsigned int  totalLength", "unsigned int  validLength",
                   "struct iq_buf *next"):
         assert field in txt
-    ref = "/root/reference/fifo.h"
+    ref = os.path.join(ROOT, "oracle", "_ref", "include", "fifo.h")      # the reference's header, placed there by the oracle build
     if os.path.exists(ref):      # compile a translation unit that includes BOTH declarations
         # identical prototypes may be repeated in C; conflicting ones are an error
         code = '#include "%s"\n' % os.path.join(HOST, "fifo.h") + "\n".join(

@@ -76,11 +76,10 @@ def test_refresh_batch_is_bit_exact_vs_reference(ref, case):
 
 
 def test_reference_circle_csv_when_present(ref):
-    """BASELINE config 4's motion file (reference circle.csv, 3000 rows of t,x,y,z ECEF)."""
-    path = "/root/reference/circle.csv"
-    if not os.path.exists(path):
-        pytest.skip("reference motion file not on this box")
-    xyz = np.loadtxt(path, delimiter=",")[:601, 1:4]
+    """BASELINE config 4's motion file (reference circle.csv, 3000 rows of t,x,y,z ECEF), from the committed capture
+    (tests/golden/program_config4_circle.npz: the file's positions in whole millimetres, test_config4.py pins them to it)."""
+    from _program import CONFIG4
+    xyz = np.load(CONFIG4)["xyz_mm"][:601] / 1000.0      # the doubles the file's three-decimal text parses to
     eph = synth_constellation(12, xyz[0], SEC, seed=9)
     trk = synth_tracks(12, WEEK, SEC)
     iono = synth_iono()
