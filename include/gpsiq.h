@@ -316,6 +316,32 @@ int gpsiq_launch(gpsiq_ctx_t *ctx, int block0, int nblocks, int nsamp, int sampl
  * resident set may run on several streams at once, and gpsiq_set_descriptors waits for every one of them before it
  * reuses the descriptor buffer they read.) */
 int gpsiq_synchronize(gpsiq_ctx_t *ctx, void *hip_stream);
+/* ---- receiver noise ----------------------------------------------------------------------------------------------------------
+ * An SDR front end adds noise; the reference's output is noiseless.  With noise on, every sample gets (before the store, gps.c:2834-2835)
+ *   I_out = (short)(I + zI(n)), Q_out = (short)(Q + zQ(n))            SC16  (SC08: (signed char)((short)(I + zI(n)) >> 4), same for Q)
+ * wrapping like a large signal does; nothing clips.  zI, zQ are integer functions of (seed, absolute block index B, sample n), so
+ * blocks stay pure functions of their descriptors and shard like them.  All arithmetic mod 2^64 unless stated:
+ *   l = n & 63, j = n >> 6;  X_0 = splitmix64(seed ^ splitmix64(B*64 + l));  X_{j+1} = X_j * 0x5851f42d4c957f2d + 0x14057b7ef767814f
+ *   w = xsh_rr(X_j) (PCG32's output of the state before the step);  zI = z(w & 0xffff), zQ = z(w >> 16)
+ *   z(U): s = U >> 15, m = U & 0x7fff, k = m >> 6, f = m & 63
+ *         mag = k < 511 ? S[k] + (((S[k+1] - S[k]) * f) >> 6) : S_tail[f];   z = s ? -mag : mag
+ *   S[k] = rint((sigma*c) * K[k] * 2^-12), S_tail[f] = rint((sigma*c) * T[f] * 2^-12)   (double arithmetic)
+ * with the committed knots K[k] = rint(4096 Phi^-1(0.5 + (64k + 0.5)/65536)), T[f] = rint(4096 Phi^-1(0.5 + (32704 + f + 0.5)/65536))
+ * and c = 1/sqrt(variance of the 65536 unscaled values) (csrc/gpsiq_noise_knots.h, scripts/gen_noise_knots.py): variance 1, kurtosis
+ * 3.002, tails to 4.32 sigma.  sigma is the standard deviation of each of I and Q in accumulator units (int16 LSB = 1, int8 LSB = 16);
+ * 0 is off (the default); negative, non-finite or > 65536 is GPSIQ_E_ARG.  gpsiq_noise_sigma_for_cn0 (gpsiq_rows.h) converts C/N0.
+ * Block numbering: a drop-in call (gpsiq_generate_block, _async, _batch, _batch_multi, gpsiq_generate_quantized and the seeded call)
+ * renders its block b as B = next_block + b and then adds its nblocks to next_block (_batch_multi: ctx[0]'s settings and counter for
+ * every device); gpsiq_launch renders resident block b as next_block + b and leaves the counter alone.  Only the default kernels,
+ * "tile" and "generic" have the noise path: another variant is GPSIQ_E_STATE while noise is on.  The carrier state is not touched. */
+typedef struct gpsiq_noise {
+    uint64_t seed;
+    double   sigma;
+    uint64_t next_block;   /* absolute index of the next drop-in call's block 0 */
+} gpsiq_noise_t;
+/* NULL turns noise off (the counter is kept). */
+int gpsiq_set_noise(gpsiq_ctx_t *ctx, const gpsiq_noise_t *noise);
+
 /* ---- [boundary] hand-off to fifo.h buffers (gps.c:2847-2865) -------------------------- */
 /* Element-exact restatement of the chunking rules, independent of the FIFO
  * implementation: the caller supplies acquire/enqueue callbacks with the fifo.h

@@ -161,6 +161,10 @@ int gpsiq_rinex_read(const char *path, int version, gpsiq_rinex_eph_t *eph, gpsi
  * satellite whose toc is within one hour of (week, sec); -1 if none. */
 int gpsiq_rinex_select(const gpsiq_rinex_eph_t *eph, int nsets, int week, double sec);
 
+/* Receiver-noise sigma (gpsiq_set_noise, include/gpsiq.h) that puts a channel of this gain at C/N0 = cn0_dbhz dB-Hz at fs Hz:
+ * the carrier table's amplitude is 250, so C = (250*gain)^2 and N0 = 2*sigma^2/fs, i.e. 250*|gain|*sqrt(fs / (2*10^(cn0/10))). */
+double gpsiq_noise_sigma_for_cn0(double cn0_dbhz, double gain, double fs);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -10,6 +10,7 @@
 
 #include "gpsiq_internal.h"
 #include "gpsiq_evalctl.h"
+#include "gpsiq_noise.h"
 
 struct gpsiq_ctx {
     int           device = -1;
@@ -53,6 +54,15 @@ struct gpsiq_ctx {
     int            max_active = 0;      // most active channels in any resident block
     long           max_amplitude = 0;   // largest sum over a block's channels of (int)(250*|gain|): bound on |I|, |Q|
     int            nco_mode = GPSIQ_NCO_FIXED;
+    // receiver noise (gpsiq_set_noise): on while sigma > 0; next_block is the absolute index the next drop-in call's block 0
+    // gets, call_block that of the running call's block 0 (every path of the call numbers its blocks from it)
+    struct Noise {
+        uint64_t seed = 0, next_block = 0;
+        double   sigma = 0.0;
+        long     max_z = 0;                            // S_tail[63] = max |z|
+        gpsiq::noise::Entry *d_tab = nullptr;          // gpsiq::noise::kTabEntries, on the context's device
+    } noise;
+    uint64_t       call_block = 0;
     // scratch of the kernel variants that need some (segm: the sign masks of one launch)
     void          *d_scratch = nullptr;
     size_t         scratch_cap = 0;
@@ -125,6 +135,8 @@ struct gpsiq_ctx {
 
 
 // helpers of gpsiq_device.cpp the other translation unit uses
+// the noise of launches whose descriptor array starts at absolute block `block` (tab == nullptr while noise is off)
+gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
 double gpsiq_wall_ms();
 int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b);
 int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s);
@@ -145,11 +157,12 @@ void gpsiq_evaldev_destroy(gpsiq_ctx *c);
 namespace gpsiq {
 hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size,
                           void *dst, size_t block_stride, int block0, int nblocks,
-                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch);
+                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch,
+                          const noise::Launch &nz);
 size_t variant_scratch_bytes(int variant, int nsamp, int nblocks);
 hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size, void *dst, size_t block_stride,
                           int block0, int nblocks, const DeviceTables *tab, const gpsiq_patch_t *patches, int npatch,
-                          hipStream_t stream);
+                          hipStream_t stream, const noise::Launch &nz);
 hipError_t launch_chain(const void *d_in, int in_stride, int nblocks, int nchan, double delt, int nsamp, const gpsiq_chain_est_t *d_start,
                         int max_seg, void *d_prep, double *d_c_before, gpsiq_chain_est_t *d_end, void *d_maps, hipStream_t stream, int which = 3);
 int chain_link(const gpsiq_chain_in_t *in, const void *maps, int nblocks, int nchan, double delt, int nsamp,

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gpsiq_ctx.h"
+#include "gpsiq_noise_knots.h"
 
 using namespace gpsiq;
 
@@ -70,6 +71,21 @@ static int ensure_out(gpsiq_ctx *c, size_t bytes)
     return GPSIQ_OK;
 }
 
+// The scaled noise table (include/gpsiq.h, "Receiver noise"): S[k] = rint((sigma*c) * K[k] * 2^-12), the same for the tail, in
+// double arithmetic that is exact here and in numpy (the library builds with -ffp-contract=off).
+static long noise_table(double sigma, gpsiq::noise::Entry *tab)
+{
+    const double s = sigma * GPSIQ_NOISE_C;
+    int32_t S[512];
+    for (int k = 0; k < 512; ++k) S[k] = (int32_t) std::rint(s * (double) gpsiq_noise_K[k] * 0x1p-12);
+    for (int k = 0; k < 511; ++k) tab[k] = {S[k], S[k + 1] - S[k]};
+    for (int f = 0; f < 64; ++f) tab[511 + f] = {(int32_t) std::rint(s * (double) gpsiq_noise_T[f] * 0x1p-12), 0};
+    for (int e = gpsiq::noise::kEntries; e < gpsiq::noise::kTabEntries; ++e) tab[e] = {0, 0};
+    return tab[gpsiq::noise::kEntries - 1].base;
+}
+
+static bool noise_variant_ok(int v) { return v == kAuto || v == kGeneric || v == kTile || v == kSeg || v == kSegHalf; }
+
 static int pick_variant(const gpsiq_ctx *c, int variant)
 {
     if (variant == kAuto)
@@ -90,6 +106,8 @@ static int check_launch(const gpsiq_ctx *c, int block0, int nblocks, int nsamp, 
     if (stride < (size_t) 2 * (size_t) nsamp * (size_t) sample_size || (stride & 3))
         return fail(GPSIQ_E_ARG, "block stride %zu too small or not a multiple of 4", stride);
     if (variant < 0 || variant >= kNumVariants) return fail(GPSIQ_E_ARG, "unknown variant %d", variant);
+    if (c->noise.sigma > 0.0 && !noise_variant_ok(variant))
+        return fail(GPSIQ_E_STATE, "variant %d has no receiver-noise path: turn noise off (gpsiq_set_noise) or use 0/generic/tile/seg/segh", variant);
     if (variant == kSegHalf && c->max_code_step > kHalfRowsMaxCodeStep)
         return fail(GPSIQ_E_RANGE, "half-row kernel needs f_code/fs <= 1 chip per sample");
     if (variant >= kRows && variant != kSegHalf && c->max_code_step > kRowsMaxCodeStep)
@@ -177,6 +195,7 @@ void gpsiq_destroy(gpsiq_ctx_t *c)
     for (auto &e : c->chain.walked) if (e) (void) hipEventDestroy(e);
     if (c->chain.back) (void) hipStreamDestroy(c->chain.back);
     if (c->chain.stream) (void) hipStreamDestroy(c->chain.stream);
+    if (c->noise.d_tab) (void) hipFree(c->noise.d_tab);
     if (c->stream) (void) hipStreamDestroy(c->stream);
     if (c->stream2) (void) hipStreamDestroy(c->stream2);
     if (c->up_stream) (void) hipStreamDestroy(c->up_stream);
@@ -368,8 +387,11 @@ int gpsiq_set_nco_mode(gpsiq_ctx_t *c, int mode)
 }
 
 // kernel + patches of blocks [block0, block0+nblocks) on stream s; marks the descriptor buffer as in use
-static int launch_on(gpsiq_ctx *c, int v, int block0, int nblocks, int nsamp, int sample_size, void *dst, size_t stride, hipStream_t s)
+// (nbase: absolute block index of the resident set's block 0, for the receiver noise)
+static int launch_on(gpsiq_ctx *c, int v, int block0, int nblocks, int nsamp, int sample_size, void *dst, size_t stride, hipStream_t s,
+                     uint64_t nbase)
 {
+    const gpsiq::noise::Launch nz = gpsiq_noise_at(c, nbase);
     const size_t need = variant_scratch_bytes(v, nsamp, nblocks);
     if (need > c->scratch_cap) {
         // growing is rare (the first launch of a shape); hipFree waits for whatever still uses the old buffer
@@ -380,22 +402,30 @@ static int launch_on(gpsiq_ctx *c, int v, int block0, int nblocks, int nsamp, in
     }
     if (c->buf[c->cur].upload_pending) HIP_TRY(hipStreamWaitEvent(s, c->buf[c->cur].uploaded, 0));    // a set staged without waiting
     hipError_t e = launch_variant(v, c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, s,
-                                  c->max_active, c->max_amplitude, need ? c->d_scratch : nullptr);
+                                  c->max_active, c->max_amplitude, need ? c->d_scratch : nullptr, nz);
     if (e == hipSuccess && c->buf[c->cur].npatch)
         e = launch_patches(c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, c->buf[c->cur].d_patch,
-                           c->buf[c->cur].npatch, s);
+                           c->buf[c->cur].npatch, s, nz);
     if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "launch: %s", hipGetErrorString(e));
     if (nblocks > 0 && nsamp > 0) return mark_use(c->buf[c->cur], s);
     return GPSIQ_OK;
 }
 
-int gpsiq_launch(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int sample_size,
-                 void *dst, size_t block_stride_bytes, void *hip_stream, int variant)
+static int launch_abs(gpsiq_ctx *c, int block0, int nblocks, int nsamp, int sample_size, void *dst, size_t block_stride_bytes,
+                      hipStream_t s, int variant, uint64_t nbase)
 {
     int rc = check_launch(c, block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, variant);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    return launch_on(c, pick_variant(c, variant), block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, (hipStream_t) hip_stream);
+    return launch_on(c, pick_variant(c, variant), block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, s, nbase);
+}
+
+// an explicit launch renders resident block b as absolute block next_block + b and leaves the counter alone (it can be repeated)
+int gpsiq_launch(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int sample_size,
+                 void *dst, size_t block_stride_bytes, void *hip_stream, int variant)
+{
+    return launch_abs(c, block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, (hipStream_t) hip_stream, variant,
+                      c ? c->noise.next_block : 0);
 }
 
 int gpsiq_synchronize(gpsiq_ctx_t *c, void *hip_stream)
@@ -422,7 +452,7 @@ int gpsiq_time_launches(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int 
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, s);
     for (int i = 0; i < iters && e == hipSuccess && rc == GPSIQ_OK; ++i)
-        rc = launch_on(c, v, block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, s);
+        rc = launch_on(c, v, block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, s, c->noise.next_block);
     if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventRecord(e1, s);
     if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventSynchronize(e1);
     if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventElapsedTime(&ms, e0, e1);
@@ -465,8 +495,9 @@ static int d2h_chunk_blocks(size_t stride)
     return (int) (n < 8 ? 8 : n);
 }
 
+// (nbase: absolute block index of q[0], for the receiver noise)
 static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nblocks, int nchan,
-                                 int nsamp, int sample_size, void *dst, int dst_is_device)
+                                 int nsamp, int sample_size, void *dst, int dst_is_device, uint64_t nbase)
 {
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size;
     const size_t stride = (blk_bytes + 15) & ~(size_t) 15;
@@ -474,7 +505,7 @@ static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nbloc
     if (rc) return rc;
     if (!nblocks || !nsamp) return GPSIQ_OK;
     if (dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3)) {
-        rc = gpsiq_launch(c, 0, nblocks, nsamp, sample_size, dst, stride, c->stream, kAuto);
+        rc = launch_abs(c, 0, nblocks, nsamp, sample_size, dst, stride, c->stream, kAuto, nbase);
         if (rc) return rc;
         return gpsiq_synchronize(c, c->stream);
     }
@@ -483,7 +514,7 @@ static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nbloc
     const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const int chunk = d2h_chunk_blocks(stride);
     if (dst_is_device || chunk <= 0 || nblocks <= chunk) {
-        rc = gpsiq_launch(c, 0, nblocks, nsamp, sample_size, c->d_out, stride, c->stream, kAuto);
+        rc = launch_abs(c, 0, nblocks, nsamp, sample_size, c->d_out, stride, c->stream, kAuto, nbase);
         if (rc) return rc;
         if (stride == blk_bytes)
             HIP_TRY(hipMemcpyAsync(dst, c->d_out, blk_bytes * (size_t) nblocks, kind, c->stream));
@@ -501,7 +532,7 @@ static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nbloc
     for (int b0 = 0; b0 < nblocks && rc == GPSIQ_OK && e == hipSuccess; b0 += chunk, ++k) {
         const int nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
         uint8_t *piece = static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
-        rc = gpsiq_launch(c, b0, nb, nsamp, sample_size, piece, stride, c->stream, kAuto);
+        rc = launch_abs(c, b0, nb, nsamp, sample_size, piece, stride, c->stream, kAuto, nbase);
         if (rc) break;
         hipStream_t cs = c->copy_stream[k & 1];
         what = "piece hand-over";
@@ -581,10 +612,11 @@ struct RefRender {
     bool dst_is_device = false, direct = false;
     size_t blk_bytes = 0, stride = 0;
     int k = 0, npiece = 0;
+    uint64_t nbase = 0;              // absolute block index of the range's first block (receiver noise)
 
-    int begin(gpsiq_ctx *ctx, int range_blocks, int nchan_, int nsamp_, int ss_, void *dst_, int dst_is_device_)
+    int begin(gpsiq_ctx *ctx, int range_blocks, int nchan_, int nsamp_, int ss_, void *dst_, int dst_is_device_, uint64_t nbase_)
     {
-        c = ctx; nchan = nchan_; nsamp = nsamp_; ss = ss_; dst = static_cast<uint8_t *>(dst_); dst_is_device = dst_is_device_ != 0; k = 0; npiece = 0;
+        c = ctx; nbase = nbase_; nchan = nchan_; nsamp = nsamp_; ss = ss_; dst = static_cast<uint8_t *>(dst_); dst_is_device = dst_is_device_ != 0; k = 0; npiece = 0;
         blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) ss;
         stride = (blk_bytes + 15) & ~(size_t) 15;
         direct = dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3);
@@ -601,7 +633,7 @@ struct RefRender {
         if (!nb || !nsamp) return GPSIQ_OK;
         uint8_t *dev = direct ? dst + (size_t) b0 * blk_bytes : static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
         hipStream_t s = piece_stream(c, npiece++);
-        rc = gpsiq_launch(c, 0, nb, nsamp, ss, dev, stride, s, kAuto);
+        rc = launch_abs(c, 0, nb, nsamp, ss, dev, stride, s, kAuto, nbase + (uint64_t) b0);
         if (rc || direct) return rc;
         hipStream_t cs = c->copy_stream[k & 1];
         HIP_TRY(hipEventRecord(c->chunk_done[k & 1], s));
@@ -861,7 +893,7 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
     if (!seeds && c->ref_start.size() < (size_t) nblocks * (size_t) nchan) c->ref_start.resize((size_t) nblocks * (size_t) nchan);
     std::vector<gpsiq_patch_t> patches;
     RefRender r;
-    int rc = r.begin(c, nblocks, nchan, nsamp, sample_size, dst, dst_is_device);
+    int rc = r.begin(c, nblocks, nchan, nsamp, sample_size, dst, dst_is_device, c->call_block);
     if (rc) return rc;
     const int chunk = ref_chunk_blocks(nblocks, nsamp);
     std::vector<int> ends;
@@ -980,6 +1012,7 @@ int gpsiq_generate_block(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan, int 
     std::memcpy(carry0, c->carry, sizeof carry0);
     std::memcpy(prn0, c->carry_prn, sizeof prn0);
     std::memcpy(handed0, c->handed, sizeof handed0);
+    const uint64_t next0 = c->noise.next_block;
     const int slot = c->anext;
     rc = gpsiq_generate_block_async(c, ch, nchan, nsamp, fs, sample_size, dst, carr_phase_out);
     if (rc) return rc;
@@ -991,6 +1024,7 @@ int gpsiq_generate_block(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan, int 
             std::memcpy(c->carry, carry0, sizeof carry0);
             std::memcpy(c->carry_prn, prn0, sizeof prn0);
             std::memcpy(c->handed, handed0, sizeof handed0);
+            c->noise.next_block = next0;
             return fail(GPSIQ_E_DEVICE, "block: %s", hipGetErrorString(e));
         }
     }
@@ -1064,11 +1098,12 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
         // once the first copy is queued a failure must not return with work in flight on the slot's page-locked staging (the next
         // call would rewrite it under the copy): the stream is drained first
         hipError_t e = hipMemcpyAsync(a.d, a.h, (size_t) nchan * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = launch_variant(v, a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, c->stream, na, amp, nullptr);
+        const gpsiq::noise::Launch nz = gpsiq_noise_at(c, c->noise.next_block);
+        if (e == hipSuccess) e = launch_variant(v, a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, c->stream, na, amp, nullptr, nz);
         if (e == hipSuccess && !patches.empty()) {
             std::memcpy(a.h_patch, patches.data(), patches.size() * sizeof(gpsiq_patch_t));
             e = hipMemcpyAsync(a.d_patch, a.h_patch, patches.size() * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = launch_patches(a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, a.d_patch, (int) patches.size(), c->stream);
+            if (e == hipSuccess) e = launch_patches(a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, a.d_patch, (int) patches.size(), c->stream, nz);
         }
         if (e == hipSuccess) e = hipMemcpyAsync(dst, a.out, blk_bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipEventRecord(a.done, c->stream);
@@ -1079,6 +1114,7 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
         a.busy = true;
         c->anext = (c->anext + 1) & 3;
     }
+    ++c->noise.next_block;                                   // the block was rendered as absolute block next_block
     for (int i = 0; i < nchan; ++i) {
         if (reference) {
             if (carr_phase_out) carr_phase_out[i] = last_prn[i] ? carr_end[i] : ch[i].carr_phase;
@@ -1107,15 +1143,32 @@ int gpsiq_generate_quantized(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblocks
     int rc = check_gen_args(c, q, dst, nblocks, nchan, nsamp, 1.0, sample_size);
     if (rc) return rc;
     if (nblocks == 0) return GPSIQ_OK;
-    return run_to_host_or_device(c, q, nblocks, nchan, nsamp, sample_size, dst, dst_is_device);
+    rc = run_to_host_or_device(c, q, nblocks, nchan, nsamp, sample_size, dst, dst_is_device, c->noise.next_block);
+    if (rc == GPSIQ_OK) c->noise.next_block += (uint64_t) nblocks;
+    return rc;
 }
 
+static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
+                          double fs, int sample_size, void *dst, int dst_is_device, double *carr_phase_out);
+
+// A drop-in call renders its block b as absolute block next_block + b (receiver noise) on whichever path it takes, and moves
+// next_block on by nblocks when it succeeds.
 int gpsiq_generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
                          double fs, int sample_size, void *dst, int dst_is_device, double *carr_phase_out)
 {
     int rc = check_gen_args(c, ch, dst, nblocks, nchan, nsamp, fs, sample_size);
     if (rc) return rc;
     if (nblocks == 0) return GPSIQ_OK;                    // an empty batch leaves the carried phases alone
+    c->call_block = c->noise.next_block;
+    rc = generate_batch(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out);
+    if (rc == GPSIQ_OK) c->noise.next_block += (uint64_t) nblocks;
+    return rc;
+}
+
+static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
+                          double fs, int sample_size, void *dst, int dst_is_device, double *carr_phase_out)
+{
+    int rc = GPSIQ_OK;
     {   // descriptors quantised / evaluated on the device (gpsiq_evaldev.cpp) where that path takes the call
         int handled = 0;
         rc = gpsiq_generate_device(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out, nullptr, &handled);
@@ -1162,7 +1215,8 @@ int gpsiq_generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, in
             const double tq1 = trace_pieces ? wall_ms() : 0.0;
             if (rc == GPSIQ_OK) rc = set_descriptors_impl(c, q.data(), nb, nchan, nullptr, 0, true);
             const double tq2 = trace_pieces ? wall_ms() : 0.0;
-            if (rc == GPSIQ_OK) rc = gpsiq_launch(c, 0, nb, nsamp, sample_size, static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, blk_bytes, piece_stream(c, (int) k), kAuto);
+            if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nb, nsamp, sample_size, static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, blk_bytes, piece_stream(c, (int) k), kAuto,
+                                                c->call_block + (uint64_t) b0);
             if (trace_pieces)
                 std::fprintf(stderr, "[gpsiq trace]   piece %zu, blocks [%d, %d): quantise from %.3f to %.3f ms, descriptors queued at %.3f, launched at %.3f\n",
                              k, b0, b0 + nb, tq0 - t0, tq1 - t0, tq2 - t0, wall_ms() - t0);
@@ -1189,7 +1243,7 @@ int gpsiq_generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, in
         int qrc = quantize_timeline(ch, nblocks, nchan, 1.0 / fs, nsamp, cont0, c->carry, q.data(), carry, prev_prn);
         if (qrc) return qrc;
         const double t2 = trace ? wall_ms() : 0.0;
-        rc = run_to_host_or_device(c, q.data(), nblocks, nchan, nsamp, sample_size, dst, dst_is_device);
+        rc = run_to_host_or_device(c, q.data(), nblocks, nchan, nsamp, sample_size, dst, dst_is_device, c->call_block);
         if (rc) return rc;
         if (trace)
             std::fprintf(stderr, "[gpsiq trace] batch %d blocks: quantise + carrier prefix %.2f ms, upload+kernel%s %.2f ms\n",
@@ -1213,17 +1267,54 @@ int gpsiq_generate_seeded(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
     if (nblocks == 0) return GPSIQ_OK;
     for (size_t k = 0; k < (size_t) nblocks * (size_t) nchan; ++k)
         if (ch[k].prn > 0 && !(carr_start[k] >= 0.0 && carr_start[k] <= 1.0)) return fail(GPSIQ_E_RANGE, "start phase %zu outside [0, 1]", k);
-    {
-        int handled = 0;
-        rc = gpsiq_generate_device(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start, &handled);
-        if (handled) return rc;
-    }
-    return generate_reference(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start);
+    c->call_block = c->noise.next_block;
+    int handled = 0;
+    rc = gpsiq_generate_device(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start, &handled);
+    if (!handled) rc = generate_reference(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start);
+    if (rc == GPSIQ_OK) c->noise.next_block += (uint64_t) nblocks;
+    return rc;
 }
 
+static int set_noise_impl(gpsiq_ctx *c, uint64_t seed, double sigma);
+static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
+                                int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
+                                double *carr_phase_out);
+
+// Every range is rendered with ctx[0]'s noise settings and numbering (device i from next_block + begin_i): the other contexts
+// take ctx[0]'s seed and sigma for the call and get their own back after it.
 int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
                                int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
                                double *carr_phase_out)
+{
+    bool listed = ctx && ndev >= 1 && ndev <= 64;
+    for (int i = 0; listed && i < ndev; ++i) listed = ctx[i] != nullptr;
+    if (!listed || nblocks <= 0)
+        return generate_batch_multi(ctx, ndev, ch, nblocks, nchan, nsamp, fs, sample_size, host_dst, dev_dst, carr_phase_out);
+    const gpsiq_ctx::Noise &n0 = ctx[0]->noise;
+    std::vector<gpsiq_ctx::Noise> own((size_t) ndev);
+    int rc = GPSIQ_OK;
+    for (int i = 1; i < ndev && rc == GPSIQ_OK; ++i) {
+        own[(size_t) i] = ctx[i]->noise;
+        if (ctx[i]->noise.seed != n0.seed || ctx[i]->noise.sigma != n0.sigma) rc = set_noise_impl(ctx[i], n0.seed, n0.sigma);
+    }
+    if (rc == GPSIQ_OK)
+        rc = generate_batch_multi(ctx, ndev, ch, nblocks, nchan, nsamp, fs, sample_size, host_dst, dev_dst, carr_phase_out);
+    if (rc == GPSIQ_OK) ctx[0]->noise.next_block += (uint64_t) nblocks;
+    for (int i = 1; i < ndev; ++i) {
+        const gpsiq_ctx::Noise &o = own[(size_t) i];
+        if (ctx[i]->noise.seed != o.seed || ctx[i]->noise.sigma != o.sigma) {
+            char err[400];
+            std::snprintf(err, sizeof err, "%s", gpsiq_last_error());
+            const int rrc = set_noise_impl(ctx[i], o.seed, o.sigma);
+            if (rc == GPSIQ_OK) rc = rrc; else (void) set_error(rc, err);
+        }
+    }
+    return rc;
+}
+
+static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
+                                int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
+                                double *carr_phase_out)
 {
     if (!ctx || ndev < 1 || ndev > 64) return fail(GPSIQ_E_ARG, "bad device list");
     for (int i = 0; i < ndev; ++i) {
@@ -1250,7 +1341,7 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
         // owns it; device i starts as soon as the walk reaches its range, and renders under the walk of what follows.
         struct Item { const gpsiq_qchan_t *q; int b0, nb; std::vector<gpsiq_patch_t> patches; };
         struct Dev {
-            gpsiq_ctx *c; int range_blocks, nchan, nsamp, ss; void *dst; int dst_is_device;
+            gpsiq_ctx *c; int range_blocks, nchan, nsamp, ss; void *dst; int dst_is_device; uint64_t nbase;
             pthread_mutex_t mu; pthread_cond_t cv; std::deque<Item> items; bool closed;
             int rc; char err[256]; pthread_t th; bool started;
         };
@@ -1258,7 +1349,7 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
         auto body = [](void *arg) -> void * {
             Dev &d = *static_cast<Dev *>(arg);
             RefRender r;
-            d.rc = r.begin(d.c, d.range_blocks, d.nchan, d.nsamp, d.ss, d.dst, d.dst_is_device);
+            d.rc = r.begin(d.c, d.range_blocks, d.nchan, d.nsamp, d.ss, d.dst, d.dst_is_device, d.nbase);
             if (d.rc != GPSIQ_OK) std::snprintf(d.err, sizeof d.err, "%s", gpsiq_last_error());
             for (;;) {
                 pthread_mutex_lock(&d.mu);
@@ -1282,6 +1373,7 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
             d.c = ctx[i]; d.range_blocks = b1 - b0; d.nchan = nchan; d.nsamp = nsamp; d.ss = sample_size;
             d.dst = host_dst ? (void *) (static_cast<uint8_t *>(host_dst) + (size_t) b0 * blk_bytes) : dev_dst[i];
             d.dst_is_device = host_dst ? 0 : 1;
+            d.nbase = c0->noise.next_block + (uint64_t) b0;          // ctx[0]'s numbering (and noise settings) for every range
             pthread_mutex_init(&d.mu, nullptr); pthread_cond_init(&d.cv, nullptr);
             d.closed = false; d.rc = GPSIQ_OK; d.err[0] = 0;
             d.started = d.range_blocks > 0 && pthread_create(&d.th, nullptr, body, &d) == 0;
@@ -1374,7 +1466,7 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
     }
     if (rc) return rc;
     // one host thread per context; each renders its own contiguous range
-    struct Part { gpsiq_ctx *c; const gpsiq_qchan_t *q; int nb, nchan, nsamp, ss; void *dst; int dst_is_device;
+    struct Part { gpsiq_ctx *c; const gpsiq_qchan_t *q; int nb, nchan, nsamp, ss; void *dst; int dst_is_device; uint64_t nbase;
                   int rc; char err[256]; pthread_t th; bool started; };
     std::vector<Part> parts((size_t) ndev);
     for (int i = 0; i < ndev; ++i) {
@@ -1384,12 +1476,13 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
         p.c = ctx[i]; p.q = q.data() + (size_t) b0 * nchan; p.nb = b1 - b0; p.nchan = nchan; p.nsamp = nsamp; p.ss = sample_size;
         p.dst = host_dst ? (void *) (static_cast<uint8_t *>(host_dst) + (size_t) b0 * blk_bytes) : dev_dst[i];
         p.dst_is_device = host_dst ? 0 : 1;
+        p.nbase = c0->noise.next_block + (uint64_t) b0;
         p.rc = GPSIQ_OK; p.err[0] = 0; p.started = false;
     }
     auto body = [](void *arg) -> void * {
         Part &p = *static_cast<Part *>(arg);
         if (p.nb > 0) {
-            p.rc = run_to_host_or_device(p.c, p.q, p.nb, p.nchan, p.nsamp, p.ss, p.dst, p.dst_is_device);
+            p.rc = run_to_host_or_device(p.c, p.q, p.nb, p.nchan, p.nsamp, p.ss, p.dst, p.dst_is_device, p.nbase);
             if (p.rc != GPSIQ_OK) std::snprintf(p.err, sizeof p.err, "%s", gpsiq_last_error());
         }
         return nullptr;
@@ -1412,7 +1505,85 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
     return GPSIQ_OK;
 }
 
+// ---- receiver noise --------------------------------------------------------------------------------------------------------
+// (the device table is replaced only when the device is idle: launches still queued read the one they were given)
+static int set_noise_impl(gpsiq_ctx *c, uint64_t seed, double sigma)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    if (sigma > 0.0) {
+        gpsiq::noise::Entry tab[gpsiq::noise::kTabEntries];
+        const long max_z = noise_table(sigma, tab);
+        if (!c->noise.d_tab) HIP_TRY(hipMalloc(&c->noise.d_tab, sizeof tab));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(c->noise.d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+        c->noise.max_z = max_z;
+    } else {
+        c->noise.max_z = 0;
+    }
+    c->noise.seed = seed;
+    c->noise.sigma = sigma > 0.0 ? sigma : 0.0;
+    return GPSIQ_OK;
+}
+
+static int check_sigma(double sigma)
+{
+    if (!(std::isfinite(sigma) && sigma >= 0.0 && sigma <= 65536.0))
+        return fail(GPSIQ_E_ARG, "noise sigma %g outside [0, 65536]", sigma);
+    return GPSIQ_OK;
+}
+
+int gpsiq_set_noise(gpsiq_ctx_t *c, const gpsiq_noise_t *nz)
+{
+    if (!c) return fail(GPSIQ_E_ARG, "null context");
+    if (!nz) return set_noise_impl(c, 0, 0.0);
+    int rc = check_sigma(nz->sigma);
+    if (rc) return rc;
+    rc = set_noise_impl(c, nz->seed, nz->sigma);
+    if (rc == GPSIQ_OK) c->noise.next_block = nz->next_block;
+    return rc;
+}
+
+int gpsiq_noise_state(const gpsiq_ctx_t *c, gpsiq_noise_t *out)
+{
+    if (!c || !out) return fail(GPSIQ_E_ARG, "null argument");
+    out->seed = c->noise.seed;
+    out->sigma = c->noise.sigma;
+    out->next_block = c->noise.next_block;
+    return GPSIQ_OK;
+}
+
+int gpsiq_noise_host(uint64_t seed, double sigma, uint64_t block, int nsamp, int32_t *iq)
+{
+    if ((!iq && nsamp > 0) || nsamp < 0) return fail(GPSIQ_E_ARG, "bad noise buffer");
+    int rc = check_sigma(sigma);
+    if (rc) return rc;
+    gpsiq::noise::Entry tab[gpsiq::noise::kTabEntries];
+    noise_table(sigma, tab);
+    for (uint32_t l = 0; l < 64u && l < (uint32_t) nsamp; ++l) {                // lane-major: one stream at a time
+        uint64_t x = gpsiq::noise::lane_start(seed, block, l);
+        for (uint32_t n = l; n < (uint32_t) nsamp; n += 64u) {
+            const uint32_t w = gpsiq::noise::xsh_rr(x);
+            x = x * gpsiq::noise::kMul + gpsiq::noise::kInc;
+            iq[2 * (size_t) n] = gpsiq::noise::z(tab, w & 0xffffu);
+            iq[2 * (size_t) n + 1] = gpsiq::noise::z(tab, w >> 16);
+        }
+    }
+    return GPSIQ_OK;
+}
+
 }  // extern "C"
+
+gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
+{
+    gpsiq::noise::Launch nz;
+    if (c->noise.sigma > 0.0) {
+        nz.tab = c->noise.d_tab;
+        nz.seed = c->noise.seed;
+        nz.block = block;
+        nz.max_z = c->noise.max_z;
+    }
+    return nz;
+}
 
 // ---- what gpsiq_evaldev.cpp uses of this file ---------------------------------------------------------------------------------
 double gpsiq_wall_ms() { return wall_ms(); }
@@ -1443,7 +1614,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         GPSIQ_P(gpsiq_chain_maps), GPSIQ_P(gpsiq_chain_link), GPSIQ_P(gpsiq_chain_summary), GPSIQ_P(gpsiq_chain_fold), GPSIQ_P(gpsiq_chain_stats),
         GPSIQ_P(gpsiq_chain_maps_device), GPSIQ_P(gpsiq_chain_range), GPSIQ_P(gpsiq_chain_range_fold), GPSIQ_P(gpsiq_time_launches), GPSIQ_P(gpsiq_num_variants), GPSIQ_P(gpsiq_variant_name),
         GPSIQ_P(gpsiq_device_eval_stats), GPSIQ_P(gpsiq_device_eval_host_ms),
-        GPSIQ_P(gpsiq_prn_code), GPSIQ_P(gpsiq_carrier_table), GPSIQ_P(gpsiq_generate_seeded),
+        GPSIQ_P(gpsiq_prn_code), GPSIQ_P(gpsiq_carrier_table), GPSIQ_P(gpsiq_generate_seeded), GPSIQ_P(gpsiq_noise_state), GPSIQ_P(gpsiq_noise_host),
 #undef GPSIQ_P
         // the internals libgpsiq_rows.so runs on (gpsiq_rows_link.cpp): one pool, one quantiser, one error text per thread
         {"set_error", reinterpret_cast<void *>(&gpsiq::set_error)}, {"parallel_for", reinterpret_cast<void *>(&gpsiq::parallel_for)},

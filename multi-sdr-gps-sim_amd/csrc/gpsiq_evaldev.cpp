@@ -400,7 +400,8 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
             uint8_t *dev = direct ? static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes : static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
             // the last piece's synthesis is timed: the rate the piece sizes are planned with is a measured one (gpsiq_note_kernel_rate)
             if (k == npieces - 1) (void) hipEventRecord(e.t_synth0, s);
-            he = launch_variant(v, nb_.d, nchan, nsamp, sample_size, dev, stride, b0, nb, c->d_tab, s, max_active > 0 ? max_active : 1, max_amp, nullptr);
+            he = launch_variant(v, nb_.d, nchan, nsamp, sample_size, dev, stride, b0, nb, c->d_tab, s, max_active > 0 ? max_active : 1, max_amp, nullptr,
+                                gpsiq_noise_at(c, c->call_block));
             if (k == npieces - 1) { (void) hipEventRecord(e.t_synth1, s); timed_blocks = nb; }
             if (trace && k == 0) t_first_launch = gpsiq_wall_ms() - t0;
             if (he == hipSuccess && !direct) {
@@ -628,7 +629,8 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
                 he = hipMemcpyAsync(nb_.d_patch, e.h_patches, npatch_total * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);
             }
             uint8_t *dev = direct ? static_cast<uint8_t *>(dst) : static_cast<uint8_t *>(c->d_out);
-            if (he == hipSuccess) he = launch_patches(nb_.d, nchan, nsamp, sample_size, dev, stride, 0, nblocks, c->d_tab, nb_.d_patch, (int) npatch_total, c->stream);
+            if (he == hipSuccess) he = launch_patches(nb_.d, nchan, nsamp, sample_size, dev, stride, 0, nblocks, c->d_tab, nb_.d_patch, (int) npatch_total, c->stream,
+                                                       gpsiq_noise_at(c, c->call_block));
         }
         if (he == hipSuccess && !direct && npatch_total) {
             // the blocks apply_patches touched go to the destination again -- behind the pieces' own copies, which may still be

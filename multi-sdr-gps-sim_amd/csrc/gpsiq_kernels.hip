@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "gpsiq_internal.h"
+#include "gpsiq_noise.h"
 
 namespace gpsiq {
 
@@ -83,7 +84,7 @@ template <int FMT>
 __global__ __launch_bounds__(kGenericThreads) void synth_generic(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
     size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
-    int tile_samples)
+    int tile_samples, const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
 {
     __shared__ uint32_t lut[kMaxChan][512];
     __shared__ uint32_t ext[kMaxChan][kPrnExtWords];
@@ -97,8 +98,23 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
     uint32_t n_end = n_begin + (uint32_t) tile_samples;
     if (n_end > (uint32_t) nsamp) n_end = (uint32_t) nsamp;
 
+    // noise (ntab != nullptr): a thread keeps one lane stream (tile_samples and the stride are multiples of 64) and moves
+    // kGenericThreads/64 rows per step
+    uint64_t nx = 0, nA = 0, nC = 0;
+    if (ntab) {
+        const uint32_t n = n_begin + threadIdx.x;
+        noise::jump(n >> 6, noise::kMul, noise::kInc, &nA, &nC);
+        nx = nA * noise::lane_start(nseed, nblock0 + (uint64_t) (block0 + blk), n & 63u) + nC;
+        noise::jump(kGenericThreads / 64, noise::kMul, noise::kInc, &nA, &nC);
+    }
     for (uint32_t n = n_begin + threadIdx.x; n < n_end; n += kGenericThreads) {
         int i_acc = 0, q_acc = 0;
+        if (ntab) {
+            const uint32_t w = noise::xsh_rr(nx);
+            nx = nA * nx + nC;
+            i_acc = noise::z(ntab, w & 0xffffu);
+            q_acc = noise::z(ntab, w >> 16);
+        }
         for (int c = 0; c < nchan; ++c) {
             const gpsiq_qchan_t &q = qs[c];
             if (q.prn == 0) continue;
@@ -409,254 +425,33 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rowsx(
 //     literal (2.5 issue cycles, where the SDWA form it replaces takes 4.3) makes the LDS address.  The table is 4 KB per
 //     channel, so a workgroup has WAVES = 16 waves (64 KB of LUT + 64 KB of windows, one workgroup per CU = the same four
 //     waves per SIMD).
+//   * NOISE (synth_tile_noise): receiver noise (include/gpsiq.h) added to each sample's sums before the store.  A lane owns
+//     lane stream `lane` of its block and its wave's rows are consecutive, so after a wave-uniform jump to the wave's first row
+//     a row costs one LCG step, xsh_rr and two gathers in the scaled table (LDS, beside the carrier LUT).  Both kernels include
+//     one body (gpsiq_tile_body.inc) with NOISE a constant: the noise-off kernels keep their names and their code.
 template <int FMT, int NCH, int ROWS, int H, bool FAST, int WAVES = kWaves, bool BOTH = false>
 __global__ __launch_bounds__(WAVES * 64, 4) void synth_tile(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
     size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
     int wave_rows, int big_wgs, int big_blocks, int tiles_small)
 {
-    constexpr int kLutEntries = BOTH ? 1024 : 512;
-    constexpr int kThreads = WAVES * 64;
-    __shared__ uint32_t lut[NCH][kLutEntries];
-    __shared__ uint32_t ext[NCH][kPrnExtWords];
-    __shared__ uint32_t win[WAVES][ROWS * H][NCH];      // one window per (row or half row, channel)
-    __shared__ gpsiq_qchan_t qs[NCH];
-    static_assert(H == 1 || H == 2, "one window per row or per half row");
-    static_assert(!BOTH || FAST, "the both-polarity table is a form of the plain-add core");
-    static_assert(kLutEntries % kThreads == 0 || kThreads % kLutEntries == 0, "LUT build: whole passes");
-    constexpr int kSpan = 64 / H;                        // samples per window
+    constexpr bool NOISE = false;
+    [[maybe_unused]] constexpr const noise::Entry *ntab = nullptr;
+    [[maybe_unused]] constexpr uint64_t nseed = 0, nblock0 = 0;
+#include "gpsiq_tile_body.inc"
+}
 
-    const int tid = threadIdx.x;
-    // workgroups [0, big_wgs) give every wave `wave_rows` consecutive rows (several chunks of
-    // ROWS rows, the last one possibly partial) of blocks [0, big_blocks); the rest of the grid
-    // covers the last blocks with one-chunk workgroups, so that what is still running when the
-    // grid drains is short (workgroups are dispatched in id order)
-    int blk, tile;
-    if ((int) blockIdx.x < big_wgs) {
-        blk = blockIdx.x / tiles_per_block; tile = blockIdx.x % tiles_per_block;
-    } else {
-        const int r = (int) blockIdx.x - big_wgs;
-        blk = big_blocks + r / tiles_small; tile = r % tiles_small;
-        wave_rows = ROWS;
-    }
-    const gpsiq_qchan_t *q_blk = desc + (size_t) (block0 + blk) * nchan;
-    const int nq = nchan < NCH ? nchan : NCH;
-    for (int i = tid; i < NCH * 12; i += kThreads)
-        reinterpret_cast<uint32_t *>(qs)[i] = i < nq * 12 ? reinterpret_cast<const uint32_t *>(q_blk)[i] : 0u;
-    __syncthreads();
-    for (int e = tid; e < kLutEntries; e += kThreads) {
-        // entry e of every channel (one pass: a thread per entry); unused slots have gain 0.0 -> entry 0.
-        // BOTH: the upper half is the table half a cycle on, i.e. the negated entries
-        const int k = BOTH ? (e + ((e >> 9) << 8)) & 511 : e;
-        const double sk = (double) dev_sin512(tab->quarter_wave, k);
-        const double ck = (double) dev_sin512(tab->quarter_wave, k + 128);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const double g = qs[c].gain;
-            const int ts = (int) (sk * g), tc = (int) (ck * g);   // gps.c:2781-2782
-            // int8 output keeps bits 4..11 of each 16-bit sum (gps.c:2845): with the entries
-            // pre-shifted by 4 (still modulo 2^16) those bits are bytes 1 and 3 of the packed sum
-            constexpr int kPre = FMT == GPSIQ_SC08 ? 4 : 0;
-            if (FAST && FMT == GPSIQ_SC08)
-                // the int8 output keeps bits 4..11 of I and Q only: 12-bit fields, I at bits 4..15 (its
-                // carries spill into bits 16..19, 16 channels x 12 bits), Q at bits 20..31; the output
-                // bytes are bytes 1 and 3 of the plain 32-bit sum, for any gain
-                lut[c][e] = (((uint32_t) tc & 0xfffu) << 4) | ((uint32_t) ts << 20);
-            else if (FAST)
-                // one integer; |tc|, |ts| <= 32767 here.  Slot 0 also carries the +0x8000 that keeps
-                // I + 32768 >= 0 in the sum (so a negative I never borrows from the Q half)
-                lut[c][e] = (uint32_t) (tc + ts * 65536) + (c == 0 ? 0x8000u : 0u);
-            else      lut[c][e] = (((uint32_t) tc << kPre) & 0xffffu) | ((uint32_t) ts << (16 + kPre));
-        }
-    }
-    for (int e = tid; e < NCH * kPrnExtWords; e += kRowsThreads) {
-        const int c = e / kPrnExtWords, w = e % kPrnExtWords;
-        ext[c][w] = qs[c].prn ? tab->prn_ext[qs[c].prn - 1][w] : 0u;
-    }
-    __syncthreads();
-    uint8_t *blk_dst = dst + (size_t) blk * block_stride;
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const uint32_t wave_samples = (uint32_t) wave_rows * 64u;
-    const uint32_t n_wave = ((uint32_t) tile * WAVES + (uint32_t) wave) * wave_samples;
-    if (n_wave >= (uint32_t) nsamp) return;             // whole wave past the block end
-
-    // ---- window builder: lane (c, g) prepares windows g, g+G, g+2G, ... of channel c ----
-    constexpr int kPad = NCH <= 4 ? 4 : NCH <= 8 ? 8 : 16;   // lanes per window group
-    constexpr int kGroups = 64 / kPad;
-    constexpr int kRun = ROWS * H / kGroups;
-    static_assert((ROWS * H) % kGroups == 0, "windows per chunk must split over the lane groups");
-    const int c_raw = lane % kPad, wg = lane / kPad;
-    const int wc = c_raw < NCH ? c_raw : 0;                  // surplus lanes shadow channel 0
-    const bool w_store = c_raw < NCH;
-    uint32_t w_k, w_nrev, w_nrot, w_dint;
-    int32_t w_e1;
-    uint64_t w_fr, w_dfr;
-    {
-        const gpsiq_qchan_t &q = qs[wc];
-        const uint32_t n_row = n_wave + (uint32_t) wg * (uint32_t) kSpan;
-        const unsigned __int128 T = (unsigned __int128) q.code_frac +
-                                    (unsigned __int128) q.code_step * (unsigned __int128) n_row;
-        const uint32_t A = (uint32_t) q.chip0 + (uint32_t) (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-        w_fr = (uint64_t) T & kCodeFracMask;
-        w_k = A % GPSIQ_CA_SEQ_LEN;                              // chip inside the period
-        const uint32_t ic = q.icode + A / GPSIQ_CA_SEQ_LEN;
-        // chips until the current nav bit ends, minus one (0..20459)
-        w_e1 = (int32_t) ((20u - ic % 20u) * GPSIQ_CA_SEQ_LEN - w_k) - 1;
-        // nav bits of this block, current bit in bit 31, the following ones below it
-        w_nrev = __builtin_bitreverse32(q.nav_bits >> ((ic / 20u) & 31u));
-        w_nrot = 0u - A;                                         // minus the rotation: only (-A) mod 32 matters
-        // chips per builder step: kSpan*kGroups samples (<= 1024 samples at <= 0.5 chip, or
-        // <= 512 samples at <= 1 chip: one period wrap at most)
-        const unsigned __int128 step = (unsigned __int128) q.code_step * (unsigned) (kSpan * kGroups);
-        w_dint = (uint32_t) (uint64_t) (step >> GPSIQ_CODE_FRAC_BITS);
-        w_dfr = (uint64_t) step & kCodeFracMask;
-    }
-
-    // ---- per-lane NCO state of every channel (steps in SGPRs via scalar loads) -----
-    const uint32_t n0 = n_wave + (uint32_t) lane;
-    uint64_t P[NCH], Q[NCH], dP[NCH], dQ[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const bool have = c < nchan;
-        const uint64_t p0 = have ? q_blk[c].carr_phase : 0u, ps = have ? (uint64_t) q_blk[c].carr_step : 0u;
-        const uint64_t f0 = have ? q_blk[c].code_frac : 0u, cs = have ? q_blk[c].code_step : 0u;
-        const uint64_t c0 = have ? (uint64_t) q_blk[c].chip0 : 0u;
-        // BOTH keeps the 59-bit phase left-aligned in the word (it then wraps by itself, index in the top nine bits)
-        constexpr int kAlign = BOTH ? 64 - GPSIQ_CARR_FRAC_BITS : 0;
-        P[c] = (p0 + ps * (uint64_t) n0) << kAlign;
-        Q[c] = (c0 << GPSIQ_CODE_FRAC_BITS) + f0 + cs * (uint64_t) n0;
-        dP[c] = (ps * 64u) << kAlign;
-        dQ[c] = cs * 64u;
-    }
-
-    const unsigned char *lut_b = reinterpret_cast<const unsigned char *>(&lut[0][0]);
-    const uint32_t *w_row = &win[wave][H == 2 ? lane >> 5 : 0][0];   // upper half wave: second window of the row
-    uint32_t *w_dst = &win[wave][wg][wc];
-
-    auto row_body = [&](int r, uint32_t n_chunk, bool check) {
-        uint32_t iq;                                             // (I & 0xffff) | Q << 16, what the int16 store keeps
-        if (FAST) {
-            uint32_t sum = 0u;                                    // int16: slot 0's entries carry a +0x8000 bias
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const uint32_t w = w_row[r * (H * NCH) + c];
-                const uint32_t t = w >> ((uint32_t) (Q[c] >> 56) & 31u);        // bit 0 = chip ^ nav bit of this lane
-                if (BOTH) {
-                    // {strays, sign, index, 2 fraction bits}: sign and index make the word address in the 4 KB table
-                    const uint32_t x = __builtin_amdgcn_alignbit(t, (uint32_t) (P[c] >> 32), 21u);
-                    sum += *reinterpret_cast<const uint32_t *>(lut_b + c * 4096 + (x & 0xffcu));
-                } else {
-                    const uint32_t x = (t << 26) + (uint32_t) (P[c] >> 32);      // + half a cycle when that bit is set
-                    const uint32_t a = (x >> 16) & 0x7fcu;
-                    sum += *reinterpret_cast<const uint32_t *>(lut_b + c * 2048 + a);
-                }
-                P[c] += dP[c];
-                Q[c] += dQ[c];
-            }
-            iq = FMT == GPSIQ_SC16 ? sum ^ 0x8000u : sum;         // take the bias off again: (I & 0xffff) | Q << 16
-        } else {
-            s16x2 acc0 = (s16x2) (0), acc1 = (s16x2) (0);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const uint32_t w = w_row[r * (H * NCH) + c];
-                const uint32_t b = (uint32_t) (Q[c] >> 56);
-                const uint32_t m = (uint32_t) __builtin_amdgcn_sbfe((int) w, b, 1u);
-                const uint32_t sgn = m | 0x00010001u;
-                const uint32_t a = (uint32_t) (P[c] >> 48) & 0x7fcu;
-                const uint32_t v = *reinterpret_cast<const uint32_t *>(lut_b + c * 2048 + a);
-                if (c & 1) acc1 = __builtin_bit_cast(s16x2, v) * __builtin_bit_cast(s16x2, sgn) + acc1;
-                else       acc0 = __builtin_bit_cast(s16x2, v) * __builtin_bit_cast(s16x2, sgn) + acc0;
-                P[c] += dP[c];
-                Q[c] += dQ[c];
-            }
-            iq = __builtin_bit_cast(uint32_t, acc0 + acc1);
-        }
-        const uint32_t n = n_chunk + (uint32_t) lane + (uint32_t) r * 64u;
-        if (!check || n < (uint32_t) nsamp) {
-            if (FMT == GPSIQ_SC16)
-                *reinterpret_cast<uint32_t *>(blk_dst + n * 4u) = iq;                     // gps.c:2842
-            else                                                                         // bytes 1 and 3, see the LUT build
-                *reinterpret_cast<uint16_t *>(blk_dst + n * 2u) = (uint16_t) __builtin_amdgcn_perm(iq, iq, 0x0c0c0301u);
-        }
-    };
-
-    for (int row0 = 0; row0 < wave_rows; row0 += ROWS) {
-        const uint32_t n_chunk = n_wave + (uint32_t) row0 * 64u;
-        // windows of this chunk (the builder state carries over from the previous chunk).
-        // A nav-bit edge comes by once in 20 ms (about 800 rows) per channel: a group of four windows
-        // during which no lane of the wave gets near one needs no attention to the edge counter and the
-        // nav word (with 16 channels about two groups in three).
-        constexpr int kGrp = 4;
-        static_assert(kRun % kGrp == 0, "window groups");
-        const uint32_t reach = (uint32_t) kGrp * (w_dint + 1u) + 32u;      // chips a lane can advance in a group + one window
-#pragma unroll 1
-        for (int i0 = 0; i0 < kRun; i0 += kGrp) {
-            if (__builtin_amdgcn_ballot_w64((uint32_t) w_e1 <= reach) == 0) {
-                const uint32_t nrot0 = w_nrot;
-                const uint32_t d0 = (uint32_t) ((int32_t) w_nrev >> 31);
-#pragma unroll
-                for (int i = i0; i < i0 + kGrp; ++i) {
-                    const uint32_t lo = ext[wc][w_k >> 5], hi = ext[wc][(w_k >> 5) + 1];
-                    const uint32_t S = __builtin_amdgcn_alignbit(hi, lo, w_k) ^ d0;   // 32 chips from chip k (shift uses k & 31)
-                    // rotate left by A mod 32 (alignbit rotates right by its low 5 bits); an unused slot
-                    // needs no masking: its LUT entries are all zero
-                    if (w_store) w_dst[i * (kGroups * NCH)] = __builtin_amdgcn_alignbit(S, S, w_nrot);
-                    w_fr += w_dfr;
-                    const uint32_t adv = w_dint + (uint32_t) (w_fr >> GPSIQ_CODE_FRAC_BITS);
-                    w_fr &= kCodeFracMask;
-                    w_nrot -= adv;
-                    const uint32_t k2 = w_k + adv;                        // adv < 1023: one period wrap at most
-                    w_k = k2 - GPSIQ_CA_SEQ_LEN < k2 ? k2 - GPSIQ_CA_SEQ_LEN : k2;
-                }
-                w_e1 -= (int32_t) (nrot0 - w_nrot);                       // chips advanced in this group
-            } else {
-#pragma unroll
-                for (int i = i0; i < i0 + kGrp; ++i) {
-                    const uint32_t lo = ext[wc][w_k >> 5], hi = ext[wc][(w_k >> 5) + 1];
-                    uint32_t S = __builtin_amdgcn_alignbit(hi, lo, w_k);
-                    S ^= (uint32_t) ((int32_t) w_nrev >> 31);
-                    // the window holds the start of the next nav bit when fewer than 32 chips of the
-                    // current one are left
-                    const bool edge = (uint32_t) w_e1 < 31u;
-                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(edge) != 0, 0)) {
-                        if (edge && ((w_nrev ^ (w_nrev << 1)) >> 31)) S ^= 0xfffffffeu << w_e1;
-                    }
-                    if (w_store) w_dst[i * (kGroups * NCH)] = __builtin_amdgcn_alignbit(S, S, w_nrot);
-                    w_fr += w_dfr;
-                    const uint32_t adv = w_dint + (uint32_t) (w_fr >> GPSIQ_CODE_FRAC_BITS);
-                    w_fr &= kCodeFracMask;
-                    w_nrot -= adv;
-                    const uint32_t k2 = w_k + adv;
-                    w_k = k2 - GPSIQ_CA_SEQ_LEN < k2 ? k2 - GPSIQ_CA_SEQ_LEN : k2;
-                    const int32_t e = w_e1 - (int32_t) adv;               // adv < 20460: one bit edge at most
-                    const int32_t m = e >> 31;
-                    w_e1 = e + (m & (int32_t) (20 * GPSIQ_CA_SEQ_LEN));
-                    w_nrev <<= (uint32_t) m & 1u;
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-        int rows = wave_rows - row0;                         // the wave's last chunk may be partial
-        rows = rows < ROWS ? rows : ROWS;
-        if (n_chunk + (uint32_t) rows * 64u <= (uint32_t) nsamp) {
-            const int rows_s = __builtin_amdgcn_readfirstlane(rows);       // the trip count is wave-uniform: keep it scalar
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int r = 0; r < rows_s; ++r) row_body(r, n_chunk, false);
-        } else {                                             // the block ends inside this chunk
-            const int in_block = (int) (((uint32_t) nsamp - n_chunk + 63u) >> 6);
-            rows = rows < in_block ? rows : in_block;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int r = 0; r < rows; ++r) row_body(r, n_chunk, true);
-        }
-        // the next chunk overwrites this wave's windows: all lanes must be done reading
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
+// the same with receiver noise: ntab is the scaled table (noise::kTabEntries entries), nblock0 the absolute index of desc's block 0
+template <int FMT, int NCH, int ROWS, int H, bool FAST>
+__global__ __launch_bounds__(kWaves * 64, 4) void synth_tile_noise(
+    const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
+    size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
+    int wave_rows, int big_wgs, int big_blocks, int tiles_small,
+    const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
+{
+    constexpr int WAVES = kWaves;
+    constexpr bool BOTH = false, NOISE = true;
+#include "gpsiq_tile_body.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -817,7 +612,8 @@ size_t variant_scratch_bytes(int variant, int nsamp, int nblocks)
 template <int FMT>
 __global__ __launch_bounds__(64) void apply_patches(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst, size_t block_stride,
-    int block0, int nblocks, const DeviceTables *__restrict__ tab, const gpsiq_patch_t *__restrict__ pt, int npatch)
+    int block0, int nblocks, const DeviceTables *__restrict__ tab, const gpsiq_patch_t *__restrict__ pt, int npatch,
+    const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
 {
     const int i = (int) (blockIdx.x * 4u + (threadIdx.x >> 4));      // four patches per wave
     const int c = (int) (threadIdx.x & 15u);                          // this lane's channel slot (GPSIQ_MAX_CHAN = 16)
@@ -850,6 +646,12 @@ __global__ __launch_bounds__(64) void apply_patches(
         i_acc += __shfl_xor(i_acc, off, 16);
         q_acc += __shfl_xor(q_acc, off, 16);
     }
+    if (lead && c == 0 && ntab) {                                     // the sample's noise, as the synthesis kernel added it
+        int32_t zi, zq;
+        noise::sample(ntab, nseed, nblock0 + p.block, p.sample, &zi, &zq);
+        i_acc += zi;
+        q_acc += zq;
+    }
     if (lead && c == 0)
         store_sample<FMT>(dst + (size_t) (p.block - (uint32_t) block0) * block_stride, p.sample,
                           ((uint32_t) i_acc & 0xffffu) | ((uint32_t) q_acc << 16));
@@ -857,15 +659,17 @@ __global__ __launch_bounds__(64) void apply_patches(
 
 hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size, void *dst, size_t block_stride,
                           int block0, int nblocks, const DeviceTables *tab, const gpsiq_patch_t *patches, int npatch,
-                          hipStream_t stream)
+                          hipStream_t stream, const noise::Launch &nz)
 {
     if (npatch <= 0 || nblocks <= 0 || nsamp <= 0) return hipSuccess;
     dim3 grid((unsigned) ((npatch + 3) / 4)), block(64);
     uint8_t *d = static_cast<uint8_t *>(dst);
     if (sample_size == GPSIQ_SC16)
-        hipLaunchKernelGGL(apply_patches<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch);
+        hipLaunchKernelGGL(apply_patches<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
+                           nz.tab, nz.seed, nz.block);
     else
-        hipLaunchKernelGGL(apply_patches<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch);
+        hipLaunchKernelGGL(apply_patches<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
+                           nz.tab, nz.seed, nz.block);
     return hipGetLastError();
 }
 
@@ -896,9 +700,12 @@ static const SegPolicy &seg_policy()
 
 hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size,
                           void *dst, size_t block_stride, int block0, int nblocks,
-                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch)
+                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch,
+                          const noise::Launch &nz)
 {
     if (nblocks <= 0 || nsamp <= 0) return hipSuccess;
+    // receiver noise exists in the default kernels (seg, segh, generic) and tile; the host refuses the others first
+    if (nz.tab && variant != kTile && variant != kSeg && variant != kSegHalf && variant != kGeneric) return hipErrorInvalidValue;
     uint8_t *d = static_cast<uint8_t *>(dst);
     // the mask kernel only has the plain-add LUT formats: int16 sums that may leave the int16 range go to seg's packed core
     if (variant == kSegMask && ((sample_size == GPSIQ_SC16 && max_amplitude > 32767) || !scratch)) variant = kSeg;
@@ -1003,8 +810,11 @@ hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int
         dim3 grid((unsigned) (big_wgs + tiles1 * tail_blocks)), block(kRowsThreads);
         // no channel sum of any resident block can leave the int16 range: plain-add kernel
         // (the int8 kernels keep 12-bit fields and are exact for any gain)
-        const bool fast = (sample_size == GPSIQ_SC08 || max_amplitude <= 32767) && seg_policy().allow_fast;
-#define GPSIQ_LAUNCH_T4(F, N, R, HH, FA) hipLaunchKernelGGL((synth_tile<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1)
+        // (with noise the bound is on |I + zI|: max_amplitude + max|z|)
+        const bool fast = (sample_size == GPSIQ_SC08 || max_amplitude + nz.max_z <= 32767) && seg_policy().allow_fast;
+#define GPSIQ_LAUNCH_T4(F, N, R, HH, FA) do { if (nz.tab) \
+            hipLaunchKernelGGL((synth_tile_noise<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1, nz.tab, nz.seed, nz.block); \
+        else hipLaunchKernelGGL((synth_tile<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1); } while (0)
 #define GPSIQ_LAUNCH_T(F, N) do { if (half) { if (fast) GPSIQ_LAUNCH_T4(F, N, 32, 2, true); else GPSIQ_LAUNCH_T4(F, N, 32, 2, false); } \
                                   else      { if (fast) GPSIQ_LAUNCH_T4(F, N, 64, 1, true); else GPSIQ_LAUNCH_T4(F, N, 64, 1, false); } } while (0)
         const int slots = max_active <= 4 ? 4 : max_active <= 8 ? 8 : max_active <= 12 ? 12 : 16;
@@ -1040,9 +850,11 @@ hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int
         const int tiles = (nsamp + tile_samples - 1) / tile_samples;
         dim3 grid((unsigned) (tiles * nblocks)), block(kGenericThreads);
         if (sample_size == GPSIQ_SC16)
-            hipLaunchKernelGGL(synth_generic<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples);
+            hipLaunchKernelGGL(synth_generic<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
+                               nz.tab, nz.seed, nz.block);
         else
-            hipLaunchKernelGGL(synth_generic<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples);
+            hipLaunchKernelGGL(synth_generic<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
+                               nz.tab, nz.seed, nz.block);
     }
     return hipGetLastError();
 }

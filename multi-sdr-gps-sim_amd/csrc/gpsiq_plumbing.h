@@ -173,6 +173,12 @@ void gpsiq_device_eval_stats(uint64_t out[6]);
 /* host time the context's last device-evaluated batch spent on descriptors (pack of pageable rows, repair, the host walker's share) */
 double gpsiq_device_eval_host_ms(const gpsiq_ctx_t *ctx);
 
+/* Receiver noise (include/gpsiq.h, gpsiq_set_noise).  gpsiq_noise_state reads the context's settings back (next_block for a
+ * checkpoint: the absolute index the next drop-in call's block 0 gets).  gpsiq_noise_host is the host twin of what the kernels add:
+ * iq[2n] = zI(n), iq[2n+1] = zQ(n) for samples n = 0..nsamp-1 of absolute block `block`, in accumulator units. */
+int gpsiq_noise_state(const gpsiq_ctx_t *ctx, gpsiq_noise_t *out);
+int gpsiq_noise_host(uint64_t seed, double sigma, uint64_t block, int nsamp, int32_t *iq);
+
 #ifdef __cplusplus
 }
 #endif

@@ -649,4 +649,10 @@ static int refresh_impl(const gpsiq_ephem_t *eph, const gpsiq_iono_t *iono, int 
     return GPSIQ_OK;
 }
 
+// C = (250*gain)^2 (the carrier table's amplitude), N0 = 2*sigma^2/fs (I and Q each of variance sigma^2 over fs Hz)
+double gpsiq_noise_sigma_for_cn0(double cn0_dbhz, double gain, double fs)
+{
+    return 250.0 * std::fabs(gain) * std::sqrt(fs / (2.0 * std::pow(10.0, cn0_dbhz / 10.0)));
+}
+
 }  // extern "C"

@@ -144,6 +144,15 @@ _device_eval_stats = _sig("gpsiq_device_eval_stats", None, _vp)
 _device_eval_host_ms = _sig("gpsiq_device_eval_host_ms", _d, _vp)
 _num_variants = _sig("gpsiq_num_variants", _i)
 _variant_name = _sig("gpsiq_variant_name", C.c_char_p, _i)
+_set_noise = _sig("gpsiq_set_noise", _i, _vp, _vp)
+_noise_state = _sig("gpsiq_noise_state", _i, _vp, _vp)
+_noise_host = _sig("gpsiq_noise_host", _i, C.c_uint64, _d, C.c_uint64, _i, _vp)
+_noise_sigma_for_cn0 = _sig("gpsiq_noise_sigma_for_cn0", _d, _d, _d, _d)
+
+
+class NoiseSettings(C.Structure):
+    """gpsiq_noise_t (include/gpsiq.h)."""
+    _fields_ = [("seed", C.c_uint64), ("sigma", C.c_double), ("next_block", C.c_uint64)]
 
 
 def _check(rc):
@@ -584,6 +593,18 @@ def rinex_select(eph, nsets, week, sec):
     return int(_rinex_select(_p(eph), int(nsets), int(week), float(sec)))
 
 
+def noise_sigma_for_cn0(cn0_dbhz, gain=1.0, fs=2.6e6):
+    """Receiver-noise sigma (accumulator units) that puts a channel of this gain at cn0_dbhz dB-Hz at fs Hz."""
+    return _noise_sigma_for_cn0(float(cn0_dbhz), float(gain), float(fs))
+
+
+def noise_host(seed, sigma, block, nsamp):
+    """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
+    out = np.zeros((int(nsamp), 2), dtype=np.int32)
+    _check(_noise_host(int(seed) & (2**64 - 1), float(sigma), int(block) & (2**64 - 1), int(nsamp), _p(out)))
+    return out
+
+
 def generate_batch_multi(contexts, desc, nsamp, fs, sample_size, host_ptr=None, device_ptrs=None, carr_out=None):
     """gpsiq_generate_batch_multi: one call, one contiguous block range per context.  host_ptr: one host buffer
     for the whole timeline; device_ptrs: one device pointer per context (its own range); neither: a numpy array."""
@@ -626,6 +647,21 @@ class Context:
     def set_nco_mode(self, mode):
         """NCO_FIXED (default) or NCO_REFERENCE for generate_block / generate_batch."""
         _check(_set_nco_mode(self._h, int(mode)))
+
+    def set_noise(self, seed, sigma, next_block=0):
+        """Receiver noise of standard deviation sigma (accumulator units; 0 = off) from `seed`; next_block is the absolute
+        block index the next drop-in call starts from (include/gpsiq.h, "receiver noise")."""
+        st = NoiseSettings(int(seed) & (2**64 - 1), float(sigma), int(next_block) & (2**64 - 1))
+        _check(_set_noise(self._h, C.byref(st)))
+
+    def noise_off(self):
+        _check(_set_noise(self._h, None))
+
+    def noise_state(self):
+        """(seed, sigma, next_block) of the context's receiver noise."""
+        st = NoiseSettings()
+        _check(_noise_state(self._h, C.byref(st)))
+        return st.seed, st.sigma, st.next_block
 
     def set_patches(self, patches):
         patches = np.ascontiguousarray(patches, dtype=PATCH_DTYPE)

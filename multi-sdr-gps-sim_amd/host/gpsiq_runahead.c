@@ -27,6 +27,8 @@
  * out.bin: the iqfile stream.  An optional eleventh argument names a SEM almanac file (the reference's almanac.sem,
  * almanac.c:73-184): its entries fill the almanac pages of subframes 4 and 5; without it those pages are empty, as with
  * the reference's --disable-almanac.
+ * Receiver noise (optional, after the positional arguments): --cn0 <dB-Hz> puts a channel of gain 1.0 at that C/N0
+ * (gpsiq_noise_sigma_for_cn0, gpsiq_set_noise), --seed <n> seeds it (default 0).  Without --cn0 the file is noiseless.
  */
 #include <math.h>
 #include <stdint.h>
@@ -127,8 +129,15 @@ static int refresh_ephemeris(struct host_state *h, double t)
 
 int main(int argc, char **argv)
 {
+    double cn0 = NAN;
+    uint64_t noise_seed = 0;
+    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0)) {   /* trailing flags */
+        if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
+        else noise_seed = strtoull(argv[argc - 1], NULL, 0);
+        argc -= 2;
+    }
     if (argc != 11 && argc != 12) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem]\n", argv[0]);
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n]\n", argv[0]);
         return 2;
     }
     const int version = atoi(argv[2]), nchan = atoi(argv[7]), ss = atoi(argv[9]);
@@ -193,6 +202,10 @@ int main(int argc, char **argv)
     {   /* GPSIQ_NCO=reference: the reference's double accumulators, as in the binding of INTEGRATION.md section 2 */
         const char *m = getenv("GPSIQ_NCO");
         if (m && strcmp(m, "reference") == 0 && gpsiq_set_nco_mode(gq, GPSIQ_NCO_REFERENCE) != GPSIQ_OK) return die("nco mode");
+    }
+    if (!isnan(cn0)) {
+        const gpsiq_noise_t nz = {noise_seed, gpsiq_noise_sigma_for_cn0(cn0, 1.0, fs), 0};
+        if (gpsiq_set_noise(gq, &nz) != GPSIQ_OK) return die("noise");
     }
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) ss;
     void *buf = gpsiq_host_alloc(blk_bytes * BLOCKS_PER_CALL);

@@ -31,7 +31,7 @@ def q(db, sql):
 
 lines = []
 for db in sorted(glob.glob(os.path.join(src, "kt*", "*.db"))):
-    lines.append(f"== rocprofv3 --kernel-trace --stats ({db}) ==")
+    lines.append(f"== rocprofv3 --kernel-trace --stats ({os.path.relpath(db, src)}) ==")   # named by its pass, not where it was written
     lines.append(f"{'kernel':<70} {'calls':>6} {'total_ns':>14} {'avg_ns':>14} {'pct':>7}")
     for name, calls, tot, avg, pct in q(db, "select name,total_calls,total_duration,average,percentage from top_kernels"):
         lines.append(f"{name[:70]:<70} {calls:>6} {tot:>14.0f} {avg:>14.1f} {pct:>7.2f}")
@@ -56,7 +56,7 @@ print("\n".join(lines))
 
 lines = []
 for db in sorted(glob.glob(os.path.join(src, "pmc*", "*.db"))):
-    lines.append(f"== rocprofv3 --pmc ({db}) ==")
+    lines.append(f"== rocprofv3 --pmc ({os.path.relpath(db, src)}) ==")
     rows = q(db, "select kernel_name, counter_name, count(*), avg(value), min(value), max(value), avg(duration) "
                  "from counters_collection group by kernel_name, counter_name order by kernel_name, counter_name")
     lines.append(f"{'kernel':<50} {'counter':<24} {'n':>3} {'avg':>18} {'min':>18} {'max':>18} {'avg_dur_ns':>12}")
