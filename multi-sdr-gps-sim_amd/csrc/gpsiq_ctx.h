@@ -66,7 +66,7 @@ struct gpsiq_ctx {
     // scratch of the kernel variants that need some (segm: the sign masks of one launch)
     void          *d_scratch = nullptr;
     size_t         scratch_cap = 0;
-    // staging for the synchronous entry points
+    // staging of the batch calls' output (PieceOut below)
     void          *d_out = nullptr;
     size_t         out_cap = 0;
     hipEvent_t     chunk_done[2] = {nullptr, nullptr};
@@ -140,8 +140,46 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
 double gpsiq_wall_ms();
 int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b);
 int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s);
-int gpsiq_ensure_out(gpsiq_ctx *c, size_t bytes);
-hipStream_t gpsiq_piece_stream(gpsiq_ctx *c, int k);
+// The stream of piece k of a batch worked through in pieces.  On ONE stream a piece's kernel starts when the last workgroup of
+// the piece before it has retired: every piece pays its own ramp-down (six pieces of a 2 000-block call: 1.75 ms of kernels
+// against 1.50 ms in one launch, profiles/r05_chain_ab.txt).  Pieces write disjoint blocks and read their own descriptor set
+// (four sets taken in turn; piece k+2 follows piece k on the same stream), so consecutive pieces alternate
+// between two streams and the next piece's first workgroups fill the compute units the last ones of this piece leave.
+// (One stream against two: profiles/r05_chain_ab.txt.)
+inline hipStream_t gpsiq_piece_stream(gpsiq_ctx *c, int k) { return (k & 1) ? c->stream2 : c->stream; }
+
+// The output of one batch call: its blocks are rendered straight into the caller's device memory where the rows are ours
+// (direct: 16-byte rows, 4-byte aligned), else into c->d_out with 16-byte rows and copied across on the context's two copy
+// streams, in turn.  finish() is the call's one drain: on every path, also after an error, nothing may still write dst or
+// read the staging when the call returns.
+struct PieceOut {
+    gpsiq_ctx *c = nullptr;
+    uint8_t   *dst = nullptr;
+    size_t     blk_bytes = 0, stride = 0;      // bytes of a block, and between blocks as rendered
+    int        nblocks = 0, copies = 0;
+    bool       dst_is_device = false, direct = false;
+
+    int begin(gpsiq_ctx *ctx, int nblocks, int nsamp, int sample_size, void *dst, int dst_is_device);   // sizes the staging
+    uint8_t *target(int b0) const { return (direct ? dst : static_cast<uint8_t *>(c->d_out)) + (size_t) b0 * stride; }   // where block b0 is rendered
+    int rendered(int b0, int nb, hipStream_t s);                 // blocks [b0, b0 + nb) cross once their kernel on s is done
+    int whole(hipStream_t s);                                    // every block, behind the kernel on s (one kernel, one copy)
+    int again(hipStream_t s, const std::vector<gpsiq_patch_t> &patches);   // the blocks patched on s (sorted by block) once more
+    int finish(const char *label, int rc = GPSIQ_OK);            // rc != GPSIQ_OK: the call has failed, its error text stands
+};
+
+// the fixed-point carrier: whether slot i continues what the context handed out (the caller gave back what it was given) ...
+inline bool gpsiq_continues(const gpsiq_ctx *c, int i, const gpsiq_chan_t &ch)
+{
+    return ch.prn > 0 && c->carry_prn[i] == ch.prn && c->handed[i] == ch.carr_phase;
+}
+// ... and what a batch call leaves in slot i: satellite prn (0: none) with the accumulator at `phase`
+inline void gpsiq_hand_back(gpsiq_ctx *c, int i, int prn, uint64_t phase, double *carr_phase_out)
+{
+    c->carry_prn[i] = prn;
+    c->carry[i] = prn ? phase : 0;
+    c->handed[i] = prn ? gpsiq::carr_phase_to_double(phase) : 0.0;
+    if (carr_phase_out) carr_phase_out[i] = c->handed[i];
+}
 int gpsiq_chain_reserve(gpsiq_ctx *c, size_t n);
 double gpsiq_rate_kernel();
 void gpsiq_note_kernel_rate(double channel_samples_per_s);      // a measured rate of the synthesis kernel (running mean)

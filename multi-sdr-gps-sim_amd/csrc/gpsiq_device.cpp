@@ -14,6 +14,7 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_noise_knots.h"
+#include "gpsiq_pieces.h"
 
 using namespace gpsiq;
 
@@ -57,17 +58,6 @@ static int mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s)
     HIP_TRY(hipEventRecord(slot->ev, s));
     slot->s = s; slot->active = true;
     b.in_use = true;
-    return GPSIQ_OK;
-}
-
-static int ensure_out(gpsiq_ctx *c, size_t bytes)
-{
-    if (bytes > c->out_cap) {
-        if (c->d_out) HIP_TRY(hipFree(c->d_out));
-        c->d_out = nullptr; c->out_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_out, bytes));
-        c->out_cap = bytes;
-    }
     return GPSIQ_OK;
 }
 
@@ -482,100 +472,114 @@ const char *gpsiq_variant_name(int v)
     }
 }
 
-// ---- synchronous drop-in entry points ---------------------------------------
+// ---- the output of a batch call (PieceOut, gpsiq_ctx.h) ----------------------------------------------------------------------
 
-// Blocks per piece of a host-destination batch: the kernel of piece k+1 runs while piece k crosses
-// PCIe (two copy streams, so consecutive copies queue back to back).  GPSIQ_PIECE_BLOCKS overrides;
-// 0 = one kernel, then one copy (the round-1 behaviour, kept for A/B measurements).
-static int d2h_chunk_blocks(size_t stride)
+int PieceOut::begin(gpsiq_ctx *ctx, int nblocks_, int nsamp, int sample_size, void *dst_, int dst_is_device_)
 {
-    if (const char *e = std::getenv("GPSIQ_PIECE_BLOCKS")) return std::atoi(e) > 0 ? std::atoi(e) : 0;   // read per call: A/B in one process
-    const size_t target = (size_t) 32 << 20;                 // ~32 MiB per piece: >= 0.5 ms on the link, a few hundred workgroups
-    const size_t n = (target + stride - 1) / stride;
-    return (int) (n < 8 ? 8 : n);
+    c = ctx; nblocks = nblocks_; copies = 0; dst = static_cast<uint8_t *>(dst_); dst_is_device = dst_is_device_ != 0;
+    blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size;
+    stride = (blk_bytes + 15) & ~(size_t) 15;
+    direct = dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = stride * (size_t) nblocks;
+    if (direct || bytes <= c->out_cap) return GPSIQ_OK;       // (sized before anything is queued)
+    if (c->d_out) HIP_TRY(hipFree(c->d_out));
+    c->d_out = nullptr; c->out_cap = 0;
+    HIP_TRY(hipMalloc(&c->d_out, bytes));
+    c->out_cap = bytes;
+    return GPSIQ_OK;
 }
 
+// blocks [b0, b0 + nb) from the staging to dst on stream s: one linear copy where the rows are contiguous
+static hipError_t copy_rows(const PieceOut &o, int b0, int nb, hipStream_t s)
+{
+    const hipMemcpyKind kind = o.dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    uint8_t *to = o.dst + (size_t) b0 * o.blk_bytes;
+    if (o.stride == o.blk_bytes) return hipMemcpyAsync(to, o.target(b0), o.blk_bytes * (size_t) nb, kind, s);
+    return hipMemcpy2DAsync(to, o.blk_bytes, o.target(b0), o.stride, o.blk_bytes, (size_t) nb, kind, s);
+}
+
+// the copy of piece k goes on copy_stream[k & 1] (consecutive copies queue back to back) once the piece's kernel has finished
+int PieceOut::rendered(int b0, int nb, hipStream_t s)
+{
+    if (direct) return GPSIQ_OK;
+    const int k = copies++ & 1;
+    hipError_t e = hipEventRecord(c->chunk_done[k], s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream[k], c->chunk_done[k], 0);
+    if (e == hipSuccess) e = copy_rows(*this, b0, nb, c->copy_stream[k]);
+    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "piece copy: %s", hipGetErrorString(e));
+}
+
+int PieceOut::whole(hipStream_t s)
+{
+    if (direct) return GPSIQ_OK;
+    const hipError_t e = copy_rows(*this, 0, nblocks, s);
+    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "copy: %s", hipGetErrorString(e));
+}
+
+// behind the pieces' own copies, which may still be on their way (the copy streams are joined to s): every block that holds a
+// patched sample, or the whole timeline when that is more than a quarter of it
+int PieceOut::again(hipStream_t s, const std::vector<gpsiq_patch_t> &patches)
+{
+    if (direct || patches.empty()) return GPSIQ_OK;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipEventRecord(c->chunk_done[k], c->copy_stream[k]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->chunk_done[k], 0);
+    }
+    size_t touched = 0;
+    for (size_t k = 0; k < patches.size(); ++k) touched += k == 0 || patches[k].block != patches[k - 1].block;
+    const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (e == hipSuccess && touched * 4 > (size_t) nblocks) e = copy_rows(*this, 0, nblocks, s);
+    else
+        for (size_t k = 0; k < patches.size() && e == hipSuccess; ++k)
+            if (k == 0 || patches[k].block != patches[k - 1].block)
+                e = hipMemcpyAsync(dst + (size_t) patches[k].block * blk_bytes, target((int) patches[k].block), blk_bytes, kind, s);
+    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "patched blocks: %s", hipGetErrorString(e));
+}
+
+int PieceOut::finish(const char *label, int rc)
+{
+    if (!c) return rc;
+    (void) hipSetDevice(c->device);
+    hipError_t e = hipSuccess;
+    for (hipStream_t s : {c->copy_stream[0], c->copy_stream[1], c->stream, c->stream2})
+        { const hipError_t d = hipStreamSynchronize(s); if (e == hipSuccess) e = d; }
+    // every launch waited for its set's upload on the device and has finished; a set that was staged but never launched on (an
+    // error in between) may still be uploading: the upload stream is drained too before the flags are dropped
+    const hipError_t u = hipStreamSynchronize(c->up_stream);
+    if (e == hipSuccess && u == hipSuccess)
+        for (auto &b : c->buf) b.upload_pending = false;
+    if (rc != GPSIQ_OK) return rc;
+    if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "%s: %s", label, hipGetErrorString(e));
+    if (u != hipSuccess) return fail(GPSIQ_E_DEVICE, "%s: descriptor upload", label);
+    return GPSIQ_OK;
+}
+
+// ---- synchronous drop-in entry points ---------------------------------------
+
+// A host-destination batch goes in pieces of d2h_chunk_blocks: kernel on c->stream, the copy of piece k behind it
+// (PieceOut::rendered).  A device destination, or one piece: one kernel, then one copy.
 // (nbase: absolute block index of q[0], for the receiver noise)
 static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nblocks, int nchan,
                                  int nsamp, int sample_size, void *dst, int dst_is_device, uint64_t nbase)
 {
-    const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size;
-    const size_t stride = (blk_bytes + 15) & ~(size_t) 15;
     int rc = gpsiq_set_descriptors(c, q, nblocks, nchan);
     if (rc) return rc;
     if (!nblocks || !nsamp) return GPSIQ_OK;
-    if (dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3)) {
-        rc = launch_abs(c, 0, nblocks, nsamp, sample_size, dst, stride, c->stream, kAuto, nbase);
-        if (rc) return rc;
-        return gpsiq_synchronize(c, c->stream);
-    }
-    rc = ensure_out(c, stride * (size_t) nblocks);
-    if (rc) return rc;
-    const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const int chunk = d2h_chunk_blocks(stride);
+    PieceOut out;
+    rc = out.begin(c, nblocks, nsamp, sample_size, dst, dst_is_device);
+    const int chunk = d2h_chunk_blocks(out.stride, piece_blocks_env());
     if (dst_is_device || chunk <= 0 || nblocks <= chunk) {
-        rc = launch_abs(c, 0, nblocks, nsamp, sample_size, c->d_out, stride, c->stream, kAuto, nbase);
-        if (rc) return rc;
-        if (stride == blk_bytes)
-            HIP_TRY(hipMemcpyAsync(dst, c->d_out, blk_bytes * (size_t) nblocks, kind, c->stream));
-        else
-            HIP_TRY(hipMemcpy2DAsync(dst, blk_bytes, c->d_out, stride, blk_bytes, (size_t) nblocks, kind, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return GPSIQ_OK;
-    }
-    // pieces: kernel on c->stream, copy of piece k on copy_stream[k & 1] once its kernel has finished.
-    // On an error in the middle the earlier pieces may still be copying into the caller's buffer: whatever happens, the
-    // three streams are drained before this returns, so the caller may free or reuse dst.
-    int k = 0;
-    hipError_t e = hipSuccess;
-    const char *what = "";
-    for (int b0 = 0; b0 < nblocks && rc == GPSIQ_OK && e == hipSuccess; b0 += chunk, ++k) {
-        const int nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-        uint8_t *piece = static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
-        rc = launch_abs(c, b0, nb, nsamp, sample_size, piece, stride, c->stream, kAuto, nbase);
-        if (rc) break;
-        hipStream_t cs = c->copy_stream[k & 1];
-        what = "piece hand-over";
-        e = hipEventRecord(c->chunk_done[k & 1], c->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(cs, c->chunk_done[k & 1], 0);
-        if (e != hipSuccess) break;
-        what = "piece copy";
-        if (stride == blk_bytes)                                  // rows are contiguous: one linear DMA
-            e = hipMemcpyAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, piece, blk_bytes * (size_t) nb, kind, cs);
-        else
-            e = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, blk_bytes, piece, stride, blk_bytes,
-                                 (size_t) nb, kind, cs);
-    }
-    const hipError_t s0 = hipStreamSynchronize(c->copy_stream[0]);
-    const hipError_t s1 = hipStreamSynchronize(c->copy_stream[1]);
-    const hipError_t s2 = hipStreamSynchronize(c->stream);
-    if (rc) return rc;                                            // gpsiq_launch has set the text
-    if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
-    if (s0 != hipSuccess || s1 != hipSuccess || s2 != hipSuccess)
-        return fail(GPSIQ_E_DEVICE, "batch pieces: %s", hipGetErrorString(s0 != hipSuccess ? s0 : s1 != hipSuccess ? s1 : s2));
-    return GPSIQ_OK;
-}
-
-// The stream of piece k of a batch worked through in pieces.  On ONE stream a piece's kernel starts when the last workgroup of
-// the piece before it has retired: every piece pays its own ramp-down (six pieces of a 2 000-block call: 1.75 ms of kernels
-// against 1.50 ms in one launch, profiles/r05_chain_ab.txt).  Pieces write disjoint blocks and read their own descriptor set
-// (four sets taken in turn; piece k+2 follows piece k on the same stream), so consecutive pieces alternate
-// between two streams and the next piece's first workgroups fill the compute units the last ones of this piece leave.
-// (One stream against two: profiles/r05_chain_ab.txt.)
-static hipStream_t piece_stream(gpsiq_ctx *c, int k)
-{
-    return (k & 1) ? c->stream2 : c->stream;
-}
-
-// Blocks per piece of a long device-destination batch in the fixed-point model: ~1 ms of kernel, a few hundred microseconds of
-// host work per piece.  GPSIQ_PIECE_BLOCKS overrides (read per call); <= 0: one piece.
-static int batch_piece_blocks(int nblocks, int nsamp)
-{
-    long n = nsamp > 0 ? ((long) 1024 * 260000) / nsamp : 1024;
-    if (n > 1024) n = 1024;
-    if (n < 32) n = 32;
-    if (const char *e = std::getenv("GPSIQ_PIECE_BLOCKS")) n = std::atoi(e);
-    return n > 0 && 2 * n <= nblocks ? (int) n : nblocks;            // fewer than two pieces' worth: one piece
+        if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nblocks, nsamp, sample_size, out.target(0), out.stride, c->stream, kAuto, nbase);
+        if (rc == GPSIQ_OK) rc = out.whole(c->stream);
+    } else
+        for (int b0 = 0; b0 < nblocks && rc == GPSIQ_OK; b0 += chunk) {
+            const int nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
+            rc = launch_abs(c, b0, nb, nsamp, sample_size, out.target(b0), out.stride, c->stream, kAuto, nbase);
+            if (rc == GPSIQ_OK) rc = out.rendered(b0, nb, c->stream);
+        }
+    return out.finish("batch pieces", rc);
 }
 
 static int check_gen_args(const gpsiq_ctx *c, const void *ch, const void *dst, int nblocks, int nchan, int nsamp, double fs, int sample_size)
@@ -588,132 +592,26 @@ static int check_gen_args(const gpsiq_ctx *c, const void *ch, const void *dst, i
 }
 
 // ---- GPSIQ_NCO_REFERENCE: walk and render in pieces ------------------------------------------
-// The carrier chain is serial in time on the host, the render is not: the timeline is cut into pieces, and while the device
-// renders (and copies out) piece k the host threads (RefWalk, gpsiq_exact.cpp: a chain task and an evaluation task per channel
-// and piece, taken piece-major from the shared pool) are in the pieces behind it.  RefRender is the device side of one context: begin() sizes the staging once, piece() queues
-// descriptors + patches + kernel (+ the copy to the destination) without waiting, finish() drains.  generate_reference
-// drives one from the calling thread; gpsiq_generate_batch_multi gives every device one, fed through a queue.
-static int ref_chunk_blocks(int nblocks, int nsamp)
+// The carrier chain is serial in time on the host, the render is not: the timeline is cut into pieces (ref_chunk_blocks,
+// piece_ends), and while the device renders (and copies out) piece k the host threads (RefWalk, gpsiq_exact.cpp: a chain task and
+// an evaluation task per channel and piece, taken piece-major from the shared pool) are in the pieces behind it.
+// generate_reference renders from the calling thread; gpsiq_generate_batch_multi gives every device a thread, fed through a queue.
+// ref_piece queues piece k of a range without waiting: blocks [b0, b0 + nb) of the range, whose descriptors q and patches (block
+// indices relative to b0) are the piece's own.
+static int ref_piece(gpsiq_ctx *c, PieceOut &out, int k, const gpsiq_qchan_t *q, int b0, int nb, int nchan, int nsamp, int ss,
+                     uint64_t nbase, const std::vector<gpsiq_patch_t> &patches)
 {
-    // A piece costs the renderer ~0.1-0.2 ms (validate + compact + upload + launch) whatever its size and nothing on the
-    // walkers' side, and should be enough samples for a launch that fills the chip: 256 blocks at 2.6 Msps (1.6 ms of
-    // walking, 0.2 ms of kernel), fewer at higher rates where a block is more device work (25 Msps: 26 blocks = 66 M samples).
-    long n = nsamp > 0 ? ((long) 256 * 260000) / nsamp : 256;
-    if (n > 256) n = 256;
-    if (n < 16) n = 16;
-    if (const char *e = std::getenv("GPSIQ_PIECE_BLOCKS")) n = std::atoi(e);       // read per call: A/B in one process; <= 0: one piece
-    return n > 0 && n < nblocks ? (int) n : nblocks;
+    int rc = set_descriptors_impl(c, q, nb, nchan, patches.data(), (int) patches.size(), true);
+    if (rc || !nb || !nsamp) return rc;
+    hipStream_t s = gpsiq_piece_stream(c, k);
+    rc = launch_abs(c, 0, nb, nsamp, ss, out.target(b0), out.stride, s, kAuto, nbase + (uint64_t) b0);
+    return rc ? rc : out.rendered(b0, nb, s);
 }
 
-struct RefRender {
-    gpsiq_ctx *c = nullptr;
-    int nchan = 0, nsamp = 0, ss = 0;
-    uint8_t *dst = nullptr;          // destination of the range's first block
-    bool dst_is_device = false, direct = false;
-    size_t blk_bytes = 0, stride = 0;
-    int k = 0, npiece = 0;
-    uint64_t nbase = 0;              // absolute block index of the range's first block (receiver noise)
-
-    int begin(gpsiq_ctx *ctx, int range_blocks, int nchan_, int nsamp_, int ss_, void *dst_, int dst_is_device_, uint64_t nbase_)
-    {
-        c = ctx; nbase = nbase_; nchan = nchan_; nsamp = nsamp_; ss = ss_; dst = static_cast<uint8_t *>(dst_); dst_is_device = dst_is_device_ != 0; k = 0; npiece = 0;
-        blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) ss;
-        stride = (blk_bytes + 15) & ~(size_t) 15;
-        direct = dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3);
-        HIP_TRY(hipSetDevice(c->device));
-        if (!direct && range_blocks && nsamp) return ensure_out(c, stride * (size_t) range_blocks);      // before anything is queued
-        return GPSIQ_OK;
-    }
-
-    // blocks [b0, b0 + nb) of the range: q and patches (block indices relative to b0) belong to this piece
-    int piece(const gpsiq_qchan_t *q, int b0, int nb, const std::vector<gpsiq_patch_t> &patches)
-    {
-        int rc = set_descriptors_impl(c, q, nb, nchan, patches.data(), (int) patches.size(), true);   // queued, not waited for
-        if (rc) return rc;
-        if (!nb || !nsamp) return GPSIQ_OK;
-        uint8_t *dev = direct ? dst + (size_t) b0 * blk_bytes : static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
-        hipStream_t s = piece_stream(c, npiece++);
-        rc = launch_abs(c, 0, nb, nsamp, ss, dev, stride, s, kAuto, nbase + (uint64_t) b0);
-        if (rc || direct) return rc;
-        hipStream_t cs = c->copy_stream[k & 1];
-        HIP_TRY(hipEventRecord(c->chunk_done[k & 1], s));
-        HIP_TRY(hipStreamWaitEvent(cs, c->chunk_done[k & 1], 0));
-        const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (stride == blk_bytes)
-            HIP_TRY(hipMemcpyAsync(dst + (size_t) b0 * blk_bytes, dev, blk_bytes * (size_t) nb, kind, cs));
-        else
-            HIP_TRY(hipMemcpy2DAsync(dst + (size_t) b0 * blk_bytes, blk_bytes, dev, stride, blk_bytes, (size_t) nb, kind, cs));
-        ++k;
-        return GPSIQ_OK;
-    }
-
-    // on every path, also after an error: nothing may still be writing the caller's buffer when the call returns
-    int finish()
-    {
-        if (!c) return GPSIQ_OK;
-        (void) hipSetDevice(c->device);
-        const hipError_t s0 = hipStreamSynchronize(c->copy_stream[0]);
-        const hipError_t s1 = hipStreamSynchronize(c->copy_stream[1]);
-        hipError_t s2 = hipStreamSynchronize(c->stream);
-        const hipError_t s3 = hipStreamSynchronize(c->stream2);
-        if (s2 == hipSuccess) s2 = s3;
-        if (s0 != hipSuccess || s1 != hipSuccess || s2 != hipSuccess)
-            return fail(GPSIQ_E_DEVICE, "reference NCO pieces: %s", hipGetErrorString(s0 != hipSuccess ? s0 : s1 != hipSuccess ? s1 : s2));
-        // every launch waited for its set's upload on the device and has finished; a set that was staged but never launched
-        // (an error in between) may still be uploading: the upload stream is drained too before the flags are dropped
-        if (hipStreamSynchronize(c->up_stream) != hipSuccess) return fail(GPSIQ_E_DEVICE, "reference NCO pieces: descriptor upload");
-        for (auto &b : c->buf) b.upload_pending = false;
-        return GPSIQ_OK;
-    }
-};
-
-// piece boundaries of a range of `n` blocks starting at block `first` of the walk, `chunk` blocks each
-// Piece sizes.  Nothing renders before the first piece is through all channels: half a chunk.  After that it depends on which
-// side is the slower one.  HOST-bound (the rule at 2.6 - 10 Msps): a chunk, then two chunks each, and a chunk and half a chunk
-// again at the end -- the last piece's kernel is all that is left after the host has finished.  KERNEL-bound (25 Msps: a block
-// is 6.7 us of device work against ~3 us of host work per thread): every launch costs ~30 us beyond its share of one big
-// launch (a 26-block piece is a single round of workgroups: 215 us measured against 183 us), so as few pieces as the host can
-// keep ahead of -- each 2.2 x the one before (the host has piece k+1 ready before the kernel of piece k ends), no small tail.
-static void piece_ends(int first, int n, int chunk, std::vector<int> *ends, bool kernel_bound = false)
-{
-    const int half = chunk > 1 ? chunk / 2 : 1;
-    if (n <= 4 * chunk) {
-        for (int b = chunk; b < n; b += chunk) ends->push_back(first + b);
-        ends->push_back(first + n);
-        return;
-    }
-    if (kernel_bound) {
-        const int growth = 220;                           // per cent
-        int b = 0, size = half;
-        while (n - b > size + half) {                // what is left after this piece is worth a piece of its own
-            b += size;
-            ends->push_back(first + b);
-            size = (int) (((long) size * growth + 50) / 100);
-            if (size > 16 * chunk) size = 16 * chunk;
-        }
-        ends->push_back(first + n);
-        return;
-    }
-    const int tail0 = n - chunk - half;               // the last two pieces: a chunk, half a chunk
-    int b = half;
-    ends->push_back(first + b);
-    b += chunk;
-    ends->push_back(first + b);
-    while (tail0 - b >= 3 * chunk) { b += 2 * chunk; ends->push_back(first + b); }     // what is left (chunk .. 3 chunks) is one piece
-    if (tail0 > b) ends->push_back(first + tail0);
-    ends->push_back(first + n - half);
-    ends->push_back(first + n);
-}
-
-// Whether a GPSIQ_NCO_REFERENCE batch is clearly kernel-bound, from the rates measured on MI355X + EPYC 9575F (DESIGN.md section
-// 2): the kernel at 6.0e12 channel-samples/s, the host at 2.5 us + 0.8 us per 10^6 samples per block and channel on each of its
-// threads (2.7 us at 2.6 Msps, 4.5 us at 25 Msps, in the call).  At 25 Msps on sixteen threads the two sides are within 1.5 x of
-// each other and the symmetric ramp measured better (1.77 against 1.91 ms per 200 blocks): only a clear case takes the few
-// growing pieces.
 // The kernel's rate is MEASURED: every batch call that renders through the device evaluation times its last piece's synthesis
 // with events and keeps a running mean in the context (gpsiq_evaldev.cpp); until the first such call, and for the host rate, the
 // figures of MI355X + EPYC 9575F stand in.  GPSIQ_RATE_KERNEL (channel-samples per second, read per call) overrides both.
-static std::atomic<double> g_rate_kernel_measured{0.0};        // a running mean over every context's calls (the placement rules below have no context at hand)
+static std::atomic<double> g_rate_kernel_measured{0.0};        // a running mean over every context's calls (the placement rules have no context at hand)
 static double rate_kernel()
 {
     if (const char *e = std::getenv("GPSIQ_RATE_KERNEL")) { const double v = std::atof(e); if (v > 1e9) return v; }
@@ -721,14 +619,6 @@ static double rate_kernel()
     return m > 0.0 ? m : 6.0e12;
 }
 static double rate_chain_us() { return 2.2; }      // microseconds per block and channel of the serial walk on one host thread
-
-static bool ref_kernel_bound(int nsamp, int nchan)
-{
-    const int threads = host_threads() < nchan ? host_threads() : nchan;
-    const double t_kernel = (double) nsamp * (double) nchan / rate_kernel();
-    const double t_host = (double) nchan * (2.5e-6 + 0.8e-12 * (double) nsamp) / (double) (threads > 0 ? threads : 1);
-    return t_kernel > 2.0 * t_host;
-}
 
 // ---- the carrier chain on the device -------------------------------------------------------------------------------
 static int chain_reserve(gpsiq_ctx *c, size_t n)
@@ -892,15 +782,15 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
     if (q.size() < (size_t) nblocks * (size_t) nchan) q.resize((size_t) nblocks * (size_t) nchan);
     if (!seeds && c->ref_start.size() < (size_t) nblocks * (size_t) nchan) c->ref_start.resize((size_t) nblocks * (size_t) nchan);
     std::vector<gpsiq_patch_t> patches;
-    RefRender r;
-    int rc = r.begin(c, nblocks, nchan, nsamp, sample_size, dst, dst_is_device, c->call_block);
+    PieceOut out;
+    int rc = out.begin(c, nblocks, nsamp, sample_size, dst, dst_is_device);
     if (rc) return rc;
-    const int chunk = ref_chunk_blocks(nblocks, nsamp);
+    const int chunk = ref_chunk_blocks(nblocks, nsamp, piece_blocks_env());
     std::vector<int> ends;
     const bool dev_chain = !seeds && chain_on_device(nblocks, nsamp, nchan);
     // (few growing pieces also with the chain on the device were tried: a 600-block piece is 0.3 ms of evaluation before it can
     // render, and the device waits for it: 2.6 ms per call against 2.4 at 2.6 Msps, profiles/r05_chain_ab.txt)
-    piece_ends(0, nblocks, chunk, &ends, ref_kernel_bound(nsamp, nchan));
+    piece_ends(0, nblocks, chunk, &ends, ref_kernel_bound(nsamp, nchan, rate_kernel(), host_threads()));
     // The carrier chain: level 1 (every block's certified map) on the device, parallel in time (gpsiq_chain_kernels.hip); the chain
     // tasks then link block to block through the maps.  Nothing renders before the first maps are back, and a launch is ~0.25 ms
     // however small: the timeline goes in two launches -- a head whose kernels cover the second launch, then the rest --, and the
@@ -910,13 +800,7 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
     if (dev_chain) {
         rc = chain_reserve(c, (size_t) nblocks * (size_t) nchan);
         if (rc) return rc;
-        // the head: pieces worth ~0.4 ms of synthesis (the second launch's latency + its first piece's evaluation)
-        const double t_block = (double) nsamp * (double) nchan / rate_kernel();
-        int want = (int) (0.4e-3 / t_block) + 1;
-        if (want > 0 && 2 * want < nblocks)                    // the first piece end at or beyond that (a bigger head measured better than a
-            for (size_t k = 0; k < ends.size(); ++k)           // smaller one: 2.35 ms per call at 900 blocks, 2.49 at 256, 2.55 at 128)
-                if (ends[k] >= want) { head = ends[k]; break; }
-        if (2 * head > nblocks) head = nblocks;                // what is left would not be worth a launch of its own
+        head = ref_head(ends, nblocks, nsamp, nchan, rate_kernel());
     }
     RefWalk w(ch, nblocks, nchan, 1.0 / fs, nsamp, q.data(), nullptr, nullptr, ends);
     w.seeds = seeds;                                         // start states known (gpsiq_generate_seeded): evaluation tasks only
@@ -955,7 +839,7 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
         w.take_patches(k, &patches, true);
         npatch += patches.size();
         const int b0 = k ? w.ends[k - 1] : 0;
-        rc = r.piece(q.data() + (size_t) b0 * nchan, b0, w.ends[k] - b0, patches);
+        rc = ref_piece(c, out, (int) k, q.data() + (size_t) b0 * nchan, b0, w.ends[k] - b0, nchan, nsamp, sample_size, c->call_block, patches);
         if (trace) {
             const double tq = wall_ms();
             t_wait += tp - tw; t_queue += tq - tp;
@@ -978,7 +862,7 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
     }
     if (threaded) pthread_join(th, nullptr);                 // the walkers read ch and write q: never leave them running
     const double tf = trace ? wall_ms() : 0.0;
-    const int frc = r.finish();
+    const int frc = out.finish("reference NCO pieces");
     if (rc != GPSIQ_OK) return fail(rc, "%s", err);
     if (w.rc != GPSIQ_OK) return fail(w.rc, "%s", w.err);
     if (frc != GPSIQ_OK) return frc;
@@ -1052,8 +936,7 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
         if (rc) return rc;
     } else {
         for (int i = 0; i < nchan; ++i) {
-            const bool cont = ch[i].prn > 0 && c->carry_prn[i] == ch[i].prn && c->handed[i] == ch[i].carr_phase;
-            rc = quantize_one(ch[i], delt, nsamp, cont ? &c->carry[i] : nullptr, &q[i], &next[i]);
+            rc = quantize_one(ch[i], delt, nsamp, gpsiq_continues(c, i, ch[i]) ? &c->carry[i] : nullptr, &q[i], &next[i]);
             if (rc) return rc;
         }
     }
@@ -1181,12 +1064,11 @@ static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
     const double t0 = trace ? wall_ms() : 0.0;
     // continue a previous call exactly where the caller hands back what it was given
     bool cont0[GPSIQ_MAX_CHAN];
-    for (int i = 0; i < nchan; ++i)
-        cont0[i] = ch[i].prn > 0 && c->carry_prn[i] == ch[i].prn && c->handed[i] == ch[i].carr_phase;
+    for (int i = 0; i < nchan; ++i) cont0[i] = gpsiq_continues(c, i, ch[i]);
     uint64_t carry[GPSIQ_MAX_CHAN] = {};
     int prev_prn[GPSIQ_MAX_CHAN] = {};
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size;
-    const int piece = batch_piece_blocks(nblocks, nsamp);
+    const int piece = batch_piece_blocks(nblocks, nsamp, piece_blocks_env());
     if (dst_is_device && !(blk_bytes & 15) && !((uintptr_t) dst & 3) && piece < nblocks && nsamp > 0) {
         // A long batch into device memory: quantise (= range-check), compact and upload piece k+1 on host threads under the
         // kernel of piece k; small pieces at both ends (piece_ends: nothing renders before the first piece is through, and the
@@ -1197,6 +1079,8 @@ static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
         bool cont[GPSIQ_MAX_CHAN];
         uint64_t seed[GPSIQ_MAX_CHAN];
         for (int i = 0; i < nchan; ++i) { cont[i] = cont0[i]; seed[i] = c->carry[i]; }
+        PieceOut out;                                                  // (direct: the rows are the caller's)
+        rc = out.begin(c, nblocks, nsamp, sample_size, dst, dst_is_device);
         std::vector<int> ends;
         // the quantiser is a fraction of the kernel's time (kernel-bound), but nothing renders before the first piece is through
         // it: the first piece is a sixteenth of the nominal one (64 blocks at 2.6 Msps: on the device 0.1 ms into the call), each
@@ -1215,8 +1099,7 @@ static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
             const double tq1 = trace_pieces ? wall_ms() : 0.0;
             if (rc == GPSIQ_OK) rc = set_descriptors_impl(c, q.data(), nb, nchan, nullptr, 0, true);
             const double tq2 = trace_pieces ? wall_ms() : 0.0;
-            if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nb, nsamp, sample_size, static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, blk_bytes, piece_stream(c, (int) k), kAuto,
-                                                c->call_block + (uint64_t) b0);
+            if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nb, nsamp, sample_size, out.target(b0), out.stride, gpsiq_piece_stream(c, (int) k), kAuto, c->call_block + (uint64_t) b0);
             if (trace_pieces)
                 std::fprintf(stderr, "[gpsiq trace]   piece %zu, blocks [%d, %d): quantise from %.3f to %.3f ms, descriptors queued at %.3f, launched at %.3f\n",
                              k, b0, b0 + nb, tq0 - t0, tq1 - t0, tq2 - t0, wall_ms() - t0);
@@ -1227,15 +1110,8 @@ static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
                 seed[i] = carry[i];
             }
         }
-        char err[400] = "";
-        if (rc != GPSIQ_OK) std::snprintf(err, sizeof err, "%s", gpsiq_last_error());
-        int src = gpsiq_synchronize(c, c->stream);                    // on every path: the kernels write the caller's buffer
-        const int src2 = gpsiq_synchronize(c, c->stream2);
-        if (src == GPSIQ_OK) src = src2;
-        if (src == GPSIQ_OK && hipStreamSynchronize(c->up_stream) != hipSuccess) src = fail(GPSIQ_E_DEVICE, "batch pieces: descriptor upload");
-        if (src == GPSIQ_OK) for (auto &b : c->buf) b.upload_pending = false;     // the uploads (also of a set never launched on) are done
-        if (rc != GPSIQ_OK) return fail(rc, "%s", err);
-        if (src != GPSIQ_OK) return src;
+        rc = out.finish("batch pieces", rc);                          // on every path: the kernels write the caller's buffer
+        if (rc != GPSIQ_OK) return rc;
         if (trace) std::fprintf(stderr, "[gpsiq trace] batch %d blocks in pieces of %d: whole call %.2f ms\n", nblocks, piece, wall_ms() - t0);
     } else {
         std::vector<gpsiq_qchan_t> &q = c->ref_q;
@@ -1249,12 +1125,7 @@ static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
             std::fprintf(stderr, "[gpsiq trace] batch %d blocks: quantise + carrier prefix %.2f ms, upload+kernel%s %.2f ms\n",
                          nblocks, t2 - t0, dst_is_device ? "" : "+D2H", wall_ms() - t2);
     }
-    for (int i = 0; i < nchan; ++i) {
-        c->carry_prn[i] = prev_prn[i];
-        c->carry[i] = carry[i];
-        c->handed[i] = prev_prn[i] ? carr_phase_to_double(carry[i]) : 0.0;
-        if (carr_phase_out) carr_phase_out[i] = c->handed[i];
-    }
+    for (int i = 0; i < nchan; ++i) gpsiq_hand_back(c, i, prev_prn[i], carry[i], carr_phase_out);      // (carry is 0 where prev_prn is: chain_carrier)
     return GPSIQ_OK;
 }
 
@@ -1348,10 +1219,10 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
         std::vector<Dev> devs((size_t) ndev);
         auto body = [](void *arg) -> void * {
             Dev &d = *static_cast<Dev *>(arg);
-            RefRender r;
-            d.rc = r.begin(d.c, d.range_blocks, d.nchan, d.nsamp, d.ss, d.dst, d.dst_is_device, d.nbase);
+            PieceOut out;
+            d.rc = out.begin(d.c, d.range_blocks, d.nsamp, d.ss, d.dst, d.dst_is_device);
             if (d.rc != GPSIQ_OK) std::snprintf(d.err, sizeof d.err, "%s", gpsiq_last_error());
-            for (;;) {
+            for (int k = 0;; ++k) {
                 pthread_mutex_lock(&d.mu);
                 while (d.items.empty() && !d.closed) pthread_cond_wait(&d.cv, &d.mu);
                 if (d.items.empty()) { pthread_mutex_unlock(&d.mu); break; }
@@ -1359,10 +1230,10 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
                 d.items.pop_front();
                 pthread_mutex_unlock(&d.mu);
                 if (d.rc != GPSIQ_OK) continue;                       // after an error: take the rest off the queue, render nothing
-                d.rc = r.piece(it.q, it.b0, it.nb, it.patches);
+                d.rc = ref_piece(d.c, out, k, it.q, it.b0, it.nb, d.nchan, d.nsamp, d.ss, d.nbase, it.patches);
                 if (d.rc != GPSIQ_OK) std::snprintf(d.err, sizeof d.err, "%s", gpsiq_last_error());
             }
-            const int frc = r.finish();
+            const int frc = out.finish("reference NCO pieces");
             if (d.rc == GPSIQ_OK && frc != GPSIQ_OK) { d.rc = frc; std::snprintf(d.err, sizeof d.err, "%s", gpsiq_last_error()); }
             return nullptr;
         };
@@ -1385,7 +1256,7 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
             (void) gpsiq_shard_range(nblocks, i, ndev, &r0, &r1);
             if (r1 == r0) continue;
             const size_t before = ends.size();
-            piece_ends(r0, r1 - r0, ref_chunk_blocks(r1 - r0, nsamp), &ends, ref_kernel_bound(nsamp, nchan));
+            piece_ends(r0, r1 - r0, ref_chunk_blocks(r1 - r0, nsamp, piece_blocks_env()), &ends, ref_kernel_bound(nsamp, nchan, rate_kernel(), host_threads()));
             owner.insert(owner.end(), ends.size() - before, i);
         }
         // the carrier chain: level 1 of the whole timeline on the first device (one launch; a GPU walks an hour of config 5 in
@@ -1460,8 +1331,7 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
     int prev_prn[GPSIQ_MAX_CHAN] = {};
     {
         bool cont0[GPSIQ_MAX_CHAN];
-        for (int i = 0; i < nchan; ++i)
-            cont0[i] = ch[i].prn > 0 && c0->carry_prn[i] == ch[i].prn && c0->handed[i] == ch[i].carr_phase;
+        for (int i = 0; i < nchan; ++i) cont0[i] = gpsiq_continues(c0, i, ch[i]);
         rc = quantize_timeline(ch, nblocks, nchan, 1.0 / fs, nsamp, cont0, c0->carry, q.data(), carry, prev_prn);
     }
     if (rc) return rc;
@@ -1496,12 +1366,7 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
     }
     for (int i = 0; i < ndev; ++i)
         if (parts[(size_t) i].rc != GPSIQ_OK) return fail(parts[(size_t) i].rc, "device range %d: %s", i, parts[(size_t) i].err);
-    for (int i = 0; i < nchan; ++i) {
-        c0->carry_prn[i] = prev_prn[i];
-        c0->carry[i] = carry[i];
-        c0->handed[i] = prev_prn[i] ? carr_phase_to_double(carry[i]) : 0.0;
-        if (carr_phase_out) carr_phase_out[i] = c0->handed[i];
-    }
+    for (int i = 0; i < nchan; ++i) gpsiq_hand_back(c0, i, prev_prn[i], carry[i], carr_phase_out);      // (carry is 0 where prev_prn is: chain_carrier)
     return GPSIQ_OK;
 }
 
@@ -1589,8 +1454,6 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
 double gpsiq_wall_ms() { return wall_ms(); }
 int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b) { return wait_idle(b); }
 int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s) { return mark_use(b, s); }
-int gpsiq_ensure_out(gpsiq_ctx *c, size_t bytes) { return ensure_out(c, bytes); }
-hipStream_t gpsiq_piece_stream(gpsiq_ctx *c, int k) { return piece_stream(c, k); }
 int gpsiq_chain_reserve(gpsiq_ctx *c, size_t n) { return chain_reserve(c, n); }
 double gpsiq_rate_kernel() { return rate_kernel(); }
 void gpsiq_note_kernel_rate(double channel_samples_per_s)

@@ -23,6 +23,7 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_eval.h"
+#include "gpsiq_pieces.h"
 
 using namespace gpsiq;
 
@@ -102,33 +103,6 @@ int evd_reserve(gpsiq_ctx *c, size_t n, SrcKind kind, bool seeds)
         e.seeds_cap = n + n / 4 + 16;
     }
     return GPSIQ_OK;
-}
-
-// Piece boundaries.  A piece's synthesis waits for its own descriptors only (pack, estimate, quantise), so pieces exist to start
-// the first synthesis early and to stage piece k+1 under the synthesis of piece k; every further piece costs a launch ramp
-// (~0.05 ms).  Descriptors the device reads where they lie stage in microseconds: one piece in the fixed-point model, a short
-// head in GPSIQ_NCO_REFERENCE (chain_prepare is 16 workgroups walking the timeline: 25 us per 1 000 blocks).  Pageable
-// descriptors are packed by the pool at ~14 x the synthesis rate (16 threads; 2 x with two): a head worth 0.35 ms of synthesis, so
-// that the pack of what follows hides under it, then pieces eight times the one before (measured, 2.6 Msps: 2 000 blocks fixed
-// model 1.56 ms per call against 1.74 with a 0.1 ms head, reference model 1.85 against 2.06).
-// GPSIQ_PIECE_BLOCKS (blocks of the first piece; <= 0: one piece) for A/B, read per call.
-void device_piece_ends(int nblocks, int nsamp, int nchan, bool pageable /* or page-locked: host memory */, bool reference, std::vector<int> *ends)
-{
-    const double t_block = (double) nsamp * (double) nchan / gpsiq_rate_kernel();
-    long head = (long) ((pageable ? 0.35e-3 : 0.15e-3) / (t_block > 0.0 ? t_block : 1e-6)) + 1;
-    if (head < 16) head = 16;
-    if (!pageable && !reference) head = 0;
-    if (const char *e = std::getenv("GPSIQ_PIECE_BLOCKS")) head = std::atol(e);
-    const long growth = 8;
-    if (head <= 0 || 2 * head > nblocks) { ends->push_back(nblocks); return; }
-    long b = head, size = growth * head;
-    ends->push_back((int) b);
-    while (nblocks - b > size + size / 2 && (int) ends->size() < kEvalMaxPieces - 1) {
-        b += size;
-        ends->push_back((int) b);
-        size *= growth;
-    }
-    ends->push_back(nblocks);
 }
 
 // descriptors in pageable memory: cut down to ev::DChan on the pool, with the synthesis kernel's launch parameters on the way
@@ -303,9 +277,9 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     }
 
     // destination: straight into the caller's device memory where its rows are ours, else through the context's staging
-    const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, stride = (blk_bytes + 15) & ~(size_t) 15;
-    const bool direct = dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3);
-    if (!direct) { rc = gpsiq_ensure_out(c, stride * (size_t) nblocks); if (rc) return rc; }
+    PieceOut out;
+    rc = out.begin(c, nblocks, nsamp, sample_size, dst, dst_is_device);
+    if (rc) return rc;
 
     // the descriptor set the evaluation writes and the synthesis reads: one for the whole call
     int nsets = gpsiq_ctx::kSets;
@@ -321,7 +295,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     }
 
     std::vector<int> ends;
-    device_piece_ends(nblocks, nsamp, nchan, kind != kSrcDevice, reference, &ends);          // (page-locked rows cross PCIe too: staged like pageable ones)
+    device_piece_ends(nblocks, nsamp, nchan, kind != kSrcDevice, reference, gpsiq_rate_kernel(), piece_blocks_env(), kEvalMaxPieces, &ends);
     const int npieces = (int) ends.size();
     hipStream_t S = e.chain_stream, E = e.eval_stream;
     ev::DChan *d_chan = static_cast<ev::DChan *>(e.d_chan), *h_chan = static_cast<ev::DChan *>(e.h_chan);
@@ -338,7 +312,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     bool cont0[GPSIQ_MAX_CHAN] = {};
     if (!reference) {
         for (int i = 0; i < nchan; ++i) {
-            cont0[i] = first[i].prn > 0 && c->carry_prn[i] == first[i].prn && c->handed[i] == first[i].carr_phase;
+            cont0[i] = gpsiq_continues(c, i, first[i]);
             e.h_fix[i].phase = c->carry[i]; e.h_fix[i].prn = c->carry_prn[i]; e.h_fix[i].cont = cont0[i] ? 1 : 0;
         }
         HIP_TRY(hipMemcpyAsync(e.d_fix, e.h_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyHostToDevice, S));
@@ -354,7 +328,6 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     int max_active = 0;
     long max_amp = 0;
     uint64_t max_step = 0;
-    int copies = 0;
     double t_first_launch = 0.0;
     int timed_blocks = 0;
     hipEvent_t *staged = e.evaluated;                       // [k]: piece k's descriptors are in the set (and a snapshot of the control block behind them)
@@ -397,28 +370,17 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
         he = hipStreamWaitEvent(s, staged[k], 0);
         if (he == hipSuccess) {
             const int v = max_step <= kRowsMaxCodeStep ? kSeg : max_step <= kHalfRowsMaxCodeStep ? kSegHalf : kGeneric;
-            uint8_t *dev = direct ? static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes : static_cast<uint8_t *>(c->d_out) + (size_t) b0 * stride;
             // the last piece's synthesis is timed: the rate the piece sizes are planned with is a measured one (gpsiq_note_kernel_rate)
             if (k == npieces - 1) (void) hipEventRecord(e.t_synth0, s);
-            he = launch_variant(v, nb_.d, nchan, nsamp, sample_size, dev, stride, b0, nb, c->d_tab, s, max_active > 0 ? max_active : 1, max_amp, nullptr,
+            he = launch_variant(v, nb_.d, nchan, nsamp, sample_size, out.target(b0), out.stride, b0, nb, c->d_tab, s, max_active > 0 ? max_active : 1, max_amp, nullptr,
                                 gpsiq_noise_at(c, c->call_block));
             if (k == npieces - 1) { (void) hipEventRecord(e.t_synth1, s); timed_blocks = nb; }
             if (trace && k == 0) t_first_launch = gpsiq_wall_ms() - t0;
-            if (he == hipSuccess && !direct) {
-                // a piece crosses to the destination as soon as it is rendered (the next piece's kernel covers the copy); in
-                // GPSIQ_NCO_REFERENCE the few blocks that hold a patched sample are copied once more behind apply_patches
-                hipStream_t cs = c->copy_stream[copies & 1];
-                he = hipEventRecord(c->chunk_done[copies & 1], s);
-                if (he == hipSuccess) he = hipStreamWaitEvent(cs, c->chunk_done[copies & 1], 0);
-                const hipMemcpyKind kd = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-                if (he == hipSuccess) {
-                    if (stride == blk_bytes) he = hipMemcpyAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, dev, blk_bytes * (size_t) nb, kd, cs);
-                    else he = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * blk_bytes, blk_bytes, dev, stride, blk_bytes, (size_t) nb, kd, cs);
-                }
-                ++copies;
-            }
         }
+        // a piece crosses to the destination as soon as it is rendered (the next piece's kernel covers the copy); in
+        // GPSIQ_NCO_REFERENCE the few blocks that hold a patched sample are copied once more behind apply_patches
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d launch: %s", k, hipGetErrorString(he)); }
+        else if (out.rendered(b0, nb, s) != GPSIQ_OK) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d launch: %s", k, gpsiq_last_error()); }
     }
     const double t_queued = gpsiq_wall_ms();
 
@@ -628,30 +590,11 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
                 std::memcpy(e.h_patches, patches.data(), npatch_total * sizeof(gpsiq_patch_t));
                 he = hipMemcpyAsync(nb_.d_patch, e.h_patches, npatch_total * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);
             }
-            uint8_t *dev = direct ? static_cast<uint8_t *>(dst) : static_cast<uint8_t *>(c->d_out);
-            if (he == hipSuccess) he = launch_patches(nb_.d, nchan, nsamp, sample_size, dev, stride, 0, nblocks, c->d_tab, nb_.d_patch, (int) npatch_total, c->stream,
-                                                       gpsiq_noise_at(c, c->call_block));
-        }
-        if (he == hipSuccess && !direct && npatch_total) {
-            // the blocks apply_patches touched go to the destination again -- behind the pieces' own copies, which may still be
-            // on their way (join the copy streams) -- or the whole timeline when that is most of it
-            const hipMemcpyKind kd = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            for (int k = 0; k < 2 && he == hipSuccess; ++k) {
-                he = hipEventRecord(c->chunk_done[k], c->copy_stream[k]);
-                if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, c->chunk_done[k], 0);
-            }
-            size_t touched = 0;
-            for (size_t k = 0; k < patches.size(); ++k) touched += k == 0 || patches[k].block != patches[k - 1].block;
-            if (he == hipSuccess && touched * 4 > (size_t) nblocks) {
-                if (stride == blk_bytes) he = hipMemcpyAsync(dst, c->d_out, blk_bytes * (size_t) nblocks, kd, c->stream);
-                else he = hipMemcpy2DAsync(dst, blk_bytes, c->d_out, stride, blk_bytes, (size_t) nblocks, kd, c->stream);
-            } else
-                for (size_t k = 0; k < patches.size() && he == hipSuccess; ++k)
-                    if (k == 0 || patches[k].block != patches[k - 1].block)
-                        he = hipMemcpyAsync(static_cast<uint8_t *>(dst) + (size_t) patches[k].block * blk_bytes,
-                                            static_cast<uint8_t *>(c->d_out) + (size_t) patches[k].block * stride, blk_bytes, kd, c->stream);
+            if (he == hipSuccess) he = launch_patches(nb_.d, nchan, nsamp, sample_size, out.target(0), out.stride, 0, nblocks, c->d_tab, nb_.d_patch, (int) npatch_total,
+                                                       c->stream, gpsiq_noise_at(c, c->call_block));
         }
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, patches: %s", hipGetErrorString(he)); }
+        else if (out.again(c->stream, patches) != GPSIQ_OK) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, patches: %s", gpsiq_last_error()); }
     }
 
     // ---- GPSIQ_CHAIN_VERIFY=N: every N-th block that went through its certified map is also walked serially ---------------------
@@ -701,12 +644,11 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
 
     // ---- drain: on every path nothing may still be writing the caller's buffer or reading our staging -------------------------
     const double t_drain = gpsiq_wall_ms();
-    const hipError_t d0 = hipStreamSynchronize(S), d1 = hipStreamSynchronize(E), d2 = hipStreamSynchronize(c->stream), d3 = hipStreamSynchronize(c->stream2);
-    const hipError_t d4 = hipStreamSynchronize(c->copy_stream[0]), d5 = hipStreamSynchronize(c->copy_stream[1]);
-    if (rc == GPSIQ_OK)
-        for (hipError_t d : {d0, d1, d2, d3, d4, d5})
-            if (d != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation: %s", hipGetErrorString(d)); break; }
-    if (rc != GPSIQ_OK) return fail(rc, "%s", err);
+    const hipError_t d0 = hipStreamSynchronize(S), d1 = hipStreamSynchronize(E);
+    if (rc == GPSIQ_OK && (d0 != hipSuccess || d1 != hipSuccess))
+        { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation: %s", hipGetErrorString(d0 != hipSuccess ? d0 : d1)); }
+    rc = out.finish("device evaluation", rc != GPSIQ_OK ? fail(rc, "%s", err) : GPSIQ_OK);     // (after an error: drains, the error stands)
+    if (rc != GPSIQ_OK) return rc;
     if (timed_blocks > 0) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, e.t_synth0, e.t_synth1) == hipSuccess && ms > 0.02f)
@@ -733,12 +675,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
             }
         chain_count((long) fin.linked, 0);
     } else {
-        for (int i = 0; i < nchan; ++i) {
-            c->carry_prn[i] = e.h_fix[i].prn;
-            c->carry[i] = e.h_fix[i].prn ? e.h_fix[i].phase : 0;
-            c->handed[i] = e.h_fix[i].prn ? carr_phase_to_double(c->carry[i]) : 0.0;
-            if (carr_phase_out) carr_phase_out[i] = c->handed[i];
-        }
+        for (int i = 0; i < nchan; ++i) gpsiq_hand_back(c, i, e.h_fix[i].prn, e.h_fix[i].phase, carr_phase_out);
     }
     e.last_nhost = fin.nhost; e.last_npatch = (unsigned) npatch_total;
     __atomic_fetch_add(&g_evd_stats[1], (uint64_t) n, __ATOMIC_RELAXED);
