@@ -339,7 +339,7 @@ typedef struct gpsiq_noise {
     double   sigma;
     uint64_t next_block;   /* absolute index of the next drop-in call's block 0 */
 } gpsiq_noise_t;
-/* NULL turns noise off (the counter is kept). */
+/* NULL turns noise off (the counter is kept).  A gain and a saturating quantiser behind the noise: gpsiq_set_level, gpsiq_rows.h. */
 int gpsiq_set_noise(gpsiq_ctx_t *ctx, const gpsiq_noise_t *noise);
 
 /* ---- [boundary] hand-off to fifo.h buffers (gps.c:2847-2865) -------------------------- */

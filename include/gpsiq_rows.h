@@ -165,6 +165,31 @@ int gpsiq_rinex_select(const gpsiq_rinex_eph_t *eph, int nsets, int week, double
  * the carrier table's amplitude is 250, so C = (250*gain)^2 and N0 = 2*sigma^2/fs, i.e. 250*|gain|*sqrt(fs / (2*10^(cn0/10))). */
 double gpsiq_noise_sigma_for_cn0(double cn0_dbhz, double gain, double fs);
 
+/* ---- Output level: scale, round and saturate in the kernels --------------------------------------------------------------
+ * A gain in front of the quantiser and a quantiser that saturates, as every front end has.  Off by default, and with the level off
+ * every output byte is what include/gpsiq.h states (the sums wrap, the int8 stream keeps bits 4..11).  With the level on, for each
+ * sample and for I and Q alike:
+ *     S   = the noiseless int16 element of the contract: (short)(sum over channels)                     (gps.c:2834)
+ *     A   = S + z(n)                     plain integer, no wrap; z = 0 while the noise is off
+ *     y   = floor((A * mult + 32768) / 65536)               exact integer arithmetic
+ *     out = min(max(y, -qmax), qmax)
+ * stored as int16 for GPSIQ_SC16 and as int8 for GPSIQ_SC08: there is no >> 4 in the int8 path, the level takes its place.  Unlike
+ * the noise-only path, where the noise is added into the 16-bit sum and wraps with it, the noise is added after the signal sum
+ * has been taken out, in 32 bits, so any sigma gpsiq_set_noise accepts is representable.  The clamp is symmetric: no DC offset.
+ * qmax = 1 gives a 3-level stream, 7 a 4-bit one, 2047 a 12-bit DAC's range, each in the int8 / int16 container.
+ * Ranges: 1 <= mult < 2^24; 1 <= qmax <= 32767, and <= 127 when a call renders GPSIQ_SC08 (checked by the rendering call, since the
+ * format is its argument); otherwise GPSIQ_E_ARG.  Every drop-in call and gpsiq_launch honour it; gpsiq_generate_batch_multi uses
+ * ctx[0]'s setting for every device.  Kernel variants without the stage return GPSIQ_E_STATE while it is on, as for the noise. */
+typedef struct gpsiq_level {
+    uint32_t mult;                 /* Q16: the scale is mult / 65536 */
+    int32_t  qmax;                 /* symmetric clamp */
+} gpsiq_level_t;
+int gpsiq_set_level(gpsiq_ctx_t *ctx, const gpsiq_level_t *level);      /* NULL: off */
+/* rms per component (I or Q) of nchan channels and noise of this sigma, in accumulator units: sqrt(sigma^2 + sum (250*gain)^2 / 2) */
+double gpsiq_composite_rms(const double *gain, int nchan, double sigma);
+/* the multiplier that takes rms_in to rms_out: rint(65536 * rms_out / rms_in), clamped to [1, 2^24 - 1] */
+uint32_t gpsiq_level_mult(double rms_in, double rms_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -63,6 +63,13 @@ struct gpsiq_ctx {
         gpsiq::noise::Entry *d_tab = nullptr;          // gpsiq::noise::kTabEntries, on the context's device
     } noise;
     uint64_t       call_block = 0;
+    // output level stage (gpsiq_set_level, include/gpsiq_rows.h): on while mult != 0.  d_zero is the all-zero noise table the
+    // kernels read while the level is on and the noise is off
+    struct Level {
+        uint32_t mult = 0;
+        int32_t  qmax = 0;
+        gpsiq::noise::Entry *d_zero = nullptr;
+    } level;
     // scratch of the kernel variants that need some (segm: the sign masks of one launch)
     void          *d_scratch = nullptr;
     size_t         scratch_cap = 0;
@@ -135,7 +142,7 @@ struct gpsiq_ctx {
 
 
 // helpers of gpsiq_device.cpp the other translation unit uses
-// the noise of launches whose descriptor array starts at absolute block `block` (tab == nullptr while noise is off)
+// the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
 gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
 double gpsiq_wall_ms();
 int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b);

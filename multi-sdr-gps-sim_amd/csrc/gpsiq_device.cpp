@@ -74,6 +74,14 @@ static long noise_table(double sigma, gpsiq::noise::Entry *tab)
     return tab[gpsiq::noise::kEntries - 1].base;
 }
 
+// the clamp has to fit the format, which only a rendering call knows
+static int check_level(const gpsiq_ctx *c, int sample_size)
+{
+    if (c->level.mult && c->level.qmax > (sample_size == GPSIQ_SC08 ? 127 : 32767))
+        return fail(GPSIQ_E_ARG, "output level: qmax %d does not fit %d-byte samples", (int) c->level.qmax, sample_size);
+    return GPSIQ_OK;
+}
+
 static bool noise_variant_ok(int v) { return v == kAuto || v == kGeneric || v == kTile || v == kSeg || v == kSegHalf; }
 
 static int pick_variant(const gpsiq_ctx *c, int variant)
@@ -98,6 +106,9 @@ static int check_launch(const gpsiq_ctx *c, int block0, int nblocks, int nsamp, 
     if (variant < 0 || variant >= kNumVariants) return fail(GPSIQ_E_ARG, "unknown variant %d", variant);
     if (c->noise.sigma > 0.0 && !noise_variant_ok(variant))
         return fail(GPSIQ_E_STATE, "variant %d has no receiver-noise path: turn noise off (gpsiq_set_noise) or use 0/generic/tile/seg/segh", variant);
+    if (c->level.mult && !noise_variant_ok(variant))
+        return fail(GPSIQ_E_STATE, "variant %d has no output-level path: turn the level off (gpsiq_set_level) or use 0/generic/tile/seg/segh", variant);
+    if (int rc = check_level(c, sample_size)) return rc;
     if (variant == kSegHalf && c->max_code_step > kHalfRowsMaxCodeStep)
         return fail(GPSIQ_E_RANGE, "half-row kernel needs f_code/fs <= 1 chip per sample");
     if (variant >= kRows && variant != kSegHalf && c->max_code_step > kRowsMaxCodeStep)
@@ -186,6 +197,7 @@ void gpsiq_destroy(gpsiq_ctx_t *c)
     if (c->chain.back) (void) hipStreamDestroy(c->chain.back);
     if (c->chain.stream) (void) hipStreamDestroy(c->chain.stream);
     if (c->noise.d_tab) (void) hipFree(c->noise.d_tab);
+    if (c->level.d_zero) (void) hipFree(c->level.d_zero);
     if (c->stream) (void) hipStreamDestroy(c->stream);
     if (c->stream2) (void) hipStreamDestroy(c->stream2);
     if (c->up_stream) (void) hipStreamDestroy(c->up_stream);
@@ -588,7 +600,7 @@ static int check_gen_args(const gpsiq_ctx *c, const void *ch, const void *dst, i
     if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
     if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
     if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
-    return GPSIQ_OK;
+    return check_level(c, sample_size);
 }
 
 // ---- GPSIQ_NCO_REFERENCE: walk and render in pieces ------------------------------------------
@@ -1147,12 +1159,13 @@ int gpsiq_generate_seeded(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
 }
 
 static int set_noise_impl(gpsiq_ctx *c, uint64_t seed, double sigma);
+static int set_level_impl(gpsiq_ctx *c, uint32_t mult, int32_t qmax);
 static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
                                 int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
                                 double *carr_phase_out);
 
-// Every range is rendered with ctx[0]'s noise settings and numbering (device i from next_block + begin_i): the other contexts
-// take ctx[0]'s seed and sigma for the call and get their own back after it.
+// Every range is rendered with ctx[0]'s noise and level settings and numbering (device i from next_block + begin_i): the other
+// contexts take ctx[0]'s seed, sigma and level for the call and get their own back after it.
 int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
                                int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
                                double *carr_phase_out)
@@ -1163,15 +1176,20 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
         return generate_batch_multi(ctx, ndev, ch, nblocks, nchan, nsamp, fs, sample_size, host_dst, dev_dst, carr_phase_out);
     const gpsiq_ctx::Noise &n0 = ctx[0]->noise;
     std::vector<gpsiq_ctx::Noise> own((size_t) ndev);
+    std::vector<gpsiq_ctx::Level> own_level((size_t) ndev);
+    for (int i = 0; i < ndev; ++i) own_level[(size_t) i] = ctx[i]->level;
     int rc = GPSIQ_OK;
     for (int i = 1; i < ndev && rc == GPSIQ_OK; ++i) {
         own[(size_t) i] = ctx[i]->noise;
         if (ctx[i]->noise.seed != n0.seed || ctx[i]->noise.sigma != n0.sigma) rc = set_noise_impl(ctx[i], n0.seed, n0.sigma);
+        if (rc == GPSIQ_OK) rc = set_level_impl(ctx[i], ctx[0]->level.mult, ctx[0]->level.qmax);
     }
     if (rc == GPSIQ_OK)
         rc = generate_batch_multi(ctx, ndev, ch, nblocks, nchan, nsamp, fs, sample_size, host_dst, dev_dst, carr_phase_out);
     if (rc == GPSIQ_OK) ctx[0]->noise.next_block += (uint64_t) nblocks;
     for (int i = 1; i < ndev; ++i) {
+        ctx[i]->level.mult = own_level[(size_t) i].mult;           // (the zero table stays: it belongs to the context's device)
+        ctx[i]->level.qmax = own_level[(size_t) i].qmax;
         const gpsiq_ctx::Noise &o = own[(size_t) i];
         if (ctx[i]->noise.seed != o.seed || ctx[i]->noise.sigma != o.sigma) {
             char err[400];
@@ -1408,6 +1426,30 @@ int gpsiq_set_noise(gpsiq_ctx_t *c, const gpsiq_noise_t *nz)
     return rc;
 }
 
+// ---- output level (include/gpsiq_rows.h; libgpsiq_rows.so's gpsiq_set_level arrives here through the plumbing entry "set_level") ----
+static int set_level_impl(gpsiq_ctx *c, uint32_t mult, int32_t qmax)
+{
+    if (mult && !c->level.d_zero) {
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t bytes = sizeof(gpsiq::noise::Entry) * gpsiq::noise::kTabEntries;
+        HIP_TRY(hipMalloc(&c->level.d_zero, bytes));
+        HIP_TRY(hipMemset(c->level.d_zero, 0, bytes));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    c->level.mult = mult;
+    c->level.qmax = mult ? qmax : 0;
+    return GPSIQ_OK;
+}
+
+static int set_level(gpsiq_ctx_t *c, const gpsiq_level_t *lv)
+{
+    if (!c) return fail(GPSIQ_E_ARG, "null context");
+    if (!lv) return set_level_impl(c, 0, 0);
+    if (lv->mult < 1u || lv->mult >= (1u << 24)) return fail(GPSIQ_E_ARG, "output level: mult %u outside [1, 2^24)", lv->mult);
+    if (lv->qmax < 1 || lv->qmax > 32767) return fail(GPSIQ_E_ARG, "output level: qmax %d outside [1, 32767]", (int) lv->qmax);
+    return set_level_impl(c, lv->mult, lv->qmax);
+}
+
 int gpsiq_noise_state(const gpsiq_ctx_t *c, gpsiq_noise_t *out)
 {
     if (!c || !out) return fail(GPSIQ_E_ARG, "null argument");
@@ -1447,6 +1489,11 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
         nz.block = block;
         nz.max_z = c->noise.max_z;
     }
+    if (c->level.mult) {
+        nz.mult = c->level.mult;
+        nz.qmax = c->level.qmax;
+        if (!nz.tab) { nz.tab = c->level.d_zero; nz.block = block; }     // noise off: the level kernels draw zeros
+    }
     return nz;
 }
 
@@ -1482,6 +1529,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         // the internals libgpsiq_rows.so runs on (gpsiq_rows_link.cpp): one pool, one quantiser, one error text per thread
         {"set_error", reinterpret_cast<void *>(&gpsiq::set_error)}, {"parallel_for", reinterpret_cast<void *>(&gpsiq::parallel_for)},
         {"quantize_one", reinterpret_cast<void *>(&gpsiq::quantize_one)}, {"chain_carrier", reinterpret_cast<void *>(&gpsiq::chain_carrier)},
+        {"set_level", reinterpret_cast<void *>(&set_level)},      // gpsiq_set_level of libgpsiq_rows.so (include/gpsiq_rows.h)
     };
     if (!name) return nullptr;
     for (const auto &e : table)

@@ -73,6 +73,17 @@ __device__ __forceinline__ void store_sample(uint8_t *__restrict__ blk_dst, uint
     }
 }
 
+// the sample with the output level stage: i_acc / q_acc are the noiseless sums, zi / zq the sample's noise
+template <int FMT>
+__device__ __forceinline__ void store_level(uint8_t *__restrict__ blk_dst, uint32_t n, int i_acc, int q_acc, int zi, int zq,
+                                            uint32_t lmult, int32_t lqmax)
+{
+    const uint32_t oi = (uint32_t) level::apply((int16_t) i_acc + zi, lmult, lqmax);
+    const uint32_t oq = (uint32_t) level::apply((int16_t) q_acc + zq, lmult, lqmax);
+    if (FMT == GPSIQ_SC16) reinterpret_cast<uint32_t *>(blk_dst)[n] = (oi & 0xffffu) | (oq << 16);
+    else                   reinterpret_cast<uint16_t *>(blk_dst)[n] = (uint16_t) ((oi & 0xffu) | (oq << 8));
+}
+
 // ---------------------------------------------------------------------------
 // Generic kernel: one sample per thread per step, every quantity of the closed form
 // evaluated at full width for that sample.  Works for any rate the descriptor format
@@ -84,7 +95,7 @@ template <int FMT>
 __global__ __launch_bounds__(kGenericThreads) void synth_generic(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
     size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
-    int tile_samples, const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
+    int tile_samples, const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0, uint32_t lmult, int32_t lqmax)
 {
     __shared__ uint32_t lut[kMaxChan][512];
     __shared__ uint32_t ext[kMaxChan][kPrnExtWords];
@@ -108,12 +119,12 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
         noise::jump(kGenericThreads / 64, noise::kMul, noise::kInc, &nA, &nC);
     }
     for (uint32_t n = n_begin + threadIdx.x; n < n_end; n += kGenericThreads) {
-        int i_acc = 0, q_acc = 0;
+        int i_acc = 0, q_acc = 0, zi = 0, zq = 0;
         if (ntab) {
             const uint32_t w = noise::xsh_rr(nx);
             nx = nA * nx + nC;
-            i_acc = noise::z(ntab, w & 0xffffu);
-            q_acc = noise::z(ntab, w >> 16);
+            zi = noise::z(ntab, w & 0xffffu);
+            zq = noise::z(ntab, w >> 16);
         }
         for (int c = 0; c < nchan; ++c) {
             const gpsiq_qchan_t &q = qs[c];
@@ -132,7 +143,8 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
             i_acc += neg ? -tc : tc;
             q_acc += neg ? -ts : ts;
         }
-        store_sample<FMT>(blk_dst, n, ((uint32_t) i_acc & 0xffffu) | ((uint32_t) q_acc << 16));
+        if (lmult) store_level<FMT>(blk_dst, n, i_acc, q_acc, zi, zq, lmult, lqmax);
+        else store_sample<FMT>(blk_dst, n, ((uint32_t) (i_acc + zi) & 0xffffu) | ((uint32_t) (q_acc + zq) << 16));
     }
 }
 
@@ -429,15 +441,20 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rowsx(
 //     lane stream `lane` of its block and its wave's rows are consecutive, so after a wave-uniform jump to the wave's first row
 //     a row costs one LCG step, xsh_rr and two gathers in the scaled table (LDS, beside the carrier LUT).  Both kernels include
 //     one body (gpsiq_tile_body.inc) with NOISE a constant: the noise-off kernels keep their names and their code.
+//   * LEVEL (synth_tile_level): the output level stage (include/gpsiq_rows.h) behind the noise: I and Q come out of the packed word
+//     sign-extended, the noise is added in 32 bits, then multiply-add, shift and clamp per component and one packed store.  Both
+//     output formats run the int16 cores (the int8 core's 12-bit fields cannot give the whole sums back).
 template <int FMT, int NCH, int ROWS, int H, bool FAST, int WAVES = kWaves, bool BOTH = false>
 __global__ __launch_bounds__(WAVES * 64, 4) void synth_tile(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
     size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
     int wave_rows, int big_wgs, int big_blocks, int tiles_small)
 {
-    constexpr bool NOISE = false;
+    constexpr bool NOISE = false, LEVEL = false;
     [[maybe_unused]] constexpr const noise::Entry *ntab = nullptr;
     [[maybe_unused]] constexpr uint64_t nseed = 0, nblock0 = 0;
+    [[maybe_unused]] constexpr uint32_t lmult = 0;
+    [[maybe_unused]] constexpr int32_t lqmax = 0;
 #include "gpsiq_tile_body.inc"
 }
 
@@ -450,7 +467,24 @@ __global__ __launch_bounds__(kWaves * 64, 4) void synth_tile_noise(
     const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
 {
     constexpr int WAVES = kWaves;
-    constexpr bool BOTH = false, NOISE = true;
+    constexpr bool BOTH = false, NOISE = true, LEVEL = false;
+    [[maybe_unused]] constexpr uint32_t lmult = 0;
+    [[maybe_unused]] constexpr int32_t lqmax = 0;
+#include "gpsiq_tile_body.inc"
+}
+
+// the same with the output level stage behind the noise (include/gpsiq_rows.h): lmult / 65536 is the scale, lqmax the clamp.  While
+// the noise is off ntab is an all-zero table (the host's choice).  FAST here means the int16 plain-add core, for
+// either output format.
+template <int FMT, int NCH, int ROWS, int H, bool FAST>
+__global__ __launch_bounds__(kWaves * 64, 4) void synth_tile_level(
+    const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
+    size_t block_stride, int block0, const DeviceTables *__restrict__ tab, int tiles_per_block,
+    int wave_rows, int big_wgs, int big_blocks, int tiles_small,
+    const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0, uint32_t lmult, int32_t lqmax)
+{
+    constexpr int WAVES = kWaves;
+    constexpr bool BOTH = false, NOISE = true, LEVEL = true;
 #include "gpsiq_tile_body.inc"
 }
 
@@ -613,7 +647,7 @@ template <int FMT>
 __global__ __launch_bounds__(64) void apply_patches(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst, size_t block_stride,
     int block0, int nblocks, const DeviceTables *__restrict__ tab, const gpsiq_patch_t *__restrict__ pt, int npatch,
-    const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0)
+    const noise::Entry *__restrict__ ntab, uint64_t nseed, uint64_t nblock0, uint32_t lmult, int32_t lqmax)
 {
     const int i = (int) (blockIdx.x * 4u + (threadIdx.x >> 4));      // four patches per wave
     const int c = (int) (threadIdx.x & 15u);                          // this lane's channel slot (GPSIQ_MAX_CHAN = 16)
@@ -646,15 +680,14 @@ __global__ __launch_bounds__(64) void apply_patches(
         i_acc += __shfl_xor(i_acc, off, 16);
         q_acc += __shfl_xor(q_acc, off, 16);
     }
-    if (lead && c == 0 && ntab) {                                     // the sample's noise, as the synthesis kernel added it
-        int32_t zi, zq;
+    int32_t zi = 0, zq = 0;
+    if (lead && c == 0 && ntab)                                       // the sample's noise, as the synthesis kernel added it
         noise::sample(ntab, nseed, nblock0 + p.block, p.sample, &zi, &zq);
-        i_acc += zi;
-        q_acc += zq;
+    if (lead && c == 0) {
+        uint8_t *blk_dst = dst + (size_t) (p.block - (uint32_t) block0) * block_stride;
+        if (lmult) store_level<FMT>(blk_dst, p.sample, i_acc, q_acc, zi, zq, lmult, lqmax);                // ... and the level stage
+        else store_sample<FMT>(blk_dst, p.sample, ((uint32_t) (i_acc + zi) & 0xffffu) | ((uint32_t) (q_acc + zq) << 16));
     }
-    if (lead && c == 0)
-        store_sample<FMT>(dst + (size_t) (p.block - (uint32_t) block0) * block_stride, p.sample,
-                          ((uint32_t) i_acc & 0xffffu) | ((uint32_t) q_acc << 16));
 }
 
 hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size, void *dst, size_t block_stride,
@@ -666,10 +699,10 @@ hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int s
     uint8_t *d = static_cast<uint8_t *>(dst);
     if (sample_size == GPSIQ_SC16)
         hipLaunchKernelGGL(apply_patches<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
-                           nz.tab, nz.seed, nz.block);
+                           nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
     else
         hipLaunchKernelGGL(apply_patches<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
-                           nz.tab, nz.seed, nz.block);
+                           nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
     return hipGetLastError();
 }
 
@@ -704,8 +737,8 @@ hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int
                           const noise::Launch &nz)
 {
     if (nblocks <= 0 || nsamp <= 0) return hipSuccess;
-    // receiver noise exists in the default kernels (seg, segh, generic) and tile; the host refuses the others first
-    if (nz.tab && variant != kTile && variant != kSeg && variant != kSegHalf && variant != kGeneric) return hipErrorInvalidValue;
+    // receiver noise and the output level exist in the default kernels (seg, segh, generic) and tile; the host refuses the others first
+    if ((nz.tab || nz.mult) && variant != kTile && variant != kSeg && variant != kSegHalf && variant != kGeneric) return hipErrorInvalidValue;
     uint8_t *d = static_cast<uint8_t *>(dst);
     // the mask kernel only has the plain-add LUT formats: int16 sums that may leave the int16 range go to seg's packed core
     if (variant == kSegMask && ((sample_size == GPSIQ_SC16 && max_amplitude > 32767) || !scratch)) variant = kSeg;
@@ -810,9 +843,12 @@ hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int
         dim3 grid((unsigned) (big_wgs + tiles1 * tail_blocks)), block(kRowsThreads);
         // no channel sum of any resident block can leave the int16 range: plain-add kernel
         // (the int8 kernels keep 12-bit fields and are exact for any gain)
-        // (with noise the bound is on |I + zI|: max_amplitude + max|z|)
-        const bool fast = (sample_size == GPSIQ_SC08 || max_amplitude + nz.max_z <= 32767) && seg_policy().allow_fast;
-#define GPSIQ_LAUNCH_T4(F, N, R, HH, FA) do { if (nz.tab) \
+        // (with noise the bound is on |I + zI|: max_amplitude + max|z|; with the output level the noise is added outside the packed
+        // word and both formats run the int16 cores: the bound is on the signal alone)
+        const bool fast = (nz.mult ? max_amplitude <= 32767 : sample_size == GPSIQ_SC08 || max_amplitude + nz.max_z <= 32767) && seg_policy().allow_fast;
+#define GPSIQ_LAUNCH_T4(F, N, R, HH, FA) do { if (nz.mult) \
+            hipLaunchKernelGGL((synth_tile_level<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1, nz.tab, nz.seed, nz.block, nz.mult, nz.qmax); \
+        else if (nz.tab) \
             hipLaunchKernelGGL((synth_tile_noise<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1, nz.tab, nz.seed, nz.block); \
         else hipLaunchKernelGGL((synth_tile<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1); } while (0)
 #define GPSIQ_LAUNCH_T(F, N) do { if (half) { if (fast) GPSIQ_LAUNCH_T4(F, N, 32, 2, true); else GPSIQ_LAUNCH_T4(F, N, 32, 2, false); } \
@@ -851,10 +887,10 @@ hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int
         dim3 grid((unsigned) (tiles * nblocks)), block(kGenericThreads);
         if (sample_size == GPSIQ_SC16)
             hipLaunchKernelGGL(synth_generic<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
-                               nz.tab, nz.seed, nz.block);
+                               nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
         else
             hipLaunchKernelGGL(synth_generic<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
-                               nz.tab, nz.seed, nz.block);
+                               nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
     }
     return hipGetLastError();
 }

@@ -8,6 +8,10 @@
 // z() is a 512-segment piecewise-linear inverse normal CDF with an exact 64-point tail (gpsiq_noise_knots.h), scaled to sigma.
 // On the device the scaled table is Entry[kEntries]: entries 0..510 are the segments (base S[k], slope S[k+1]-S[k]), entries
 // 511..574 the tail points (base S_tail[f], slope 0), so one 8-byte gather per component serves both cases.
+//
+// The output level stage (include/gpsiq_rows.h, "Output level") follows the noise and lives here with it: level::apply is the
+// contract's scale, round and clamp of one component, for the kernels that work sample by sample and as the statement the tile
+// body's own copy is held against.
 #ifndef GPSIQ_NOISE_H
 #define GPSIQ_NOISE_H
 
@@ -34,11 +38,14 @@ struct Entry {
 
 // what a launch needs: the scaled table on the device (nullptr: noise off), the seed, the absolute index of the descriptor
 // array's block 0, and max|z| (the int16 plain-add core needs every |I + zI| <= 32767)
+// With the output level on (mult != 0) tab is never null: an all-zero table stands in while the noise is off.
 struct Launch {
     const Entry *tab = nullptr;
     uint64_t     seed = 0;
     uint64_t     block = 0;
     long         max_z = 0;
+    uint32_t     mult = 0;     // output level: Q16 multiplier, 0 = off
+    int32_t      qmax = 0;     //               symmetric clamp
 };
 
 GPSIQ_NOISE_HD inline uint64_t splitmix64(uint64_t x)
@@ -97,5 +104,17 @@ GPSIQ_NOISE_HD inline void sample(const Entry *tab, uint64_t seed, uint64_t bloc
 }
 
 }  // namespace noise
+
+namespace level {
+
+// out = clamp(floor((A * mult + 32768) / 65536), -qmax, qmax); |A| < 2^19 and mult < 2^24, so the product needs 64 bits and the
+// quotient fits 32 (the shift of a negative int64_t is arithmetic: floor)
+GPSIQ_NOISE_HD inline int32_t apply(int32_t A, uint32_t mult, int32_t qmax)
+{
+    const int32_t y = (int32_t) (((int64_t) A * (int64_t) (int32_t) mult + 32768) >> 16);
+    return y < -qmax ? -qmax : y > qmax ? qmax : y;
+}
+
+}  // namespace level
 }  // namespace gpsiq
 #endif

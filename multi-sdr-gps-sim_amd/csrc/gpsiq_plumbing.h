@@ -22,7 +22,9 @@ void *gpsiq_plumbing(const char *name);
 /* Besides the functions declared below, gpsiq_plumbing() knows four names that are the library's internals as libgpsiq_rows.so (the
  * rows either side of the path: refresh, nav message, RINEX, motion -- include/gpsiq_rows.h, gpsiq_extras.h) needs them, so that the
  * two libraries share ONE worker pool, ONE quantiser and ONE error text per thread (csrc/gpsiq_rows_link.cpp is the other end):
- * "set_error", "parallel_for", "quantize_one", "chain_carrier" (csrc/gpsiq_internal.h has their C++ signatures). */
+ * "set_error", "parallel_for", "quantize_one", "chain_carrier" (csrc/gpsiq_internal.h has their C++ signatures).
+ * A fifth name, "set_level", is the implementation of gpsiq_set_level (include/gpsiq_rows.h, "Output level"), which libgpsiq_rows.so
+ * exports because this library is at its export limit: int (gpsiq_ctx_t *, const gpsiq_level_t *). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */

@@ -655,4 +655,19 @@ double gpsiq_noise_sigma_for_cn0(double cn0_dbhz, double gain, double fs)
     return 250.0 * std::fabs(gain) * std::sqrt(fs / (2.0 * std::pow(10.0, cn0_dbhz / 10.0)));
 }
 
+// per component: a channel of amplitude 250*gain has mean square (250*gain)^2 / 2 in I and in Q, the noise sigma^2
+double gpsiq_composite_rms(const double *gain, int nchan, double sigma)
+{
+    double p = sigma * sigma;
+    for (int c = 0; gain && c < nchan; ++c) p += (250.0 * gain[c]) * (250.0 * gain[c]) / 2.0;
+    return std::sqrt(p);
+}
+
+uint32_t gpsiq_level_mult(double rms_in, double rms_out)
+{
+    const double m = std::rint(65536.0 * rms_out / rms_in);
+    if (!(m >= 1.0)) return 1u;                            // also NaN (0/0) and a negative ratio
+    return m > 16777215.0 ? 16777215u : (uint32_t) m;
+}
+
 }  // extern "C"

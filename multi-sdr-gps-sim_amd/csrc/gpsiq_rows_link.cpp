@@ -51,3 +51,11 @@ void chain_carrier(gpsiq_qchan_t *q, int nblocks, int nchan, int nsamp, const bo
 }
 
 }  // namespace gpsiq
+
+// The output level is context state, which lives in libgpsiq.so; the typed call is exported here because the boundary library
+// is at its export limit (include/gpsiq_rows.h, "Output level").
+extern "C" __attribute__((visibility("default"))) int gpsiq_set_level(gpsiq_ctx_t *ctx, const gpsiq_level_t *lv)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_level_t *)>("set_level");
+    return f(ctx, lv);
+}

@@ -1,8 +1,14 @@
-// gpsiq_tile_body.inc -- the body of the tile kernels (gpsiq_kernels.hip: synth_tile and synth_tile_noise), included inside both.
+// gpsiq_tile_body.inc -- the body of the tile kernels (gpsiq_kernels.hip: synth_tile, synth_tile_noise and synth_tile_level), included
+// inside each.
 // Textual inclusion rather than a shared device function: inlining a function (its parameters, its early return) gives the
 // compiler another IR to schedule, and the noise-off kernels must stay the code they were.  In scope where it is included:
-// the kernel parameters, FMT NCH ROWS H FAST WAVES BOTH, and NOISE with ntab / nseed / nblock0 (the receiver noise).
+// the kernel parameters, FMT NCH ROWS H FAST WAVES BOTH, NOISE with ntab / nseed / nblock0 (the receiver noise), and LEVEL with
+// lmult / lqmax (the output level stage, include/gpsiq_rows.h; LEVEL kernels are NOISE kernels).
     constexpr int kLutEntries = BOTH ? 1024 : 512;
+    // the output level works on the whole 16-bit sums: both formats then accumulate with the int16 table layout (the int8 core's
+    // 12-bit fields hold the sums modulo 2^12 only)
+    constexpr int LFMT = LEVEL ? GPSIQ_SC16 : FMT;
+    static_assert(!LEVEL || (NOISE && !BOTH), "the level stage follows the noise in the noise kernels");
     constexpr int kThreads = WAVES * 64;
     __shared__ uint32_t lut[NCH][kLutEntries];
     __shared__ uint32_t ext[NCH][kPrnExtWords];
@@ -43,8 +49,8 @@
             const int ts = (int) (sk * g), tc = (int) (ck * g);   // gps.c:2781-2782
             // int8 output keeps bits 4..11 of each 16-bit sum (gps.c:2845): with the entries
             // pre-shifted by 4 (still modulo 2^16) those bits are bytes 1 and 3 of the packed sum
-            constexpr int kPre = FMT == GPSIQ_SC08 ? 4 : 0;
-            if (FAST && FMT == GPSIQ_SC08)
+            constexpr int kPre = LFMT == GPSIQ_SC08 ? 4 : 0;
+            if (FAST && LFMT == GPSIQ_SC08)
                 // the int8 output keeps bits 4..11 of I and Q only: 12-bit fields, I at bits 4..15 (its
                 // carries spill into bits 16..19, 16 channels x 12 bits), Q at bits 20..31; the output
                 // bytes are bytes 1 and 3 of the plain 32-bit sum, for any gain
@@ -133,6 +139,12 @@
     const uint32_t *w_row = &win[wave][H == 2 ? lane >> 5 : 0][0];   // upper half wave: second window of the row
     uint32_t *w_dst = &win[wave][wg][wc];
 
+    // the clamp's lower bound, once per wave in a vector register of its own (as the result of an asm statement it is kept, not
+    // formed again from the scalar register in every row).  The packed core has no register to spare for it (128 VGPRs: it would
+    // spill) and forms it per row.
+    [[maybe_unused]] int32_t l_neg = 0;
+    if constexpr (LEVEL && FAST) asm("v_mov_b32 %0, %1" : "=v"(l_neg) : "s"(-(int32_t) lqmax));
+
     auto row_body = [&](int r, uint32_t n_chunk, bool check) {
         uint32_t iq;                                             // (I & 0xffff) | Q << 16, what the int16 store keeps
         [[maybe_unused]] uint32_t zi = 0, zq = 0;                // noise of this lane's sample, mod 2^32
@@ -160,14 +172,14 @@
                 P[c] += dP[c];
                 Q[c] += dQ[c];
             }
-            if constexpr (NOISE) {
+            if constexpr (NOISE && !LEVEL) {
                 if (FMT == GPSIQ_SC08)
                     // a 17th term in the 12-bit fields: I's spill bits (16..19) are cleared first, so its carry stays out of Q
                     sum = (sum & ~0xf0000u) + ((zi & 0xfffu) << 4) + (zq << 20);
                 else
                     sum += zi + (zq << 16);                       // |I + zI| <= 32767 (the host's choice of core): no borrow into Q
             }
-            iq = FMT == GPSIQ_SC16 ? sum ^ 0x8000u : sum;         // take the bias off again: (I & 0xffff) | Q << 16
+            iq = LFMT == GPSIQ_SC16 ? sum ^ 0x8000u : sum;        // take the bias off again: (I & 0xffff) | Q << 16
         } else {
             s16x2 acc0 = (s16x2) (0), acc1 = (s16x2) (0);
 #pragma unroll
@@ -183,11 +195,31 @@
                 P[c] += dP[c];
                 Q[c] += dQ[c];
             }
-            if constexpr (NOISE) {
+            if constexpr (NOISE && !LEVEL) {
                 constexpr int kPre = FMT == GPSIQ_SC08 ? 4 : 0;  // the int8 entries are pre-shifted by 4, see the LUT build
                 acc0 = __builtin_bit_cast(s16x2, ((zi << kPre) & 0xffffu) | (zq << (16 + kPre))) + acc0;
             }
             iq = __builtin_bit_cast(uint32_t, acc0 + acc1);
+        }
+        if constexpr (LEVEL) {
+            // iq holds the noiseless sums as the int16 store would keep them.  Each comes out of the word sign-extended, the
+            // noise is added in 32 bits (nothing wraps), then scale, round, clamp: the product needs more than 32 bits
+            // (|A| < 2^19, mult < 2^24: v_mad_i64_i32), the quotient does not
+            const int32_t ai = (int32_t) (int16_t) iq + (int32_t) zi, aq = ((int32_t) iq >> 16) + (int32_t) zq;
+            const int32_t yi = (int32_t) (((int64_t) ai * (int64_t) (int32_t) lmult + 32768) >> 16);
+            const int32_t yq = (int32_t) (((int64_t) aq * (int64_t) (int32_t) lmult + 32768) >> 16);
+            // the clamp is one v_med3_i32 per component (written out: the compiler cannot know that -qmax <= qmax and emits
+            // min, compare and select; a VOP3 instruction reads one scalar register at most, so -qmax sits in a vector register)
+            uint32_t oi, oq;
+            if constexpr (!FAST) l_neg = -(int32_t) lqmax;
+            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oi) : "v"(yi), "v"(l_neg), "s"((int32_t) lqmax));
+            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oq) : "v"(yq), "v"(l_neg), "s"((int32_t) lqmax));
+            const uint32_t n = n_chunk + (uint32_t) lane + (uint32_t) r * 64u;
+            if (!check || n < (uint32_t) nsamp) {
+                if (FMT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(blk_dst + n * 4u) = (oi & 0xffffu) | (oq << 16);
+                else *reinterpret_cast<uint16_t *>(blk_dst + n * 2u) = (uint16_t) ((oi & 0xffu) | (oq << 8));
+            }
+            return;
         }
         const uint32_t n = n_chunk + (uint32_t) lane + (uint32_t) r * 64u;
         if (!check || n < (uint32_t) nsamp) {

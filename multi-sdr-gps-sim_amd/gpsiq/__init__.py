@@ -148,11 +148,19 @@ _set_noise = _sig("gpsiq_set_noise", _i, _vp, _vp)
 _noise_state = _sig("gpsiq_noise_state", _i, _vp, _vp)
 _noise_host = _sig("gpsiq_noise_host", _i, C.c_uint64, _d, C.c_uint64, _i, _vp)
 _noise_sigma_for_cn0 = _sig("gpsiq_noise_sigma_for_cn0", _d, _d, _d, _d)
+_set_level = _sig("gpsiq_set_level", _i, _vp, _vp)
+_composite_rms = _sig("gpsiq_composite_rms", _d, _vp, _i, _d)
+_level_mult = _sig("gpsiq_level_mult", C.c_uint32, _d, _d)
 
 
 class NoiseSettings(C.Structure):
     """gpsiq_noise_t (include/gpsiq.h)."""
     _fields_ = [("seed", C.c_uint64), ("sigma", C.c_double), ("next_block", C.c_uint64)]
+
+
+class LevelSettings(C.Structure):
+    """gpsiq_level_t (include/gpsiq_rows.h)."""
+    _fields_ = [("mult", C.c_uint32), ("qmax", C.c_int32)]
 
 
 def _check(rc):
@@ -598,6 +606,17 @@ def noise_sigma_for_cn0(cn0_dbhz, gain=1.0, fs=2.6e6):
     return _noise_sigma_for_cn0(float(cn0_dbhz), float(gain), float(fs))
 
 
+def composite_rms(gains, sigma=0.0):
+    """Rms per component (I or Q) of channels with these gains plus noise of this sigma, in accumulator units."""
+    g = np.ascontiguousarray(gains, dtype=np.float64).ravel()
+    return _composite_rms(_p(g) if g.size else None, int(g.size), float(sigma))
+
+
+def level_mult(rms_in, rms_out):
+    """The Q16 multiplier of Context.set_level that takes rms_in to rms_out (include/gpsiq_rows.h, "Output level")."""
+    return int(_level_mult(float(rms_in), float(rms_out)))
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -662,6 +681,15 @@ class Context:
         st = NoiseSettings()
         _check(_noise_state(self._h, C.byref(st)))
         return st.seed, st.sigma, st.next_block
+
+    def set_level(self, mult, qmax):
+        """Output level stage: out = clamp(floor((S + z) * mult / 65536 + 1/2), -qmax, qmax) in the kernels, in place of the
+        wrapping store (include/gpsiq_rows.h, "Output level"); level_off() restores it."""
+        st = LevelSettings(int(mult), int(qmax))
+        _check(_set_level(self._h, C.byref(st)))
+
+    def level_off(self):
+        _check(_set_level(self._h, None))
 
     def set_patches(self, patches):
         patches = np.ascontiguousarray(patches, dtype=PATCH_DTYPE)

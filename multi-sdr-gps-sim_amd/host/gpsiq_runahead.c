@@ -29,6 +29,10 @@
  * the reference's --disable-almanac.
  * Receiver noise (optional, after the positional arguments): --cn0 <dB-Hz> puts a channel of gain 1.0 at that C/N0
  * (gpsiq_noise_sigma_for_cn0, gpsiq_set_noise), --seed <n> seeds it (default 0).  Without --cn0 the file is noiseless.
+ * Output level (optional, same place): --level <rms> scales the stream so that the composite of the first block's channels and the
+ * noise has that rms per component, in output steps, and saturates instead of wrapping; --qmax <n> is the clamp (default: full scale
+ * of the format, 127 or 32767).  The multiplier is fixed for the run from the first block (gpsiq_composite_rms, gpsiq_level_mult,
+ * gpsiq_set_level), so the file stays a function of the arguments alone.  Without --level the stream is the reference's.
  */
 #include <math.h>
 #include <stdint.h>
@@ -130,14 +134,19 @@ static int refresh_ephemeris(struct host_state *h, double t)
 int main(int argc, char **argv)
 {
     double cn0 = NAN;
+    double level_rms = NAN;
+    int qmax = 0;
     uint64_t noise_seed = 0;
-    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0)) {   /* trailing flags */
+    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 ||
+                        strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0)) {       /* trailing flags */
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
+        else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
+        else if (strcmp(argv[argc - 2], "--qmax") == 0) qmax = atoi(argv[argc - 1]);
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
     if (argc != 11 && argc != 12) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n]\n", argv[0]);
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n]\n", argv[0]);
         return 2;
     }
     const int version = atoi(argv[2]), nchan = atoi(argv[7]), ss = atoi(argv[9]);
@@ -203,10 +212,14 @@ int main(int argc, char **argv)
         const char *m = getenv("GPSIQ_NCO");
         if (m && strcmp(m, "reference") == 0 && gpsiq_set_nco_mode(gq, GPSIQ_NCO_REFERENCE) != GPSIQ_OK) return die("nco mode");
     }
+    const double sigma = isnan(cn0) ? 0.0 : gpsiq_noise_sigma_for_cn0(cn0, 1.0, fs);
     if (!isnan(cn0)) {
-        const gpsiq_noise_t nz = {noise_seed, gpsiq_noise_sigma_for_cn0(cn0, 1.0, fs), 0};
+        const gpsiq_noise_t nz = {noise_seed, sigma, 0};
         if (gpsiq_set_noise(gq, &nz) != GPSIQ_OK) return die("noise");
     }
+    if (!isnan(level_rms) && !(level_rms > 0.0)) { fprintf(stderr, "bad --level\n"); return 2; }
+    if (qmax && isnan(level_rms)) { fprintf(stderr, "--qmax needs --level\n"); return 2; }
+    int level_set = isnan(level_rms);                                          /* nothing to set without --level */
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) ss;
     void *buf = gpsiq_host_alloc(blk_bytes * BLOCKS_PER_CALL);
     gpsiq_chan_t *desc = malloc(sizeof *desc * BLOCKS_PER_CALL * (size_t) nchan);
@@ -232,6 +245,15 @@ int main(int argc, char **argv)
             for (int k = 0; k < nb; ++k)
                 for (int i = 0; i < nchan; ++i)
                     desc[(size_t) k * nchan + i].carr_phase = (have_carr && k == 0 && carr[i] >= 0.0) ? carr[i] : h.trk[i].carr_phase;
+            if (!level_set) {                                                  /* once, from the run's first block */
+                double gain[GPSIQ_MAX_CHAN];
+                int ng = 0;
+                for (int i = 0; i < nchan; ++i)
+                    if (desc[i].prn > 0) gain[ng++] = desc[i].gain;
+                const gpsiq_level_t lv = {gpsiq_level_mult(gpsiq_composite_rms(gain, ng, sigma), level_rms), qmax ? qmax : ss == 1 ? 127 : 32767};
+                if (gpsiq_set_level(gq, &lv) != GPSIQ_OK) return die("level");
+                level_set = 1;
+            }
             if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
             if (fwrite(buf, blk_bytes, (size_t) nb, fo) != (size_t) nb) { fprintf(stderr, "short write\n"); return 1; }

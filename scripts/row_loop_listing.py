@@ -5,7 +5,16 @@ llvm-objdump -d on them, finds synth_tile<1, 16, 64, 1, true, 8, false> (int8) a
 the innermost loop that holds the per-channel core (the ds_read_b32 gathers): every instruction with the issue cost of its
 encoding class as measured on this chip (profiles/r01_ubench_valu_encodings.txt), and the totals the roofline discussion in
 DESIGN.md section 4 quotes (VALU per 16-channel row, LDS gathers, issue cycles).  No GPU needed.
-usage: python scripts/row_loop_listing.py [tag]"""
+A second argument is a regular expression that selects other kernels by their demangled name, e.g. the headline kernels of the
+noise and the output level: 'synth_tile_(noise|level)<[12], 16, 64, 1, true>'.
+usage: python scripts/row_loop_listing.py [tag [kernel-regex]]
+
+--hashes: one line per kernel whose demangled name matches the regex (default: every synth_tile / synth_tile_noise instantiation),
+with the SHA-256 prefix of its instruction stream (llvm-objdump -d, addresses and comments stripped).  With a second library the
+two are compared kernel by kernel: how a change is shown to have left existing kernels as they were (build the commit before
+with `make -C multi-sdr-gps-sim_amd/csrc OUT=<elsewhere>/libgpsiq.so` and pass that file).
+usage: python scripts/row_loop_listing.py --hashes [--regex R] [library [library-before]]"""
+import hashlib
 import collections
 import os
 import re
@@ -33,8 +42,8 @@ def issue_cycles(op, text):
     return 2.5
 
 
-def code_objects():
-    blob = open(LIB, "rb").read()
+def code_objects(lib=None):
+    blob = open(lib or LIB, "rb").read()
     out = []
     for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob):
         base = m.start()
@@ -51,6 +60,7 @@ def code_objects():
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r05"
+    pattern = sys.argv[2] if len(sys.argv) > 2 else r"synth_tile<[12], 16, 64, 1, true, 8, false>"
     dst = os.path.join(ROOT, "profiles", f"{tag}_synth_tile_row_loop.txt")
     lines_out = []
     with tempfile.TemporaryDirectory() as td:
@@ -65,7 +75,7 @@ def main():
                 if not m:
                     continue
                 name = subprocess.run([CXXFILT, m.group(1)], capture_output=True, text=True).stdout.strip()
-                if not re.search(r"synth_tile<[12], 16, 64, 1, true, 8, false>", name):
+                if not re.search(pattern, name):
                     continue
                 body = [ln.strip() for ln in f.split("\n")[1:] if ln.strip()]
                 ins = []
@@ -117,6 +127,48 @@ def main():
             print(ln)
 
 
+def kernel_hashes(lib, pattern):
+    """{demangled kernel name (without the parameter list): hash of its instructions}"""
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for k, co in enumerate(code_objects(lib)):
+            path = os.path.join(td, f"co{k}.o")
+            open(path, "wb").write(co)
+            dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", path], capture_output=True, text=True).stdout
+            funcs = {}
+            for f in re.split(r"\n(?=[0-9a-f]+ <[^>]+>:\n)", dis):
+                m = re.match(r"[0-9a-f]+ <([^>]+)>:", f.split("\n", 1)[0])
+                if m:
+                    funcs[m.group(1)] = [t for t in (ln.split("//")[0].strip() for ln in f.split("\n")[1:]) if t]
+            names = list(funcs)
+            dem = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+            for n, d in zip(names, dem):
+                if re.search(pattern, d):
+                    out[d.split("(")[0]] = (hashlib.sha256("\n".join(funcs[n]).encode()).hexdigest()[:16], len(funcs[n]))
+    return out
+
+
+def hashes_main(argv):
+    pattern = r"synth_tile(_noise)?<"
+    if argv[:1] == ["--regex"]:
+        pattern, argv = argv[1], argv[2:]
+    now = kernel_hashes(argv[0] if argv else LIB, pattern)
+    before = kernel_hashes(argv[1], pattern) if len(argv) > 1 else None
+    same = 0
+    for name in sorted(set(now) | set(before or {})):
+        h, n = now.get(name, ("-", 0))
+        if before is None:
+            print(f"{h} {n:5d}  {name}")
+            continue
+        hb, nb = before.get(name, ("-", 0))
+        same += h == hb
+        print(f"{h} {n:5d}  {hb} {nb:5d}  {'same' if h == hb else 'DIFFERENT'}  {name}")
+    if before is not None:
+        print(f"# {same} of {len(set(now) | set(before))} kernels matching {pattern!r} have the same instructions in both libraries")
+        return 0 if same == len(set(now) | set(before)) else 1
+    return 0
+
+
 def kernels_id():
     sys.path.insert(0, os.path.join(ROOT, "multi-sdr-gps-sim_amd"))
     import gpsiq
@@ -124,4 +176,6 @@ def kernels_id():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--hashes"]:
+        sys.exit(hashes_main(sys.argv[2:]))
     main()
