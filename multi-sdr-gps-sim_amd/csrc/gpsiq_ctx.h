@@ -50,9 +50,7 @@ struct gpsiq_ctx {
     int            cur = 0;             // buf[cur] holds the resident set
     gpsiq_qchan_t *d_desc = nullptr;    // == buf[cur].d
     int            nblocks = 0, nchan = 0;
-    uint64_t       max_code_step = 0;
-    int            max_active = 0;      // most active channels in any resident block
-    long           max_amplitude = 0;   // largest sum over a block's channels of (int)(250*|gain|): bound on |I|, |Q|
+    gpsiq::SynthClass cls;              // what the resident set contributes to the choice of kernel (gpsiq_launch_plan.h)
     int            nco_mode = GPSIQ_NCO_FIXED;
     // receiver noise (gpsiq_set_noise): on while sigma > 0; next_block is the absolute index the next drop-in call's block 0
     // gets, call_block that of the running call's block 0 (every path of the call numbers its blocks from it)
@@ -200,11 +198,37 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
 void gpsiq_evaldev_destroy(gpsiq_ctx *c);
 
 namespace gpsiq {
+// The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
+// nullptr where there is none).  Common head: descriptors, nchan, nsamp, dst, block stride, block0, tables.
+using TileFn      = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int);
+using TileNoiseFn = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int,
+                             const noise::Entry *, uint64_t, uint64_t);
+using TileLevelFn = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int,
+                             const noise::Entry *, uint64_t, uint64_t, uint32_t, int32_t);
+using MaskFn      = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, const uint64_t *, int, int, int);
+using SignMasksFn = void (*)(const gpsiq_qchan_t *, int, int, int, int, const DeviceTables *, uint64_t *, int, int);
+using RowsFn      = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, int);
+using GenericFn   = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, const DeviceTables *, int, int,
+                             const noise::Entry *, uint64_t, uint64_t, uint32_t, int32_t);
+using PatchFn     = void (*)(const gpsiq_qchan_t *, int, int, uint8_t *, size_t, int, int, const DeviceTables *, const gpsiq_patch_t *, int,
+                             const noise::Entry *, uint64_t, uint64_t, uint32_t, int32_t);
+TileFn      tile_kernel(int fmt, int slots, bool half, bool fast);          // tile, seg (half = false), segh
+TileNoiseFn tile_noise_kernel(int fmt, int slots, bool half, bool fast);
+TileLevelFn tile_level_kernel(int fmt, int slots, bool half, bool fast);
+TileFn      both_kernel(int fmt, int slots);                                // segb
+MaskFn      mask_kernel(int fmt, int slots);                                // segm, behind sign_masks_kernel()
+SignMasksFn sign_masks_kernel();
+RowsFn      rowsx_kernel(int fmt, int slots);
+RowsFn      rows_kernel(int fmt);
+GenericFn   generic_kernel(int fmt);
+PatchFn     patch_kernel(int fmt);
+
+// gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
+// of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)
 hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size,
                           void *dst, size_t block_stride, int block0, int nblocks,
-                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch,
+                          const DeviceTables *tab, hipStream_t stream, const SynthClass &cls, void *scratch,
                           const noise::Launch &nz);
-size_t variant_scratch_bytes(int variant, int nsamp, int nblocks);
 hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size, void *dst, size_t block_stride,
                           int block0, int nblocks, const DeviceTables *tab, const gpsiq_patch_t *patches, int npatch,
                           hipStream_t stream, const noise::Launch &nz);

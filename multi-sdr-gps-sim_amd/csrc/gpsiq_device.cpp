@@ -82,14 +82,7 @@ static int check_level(const gpsiq_ctx *c, int sample_size)
     return GPSIQ_OK;
 }
 
-static bool noise_variant_ok(int v) { return v == kAuto || v == kGeneric || v == kTile || v == kSeg || v == kSegHalf; }
-
-static int pick_variant(const gpsiq_ctx *c, int variant)
-{
-    if (variant == kAuto)
-        return c->max_code_step <= kRowsMaxCodeStep ? kSeg : c->max_code_step <= kHalfRowsMaxCodeStep ? kSegHalf : kGeneric;
-    return variant;
-}
+static int pick_variant(const gpsiq_ctx *c, int variant) { return variant == kAuto ? auto_variant(c->cls.max_code_step) : variant; }
 
 static int check_launch(const gpsiq_ctx *c, int block0, int nblocks, int nsamp, int sample_size,
                         const void *dst, size_t stride, int variant)
@@ -104,14 +97,15 @@ static int check_launch(const gpsiq_ctx *c, int block0, int nblocks, int nsamp, 
     if (stride < (size_t) 2 * (size_t) nsamp * (size_t) sample_size || (stride & 3))
         return fail(GPSIQ_E_ARG, "block stride %zu too small or not a multiple of 4", stride);
     if (variant < 0 || variant >= kNumVariants) return fail(GPSIQ_E_ARG, "unknown variant %d", variant);
-    if (c->noise.sigma > 0.0 && !noise_variant_ok(variant))
+    const bool stages_ok = variant == kAuto || has_noise_path(variant);      // kAuto picks among kernels that have one
+    if (c->noise.sigma > 0.0 && !stages_ok)
         return fail(GPSIQ_E_STATE, "variant %d has no receiver-noise path: turn noise off (gpsiq_set_noise) or use 0/generic/tile/seg/segh", variant);
-    if (c->level.mult && !noise_variant_ok(variant))
+    if (c->level.mult && !stages_ok)
         return fail(GPSIQ_E_STATE, "variant %d has no output-level path: turn the level off (gpsiq_set_level) or use 0/generic/tile/seg/segh", variant);
     if (int rc = check_level(c, sample_size)) return rc;
-    if (variant == kSegHalf && c->max_code_step > kHalfRowsMaxCodeStep)
+    if (variant == kSegHalf && c->cls.max_code_step > kHalfRowsMaxCodeStep)
         return fail(GPSIQ_E_RANGE, "half-row kernel needs f_code/fs <= 1 chip per sample");
-    if (variant >= kRows && variant != kSegHalf && c->max_code_step > kRowsMaxCodeStep)
+    if (variant >= kRows && variant != kSegHalf && c->cls.max_code_step > kRowsMaxCodeStep)
         return fail(GPSIQ_E_RANGE, "row kernel needs f_code/fs <= 31/63 chip per sample");
     return GPSIQ_OK;
 }
@@ -342,7 +336,7 @@ static int set_descriptors_impl(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblo
     }
     c->cur = next;
     c->d_desc = nb.d;
-    c->nblocks = nblocks; c->nchan = nchan; c->max_code_step = pj.mx; c->max_active = pj.max_active; c->max_amplitude = pj.max_amp;
+    c->nblocks = nblocks; c->nchan = nchan; c->cls = {pj.mx, pj.max_active, pj.max_amp};
     nb.npatch = n ? npatch : 0;
     return GPSIQ_OK;
 }
@@ -404,7 +398,7 @@ static int launch_on(gpsiq_ctx *c, int v, int block0, int nblocks, int nsamp, in
     }
     if (c->buf[c->cur].upload_pending) HIP_TRY(hipStreamWaitEvent(s, c->buf[c->cur].uploaded, 0));    // a set staged without waiting
     hipError_t e = launch_variant(v, c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, s,
-                                  c->max_active, c->max_amplitude, need ? c->d_scratch : nullptr, nz);
+                                  c->cls, need ? c->d_scratch : nullptr, nz);
     if (e == hipSuccess && c->buf[c->cur].npatch)
         e = launch_patches(c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, c->buf[c->cur].d_patch,
                            c->buf[c->cur].npatch, s, nz);
@@ -468,21 +462,7 @@ int gpsiq_time_launches(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int 
 
 int gpsiq_num_variants(void) { return kNumVariants; }
 
-const char *gpsiq_variant_name(int v)
-{
-    switch (v) {
-    case kAuto: return "auto";
-    case kGeneric: return "generic";
-    case kRows: return "rows";
-    case kRowsX: return "rowsx";
-    case kTile: return "tile";
-    case kSeg: return "seg";
-    case kSegHalf: return "segh";
-    case kSegMask: return "segm";
-    case kSegBoth: return "segb";
-    default: return "?";
-    }
-}
+const char *gpsiq_variant_name(int v) { return variant_name(v); }
 
 // ---- the output of a batch call (PieceOut, gpsiq_ctx.h) ----------------------------------------------------------------------
 
@@ -960,13 +940,12 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
     if (!a.done) HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
     // compact (active channels first) and take the launch parameters, as gpsiq_set_descriptors does for a batch
     int na = 0;
-    long amp = 0;
-    uint64_t max_step = 0;
+    SynthClass cls;
     for (int i = 0; i < nchan; ++i) {
         if (!q[i].prn) continue;
         if (!(q[i].gain > -kMaxGain && q[i].gain < kMaxGain)) return fail(GPSIQ_E_RANGE, "gain %g outside the NCO format", q[i].gain);
-        if (q[i].code_step > max_step) max_step = q[i].code_step;
-        amp += (long) (250.0 * std::fabs(q[i].gain));
+        if (q[i].code_step > cls.max_code_step) cls.max_code_step = q[i].code_step;
+        cls.max_amplitude += (long) (250.0 * std::fabs(q[i].gain));
         a.h[na++] = q[i];
     }
     for (int i = na; i < nchan; ++i) std::memset(&a.h[i], 0, sizeof(gpsiq_qchan_t));
@@ -989,12 +968,12 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
         a.patch_cap = cap;
     }
     if (nsamp > 0) {
-        const int v = max_step <= kRowsMaxCodeStep ? kSeg : max_step <= kHalfRowsMaxCodeStep ? kSegHalf : kGeneric;
+        cls.max_active = na;
         // once the first copy is queued a failure must not return with work in flight on the slot's page-locked staging (the next
         // call would rewrite it under the copy): the stream is drained first
         hipError_t e = hipMemcpyAsync(a.d, a.h, (size_t) nchan * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, c->stream);
         const gpsiq::noise::Launch nz = gpsiq_noise_at(c, c->noise.next_block);
-        if (e == hipSuccess) e = launch_variant(v, a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, c->stream, na, amp, nullptr, nz);
+        if (e == hipSuccess) e = launch_variant(auto_variant(cls.max_code_step), a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, c->stream, cls, nullptr, nz);
         if (e == hipSuccess && !patches.empty()) {
             std::memcpy(a.h_patch, patches.data(), patches.size() * sizeof(gpsiq_patch_t));
             e = hipMemcpyAsync(a.d_patch, a.h_patch, patches.size() * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);

@@ -325,9 +325,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     PackJob pj = {ch, h_chan, nullptr, nchan, delt, 0, 0, 0};
     hipError_t he = hipSuccess;
     char err[400] = "";
-    int max_active = 0;
-    long max_amp = 0;
-    uint64_t max_step = 0;
+    SynthClass cls;                                         // of the pieces staged so far
     double t_first_launch = 0.0;
     int timed_blocks = 0;
     hipEvent_t *staged = e.evaluated;                       // [k]: piece k's descriptors are in the set (and a snapshot of the control block behind them)
@@ -361,18 +359,17 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
         // the launch parameters of the synthesis kernel: from the pool's pack at once, from the device's pack behind the event
         if (he == hipSuccess && kind != kSrcPageable) he = hipEventSynchronize(staged[k]);
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d: %s", k, hipGetErrorString(he)); break; }
-        if (kind == kSrcPageable) { max_step = pj.mx; max_active = pj.max_active; max_amp = pj.max_amp; }
+        if (kind == kSrcPageable) cls = {pj.mx, std::max(pj.max_active, 1), pj.max_amp};
         else {
             const EvalCtrl &ck = e.h_ctrl[k];
-            max_step = std::max<uint64_t>(max_step, ck.max_code_step); max_active = std::max(max_active, ck.max_active); max_amp = std::max<long>(max_amp, (long) ck.max_amp);
+            cls = {std::max<uint64_t>(cls.max_code_step, ck.max_code_step), std::max({cls.max_active, ck.max_active, 1}), std::max<long>(cls.max_amplitude, (long) ck.max_amp)};
         }
         hipStream_t s = gpsiq_piece_stream(c, k);
         he = hipStreamWaitEvent(s, staged[k], 0);
         if (he == hipSuccess) {
-            const int v = max_step <= kRowsMaxCodeStep ? kSeg : max_step <= kHalfRowsMaxCodeStep ? kSegHalf : kGeneric;
             // the last piece's synthesis is timed: the rate the piece sizes are planned with is a measured one (gpsiq_note_kernel_rate)
             if (k == npieces - 1) (void) hipEventRecord(e.t_synth0, s);
-            he = launch_variant(v, nb_.d, nchan, nsamp, sample_size, out.target(b0), out.stride, b0, nb, c->d_tab, s, max_active > 0 ? max_active : 1, max_amp, nullptr,
+            he = launch_variant(auto_variant(cls.max_code_step), nb_.d, nchan, nsamp, sample_size, out.target(b0), out.stride, b0, nb, c->d_tab, s, cls, nullptr,
                                 gpsiq_noise_at(c, c->call_block));
             if (k == npieces - 1) { (void) hipEventRecord(e.t_synth1, s); timed_blocks = nb; }
             if (trace && k == 0) t_first_launch = gpsiq_wall_ms() - t0;
@@ -663,7 +660,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     // ---- the resident set and the carried state ------------------------------------------------------------------------------
     c->cur = next;
     c->d_desc = nb_.d;
-    c->nblocks = nblocks; c->nchan = nchan; c->max_code_step = max_step; c->max_active = max_active > 0 ? max_active : 1; c->max_amplitude = max_amp;
+    c->nblocks = nblocks; c->nchan = nchan; c->cls = cls;
     nb_.npatch = (int) npatch_total;
     nb_.active_per_block.assign((size_t) nblocks, (uint8_t) nchan);
     nb_.upload_pending = false;

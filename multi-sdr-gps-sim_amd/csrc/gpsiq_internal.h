@@ -6,6 +6,7 @@
 #include "../../include/gpsiq_extras.h"      // gpsiq.h (the boundary) + gpsiq_rows.h (section 8f rows) + the frozen convenience set
 #include "gpsiq_plumbing.h"                  // the library's own plumbing (hidden symbols, reached through gpsiq_plumbing())
 #include "gpsiq_tables.h"
+#include "gpsiq_launch_plan.h"                // the kernel variants and the launch planner
 
 #include <pthread.h>
 #include <atomic>
@@ -119,27 +120,6 @@ void parallel_for(int n, int nthreads, int grain, void (*fn)(void *ctx, int begi
 // |gain| bound of every entry point that takes a gain: (int)(250*|gain|) of 16 channels must fit the 32-bit sums with
 // room to spare, and the LUT build converts table*gain to int.  (The reference's gains are below 2.)
 constexpr double kMaxGain = 4.0e6;
-
-// Kernel variants (gpsiq_launch's `variant`).
-enum Variant {
-    kAuto = 0,      // fast when every resident descriptor allows it, else generic
-    kGeneric = 1,   // one sample per thread, full-width closed form per sample (any rate)
-    kRows = 2,      // 64-sample rows per wave, incremental NCOs, LDS-staged windows
-    kRowsX = 3,     // same rows, channel-inner loop order with all NCO state in registers
-    kTile = 4,      // rowsx with trimmed per-tile overhead, 64 rows per wave (32768-sample tiles)
-    kSeg = 5,       // tile kernel, each wave running several consecutive 64-row chunks
-    kSegHalf = 6,   // seg with one window per 32 samples: for sample rates down to 1.023 Msps
-    kSegMask = 7,   // high sample rates: per-(channel,row) 64-bit sign masks from a pre-pass, applied as EXEC masks
-    kSegBoth = 8,   // seg's plain-add core with a both-polarity LUT (sign concatenated above the index), 16-wave workgroups
-    kNumVariants
-};
-
-// The row kernel needs all 64 lanes of a row inside one 32-chip window:
-// 63*code_step + (1 chip) <= 32 chips.
-constexpr uint64_t kRowsMaxCodeStep = ((UINT64_C(31) << GPSIQ_CODE_FRAC_BITS) - 1) / 63;
-// With a window per half row (32 lanes): 31*code_step + (1 chip) <= 32 chips, i.e. up to one
-// chip per sample (fs >= 1.023 Msps).
-constexpr uint64_t kHalfRowsMaxCodeStep = ((UINT64_C(31) << GPSIQ_CODE_FRAC_BITS) - 1) / 31;
 
 }  // namespace gpsiq
 #endif

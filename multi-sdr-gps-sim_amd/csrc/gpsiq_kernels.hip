@@ -11,9 +11,11 @@
 //   * nothing is read from HBM per sample: the only traffic is the IQ write.
 // No MFMA: there is no contraction in this path; it is integer VALU + LDS gather.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 
-#include "gpsiq_internal.h"
+#include <array>
+
+#include "gpsiq_ctx.h"
+#include "gpsiq_geometry.h"
 #include "gpsiq_noise.h"
 
 namespace gpsiq {
@@ -89,8 +91,6 @@ __device__ __forceinline__ void store_level(uint8_t *__restrict__ blk_dst, uint3
 // evaluated at full width for that sample.  Works for any rate the descriptor format
 // allows; it is the fallback for sample rates too low for the row kernel, and an
 // independent second implementation the tests cross-check the row kernel against.
-constexpr int kGenericThreads = 256;
-
 template <int FMT>
 __global__ __launch_bounds__(kGenericThreads) void synth_generic(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, uint8_t *__restrict__ dst,
@@ -163,10 +163,7 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
 // (64x32-bit products, wrapping mod 2^64 = mod 32 cycles / mod 256 chips).
 // Code phase word: [chips mod 256 : 8][fraction : 56]; carrier word: [5 don't-care]
 // [LUT index : 9][fraction : 50].
-constexpr int kWaves = 8;
-constexpr int kRowsPerWave = 32;
-constexpr int kRowsThreads = kWaves * 64;
-constexpr int kRowsTile = kWaves * kRowsPerWave * 64;   // 16384 samples
+// (kWaves, kRowsPerWave and what follows from them: gpsiq_geometry.h)
 constexpr int kWinRowsPerLane = kRowsPerWave * kMaxChan / 64;   // rows one lane prepares
 
 template <int FMT>
@@ -503,9 +500,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void synth_tile_level(
 // LUT in LDS.  The arithmetic is the closed form of include/gpsiq.h, evaluated exactly:
 //   sample pos of the chip edge e of a row: smallest pos with  f0 + pos*cs >= e*2^56  (f0: code fraction at the
 //   row start), walked with  2^56 = q*cs + r:  the next edge is q or q+1 samples on, by the remainder.
-constexpr int kMaskRowsPerThread = 16;      // consecutive rows one pre-pass thread walks (one division per 1024 samples)
-
-__global__ __launch_bounds__(256) void sign_masks(
+__global__ __launch_bounds__(kMaskThreads) void sign_masks(
     const gpsiq_qchan_t *__restrict__ desc, int nchan, int nsamp, int block0, int nblocks,
     const DeviceTables *__restrict__ tab, uint64_t *__restrict__ masks, int rows_total, int rowgroups)
 {
@@ -629,12 +624,6 @@ __global__ __launch_bounds__(kRowsThreads) void synth_mask(
     }
 }
 
-size_t variant_scratch_bytes(int variant, int nsamp, int nblocks)
-{
-    if (variant != kSegMask || nsamp <= 0 || nblocks <= 0) return 0;
-    return (size_t) nblocks * (size_t) ((nsamp + 63) / 64) * 16u * sizeof(uint64_t);
-}
-
 // ---------------------------------------------------------------------------
 // GPSIQ_NCO_REFERENCE fix-up (csrc/gpsiq_exact.cpp): the few samples per 10^7 where the reference's
 // double accumulators pick another LUT entry or sign than the closed form are recomputed whole --
@@ -690,209 +679,67 @@ __global__ __launch_bounds__(64) void apply_patches(
     }
 }
 
-hipError_t launch_patches(const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size, void *dst, size_t block_stride,
-                          int block0, int nblocks, const DeviceTables *tab, const gpsiq_patch_t *patches, int npatch,
-                          hipStream_t stream, const noise::Launch &nz)
-{
-    if (npatch <= 0 || nblocks <= 0 || nsamp <= 0) return hipSuccess;
-    dim3 grid((unsigned) ((npatch + 3) / 4)), block(64);
-    uint8_t *d = static_cast<uint8_t *>(dst);
-    if (sample_size == GPSIQ_SC16)
-        hipLaunchKernelGGL(apply_patches<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
-                           nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
-    else
-        hipLaunchKernelGGL(apply_patches<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, nblocks, tab, patches, npatch,
-                           nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------
-// Grid-shape policy of the seg variants; the defaults can be overridden for experiments with
-// GPSIQ_SEG_TAIL_WGS / GPSIQ_SEG_MAX_WAVE_ROWS / GPSIQ_SEG_SETUP_ROWS / GPSIQ_SEG_DRAIN (read once).
-struct SegPolicy {
-    int    tail_wgs;        // one-chunk workgroups at the end of the grid
-    int    max_wave_rows;   // longest run of rows a wave may own
-    double setup_rows;      // per-workgroup set-up, in row-times (measured: tile vs seg = 4 %)
-    double drain_rounds;    // time lost while the grid drains, in workgroup durations
-    double resident_wgs;    // 256 CUs x 2 workgroups (67 KB LDS each)
-    bool   allow_fast;      // GPSIQ_NO_FAST=1 forces the packed-multiply kernels (A/B experiments, tests)
-};
-static const SegPolicy &seg_policy()
+// The kernels that exist, as data: what the launcher (gpsiq_launch.cpp) looks up with the run-time values of a plan
+// (gpsiq_launch_plan.h).  Every instantiation of the library is named here and nowhere else; nullptr: no such kernel.
+template <int... N> struct Ints {};
+using Slots = Ints<4, 8, 12, 16>;       // channel slots of the tile, mask and both-polarity kernels
+using SlotsX = Ints<4, 8, 16>;          // ... of synth_rowsx
+
+template <int... N> constexpr int index_of(Ints<N...>, int n)
 {
-    static const SegPolicy pol = [] {
-        SegPolicy p = {512, 512, 3.5, 0.3, 512.0, true};
-        if (const char *e = std::getenv("GPSIQ_SEG_TAIL_WGS")) p.tail_wgs = std::atoi(e);
-        if (const char *e = std::getenv("GPSIQ_SEG_MAX_WAVE_ROWS")) p.max_wave_rows = std::atoi(e);
-        if (const char *e = std::getenv("GPSIQ_SEG_SETUP_ROWS")) p.setup_rows = std::atof(e);
-        if (const char *e = std::getenv("GPSIQ_SEG_DRAIN")) p.drain_rounds = std::atof(e);
-        if (const char *e = std::getenv("GPSIQ_NO_FAST")) p.allow_fast = std::atoi(e) == 0;
-        return p;
-    }();
-    return pol;
+    int at = -1, i = 0;
+    ((at = N == n ? i : at, ++i), ...);
+    return at;
+}
+// the table of format `fmt` out of (int8, int16); its entry `i`, nullptr when i < 0
+template <class T> static auto pick(const T &t08, const T &t16, int fmt, int i) -> typename T::value_type
+{
+    return i < 0 || (fmt != GPSIQ_SC08 && fmt != GPSIQ_SC16) ? nullptr : (fmt == GPSIQ_SC16 ? t16 : t08)[(size_t) i];
 }
 
-hipError_t launch_variant(int variant, const gpsiq_qchan_t *desc, int nchan, int nsamp, int sample_size,
-                          void *dst, size_t block_stride, int block0, int nblocks,
-                          const DeviceTables *tab, hipStream_t stream, int max_active, long max_amplitude, void *scratch,
-                          const noise::Launch &nz)
-{
-    if (nblocks <= 0 || nsamp <= 0) return hipSuccess;
-    // receiver noise and the output level exist in the default kernels (seg, segh, generic) and tile; the host refuses the others first
-    if ((nz.tab || nz.mult) && variant != kTile && variant != kSeg && variant != kSegHalf && variant != kGeneric) return hipErrorInvalidValue;
-    uint8_t *d = static_cast<uint8_t *>(dst);
-    // the mask kernel only has the plain-add LUT formats: int16 sums that may leave the int16 range go to seg's packed core
-    if (variant == kSegMask && ((sample_size == GPSIQ_SC16 && max_amplitude > 32767) || !scratch)) variant = kSeg;
-    if (variant == kSegMask) {
-        const int rows_total = (nsamp + 63) / 64;
-        const int rowgroups = (rows_total + kMaskRowsPerThread - 1) / kMaskRowsPerThread;
-        uint64_t *masks = static_cast<uint64_t *>(scratch);
-        const size_t threads = (size_t) nblocks * rowgroups * 16;
-        hipLaunchKernelGGL(sign_masks, dim3((unsigned) ((threads + 255) / 256)), dim3(256), 0, stream, desc, nchan, nsamp, block0, nblocks,
-                           tab, masks, rows_total, rowgroups);
-        // every wave the same number of rows; workgroups of ~256 rows per wave amortise the LUT build
-        int wave_rows = 256, tiles = (rows_total + kWaves * wave_rows - 1) / (kWaves * wave_rows);
-        wave_rows = (rows_total + kWaves * tiles - 1) / (kWaves * tiles);
-        dim3 grid((unsigned) (tiles * nblocks)), block(kRowsThreads);
-        const int slots = max_active <= 4 ? 4 : max_active <= 8 ? 8 : max_active <= 12 ? 12 : 16;
-#define GPSIQ_LAUNCH_M(F, N) hipLaunchKernelGGL((synth_mask<F, N>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, masks, rows_total, tiles, wave_rows)
-        if (sample_size == GPSIQ_SC16) {
-            if (slots == 4) GPSIQ_LAUNCH_M(GPSIQ_SC16, 4); else if (slots == 8) GPSIQ_LAUNCH_M(GPSIQ_SC16, 8);
-            else if (slots == 12) GPSIQ_LAUNCH_M(GPSIQ_SC16, 12); else GPSIQ_LAUNCH_M(GPSIQ_SC16, 16);
-        } else {
-            if (slots == 4) GPSIQ_LAUNCH_M(GPSIQ_SC08, 4); else if (slots == 8) GPSIQ_LAUNCH_M(GPSIQ_SC08, 8);
-            else if (slots == 12) GPSIQ_LAUNCH_M(GPSIQ_SC08, 12); else GPSIQ_LAUNCH_M(GPSIQ_SC08, 16);
-        }
-#undef GPSIQ_LAUNCH_M
-        return hipGetLastError();
-    }
-    // the both-polarity table is a form of the plain-add core: sums that may leave the int16 range go to seg's packed core
-    if (variant == kSegBoth && !((sample_size == GPSIQ_SC08 || max_amplitude <= 32767) && seg_policy().allow_fast)) variant = kSeg;
-    if (variant == kSegBoth) {
-        // 4 KB of LUT per channel: with 16 channels two 8-wave workgroups still fit a CU (the same four waves per SIMD as
-        // seg) when a chunk is 16 rows, i.e. 8 KB of windows per workgroup (64 + 8 + 3 KB, twice = 150 of 160 KB); a single
-        // 16-wave workgroup per CU with 64-row chunks measured 10 % SLOWER than seg although its waves ran 11 % faster
-        // (SQ_WAVE_CYCLES): with one workgroup per CU nothing fills the CU while that workgroup starts up or drains.
-        const int slots = max_active <= 4 ? 4 : max_active <= 8 ? 8 : max_active <= 12 ? 12 : 16;
-        const int rows = slots == 4 ? 64 : slots == 8 ? 32 : 16;     // rows per chunk: the lane groups of the window builder need 4 windows each
-        const SegPolicy &pol = seg_policy();
-        const int rows_total = (nsamp + 63) / 64;
-        const int tiles1 = (rows_total + kWaves * rows - 1) / (kWaves * rows);
-        int wave_rows = rows, tiles = tiles1, tail_blocks = 0;
-        double best = 0.0;
-        for (int nwg = 1; nwg <= tiles1; ++nwg) {
-            const int wr = (rows_total + kWaves * nwg - 1) / (kWaves * nwg);
-            if (wr > pol.max_wave_rows) continue;
-            if (wr < rows && nwg < tiles1) break;
-            const double fill = (double) rows_total / ((double) kWaves * nwg * wr);
-            const double amort = (double) wr / ((double) wr + pol.setup_rows);
-            const double rounds = (double) nblocks * nwg / pol.resident_wgs;
-            const double score = fill * amort * rounds / (rounds + pol.drain_rounds);
-            if (score > best) { best = score; wave_rows = wr > rows ? wr : rows; tiles = nwg; }
-        }
-        if (wave_rows > rows) {
-            tail_blocks = (pol.tail_wgs + tiles1 - 1) / tiles1;
-            if (tail_blocks > nblocks / 2) tail_blocks = nblocks / 2;
-        }
-        const int big_blocks = nblocks - tail_blocks;
-        const int big_wgs = tiles * big_blocks;
-        dim3 grid((unsigned) (big_wgs + tiles1 * tail_blocks)), block(kRowsThreads);
-#define GPSIQ_LAUNCH_B(F, N, R) hipLaunchKernelGGL((synth_tile<F, N, R, 1, true, kWaves, true>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1)
-        if (sample_size == GPSIQ_SC16) {
-            if (slots == 4) GPSIQ_LAUNCH_B(GPSIQ_SC16, 4, 64); else if (slots == 8) GPSIQ_LAUNCH_B(GPSIQ_SC16, 8, 32);
-            else if (slots == 12) GPSIQ_LAUNCH_B(GPSIQ_SC16, 12, 16); else GPSIQ_LAUNCH_B(GPSIQ_SC16, 16, 16);
-        } else {
-            if (slots == 4) GPSIQ_LAUNCH_B(GPSIQ_SC08, 4, 64); else if (slots == 8) GPSIQ_LAUNCH_B(GPSIQ_SC08, 8, 32);
-            else if (slots == 12) GPSIQ_LAUNCH_B(GPSIQ_SC08, 12, 16); else GPSIQ_LAUNCH_B(GPSIQ_SC08, 16, 16);
-        }
-#undef GPSIQ_LAUNCH_B
-        return hipGetLastError();
-    }
-    if (variant == kTile || variant == kSeg || variant == kSegHalf) {
-        const bool half = variant == kSegHalf;
-        const int rows = half ? 32 : 64;                  // rows per chunk (the window array holds 64 windows per wave)
-        const int rows_total = (nsamp + 63) / 64;
-        // seg: many rows per wave amortise the per-workgroup set-up (LUT build, start products),
-        // but long workgroups make the drain of the grid expensive.  Every block is cut into
-        // nwg workgroups whose 8 waves all get the same number of rows, so no wave idles while
-        // its workgroup holds a CU slot, whatever the block length.  nwg maximises
-        //   (rows used / rows scheduled) x (rows per wave / (rows per wave + set-up)) x (rounds / (rounds + drain)),
-        // a model fitted to the measured variant sweeps; the last blocks are covered by
-        // one-chunk workgroups so that the drain is short.
-        const int tiles1 = (rows_total + kWaves * rows - 1) / (kWaves * rows);
-        int wave_rows = rows, tiles = tiles1, tail_blocks = 0;
-        if (variant != kTile) {
-            const SegPolicy &pol = seg_policy();
-            double best = 0.0;
-            for (int nwg = 1; nwg <= tiles1; ++nwg) {
-                const int wr = (rows_total + kWaves * nwg - 1) / (kWaves * nwg);
-                if (wr > pol.max_wave_rows) continue;
-                if (wr < rows && nwg < tiles1) break;
-                const double fill = (double) rows_total / ((double) kWaves * nwg * wr);
-                const double amort = (double) wr / ((double) wr + pol.setup_rows);
-                const double rounds = (double) nblocks * nwg / pol.resident_wgs;
-                const double score = fill * amort * rounds / (rounds + pol.drain_rounds);
-                if (score > best) { best = score; wave_rows = wr > rows ? wr : rows; tiles = nwg; }
-            }
-            if (wave_rows > rows) {
-                tail_blocks = (pol.tail_wgs + tiles1 - 1) / tiles1;
-                if (tail_blocks > nblocks / 2) tail_blocks = nblocks / 2;
-            }
-        }
-        const int big_blocks = nblocks - tail_blocks;
-        const int big_wgs = tiles * big_blocks;
-        dim3 grid((unsigned) (big_wgs + tiles1 * tail_blocks)), block(kRowsThreads);
-        // no channel sum of any resident block can leave the int16 range: plain-add kernel
-        // (the int8 kernels keep 12-bit fields and are exact for any gain)
-        // (with noise the bound is on |I + zI|: max_amplitude + max|z|; with the output level the noise is added outside the packed
-        // word and both formats run the int16 cores: the bound is on the signal alone)
-        const bool fast = (nz.mult ? max_amplitude <= 32767 : sample_size == GPSIQ_SC08 || max_amplitude + nz.max_z <= 32767) && seg_policy().allow_fast;
-#define GPSIQ_LAUNCH_T4(F, N, R, HH, FA) do { if (nz.mult) \
-            hipLaunchKernelGGL((synth_tile_level<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1, nz.tab, nz.seed, nz.block, nz.mult, nz.qmax); \
-        else if (nz.tab) \
-            hipLaunchKernelGGL((synth_tile_noise<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1, nz.tab, nz.seed, nz.block); \
-        else hipLaunchKernelGGL((synth_tile<F, N, R, HH, FA>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, wave_rows, big_wgs, big_blocks, tiles1); } while (0)
-#define GPSIQ_LAUNCH_T(F, N) do { if (half) { if (fast) GPSIQ_LAUNCH_T4(F, N, 32, 2, true); else GPSIQ_LAUNCH_T4(F, N, 32, 2, false); } \
-                                  else      { if (fast) GPSIQ_LAUNCH_T4(F, N, 64, 1, true); else GPSIQ_LAUNCH_T4(F, N, 64, 1, false); } } while (0)
-        const int slots = max_active <= 4 ? 4 : max_active <= 8 ? 8 : max_active <= 12 ? 12 : 16;
-        if (sample_size == GPSIQ_SC16) {
-            if (slots == 4) GPSIQ_LAUNCH_T(GPSIQ_SC16, 4); else if (slots == 8) GPSIQ_LAUNCH_T(GPSIQ_SC16, 8);
-            else if (slots == 12) GPSIQ_LAUNCH_T(GPSIQ_SC16, 12); else GPSIQ_LAUNCH_T(GPSIQ_SC16, 16);
-        } else {
-            if (slots == 4) GPSIQ_LAUNCH_T(GPSIQ_SC08, 4); else if (slots == 8) GPSIQ_LAUNCH_T(GPSIQ_SC08, 8);
-            else if (slots == 12) GPSIQ_LAUNCH_T(GPSIQ_SC08, 12); else GPSIQ_LAUNCH_T(GPSIQ_SC08, 16);
-        }
-#undef GPSIQ_LAUNCH_T
-#undef GPSIQ_LAUNCH_T4
-    } else if (variant == kRowsX) {
-        const int tiles = (nsamp + kRowsTile - 1) / kRowsTile;
-        dim3 grid((unsigned) (tiles * nblocks)), block(kRowsThreads);
-#define GPSIQ_LAUNCH_X(F, N) hipLaunchKernelGGL((synth_rowsx<F, N>), grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles)
-        const int slots = max_active <= 4 ? 4 : max_active <= 8 ? 8 : 16;
-        if (sample_size == GPSIQ_SC16) {
-            if (slots == 4) GPSIQ_LAUNCH_X(GPSIQ_SC16, 4); else if (slots == 8) GPSIQ_LAUNCH_X(GPSIQ_SC16, 8); else GPSIQ_LAUNCH_X(GPSIQ_SC16, 16);
-        } else {
-            if (slots == 4) GPSIQ_LAUNCH_X(GPSIQ_SC08, 4); else if (slots == 8) GPSIQ_LAUNCH_X(GPSIQ_SC08, 8); else GPSIQ_LAUNCH_X(GPSIQ_SC08, 16);
-        }
-#undef GPSIQ_LAUNCH_X
-    } else if (variant == kRows) {
-        const int tiles = (nsamp + kRowsTile - 1) / kRowsTile;
-        dim3 grid((unsigned) (tiles * nblocks)), block(kRowsThreads);
-        if (sample_size == GPSIQ_SC16)
-            hipLaunchKernelGGL(synth_rows<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles);
-        else
-            hipLaunchKernelGGL(synth_rows<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles);
-    } else {
-        const int tile_samples = 4096;
-        const int tiles = (nsamp + tile_samples - 1) / tile_samples;
-        dim3 grid((unsigned) (tiles * nblocks)), block(kGenericThreads);
-        if (sample_size == GPSIQ_SC16)
-            hipLaunchKernelGGL(synth_generic<GPSIQ_SC16>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
-                               nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
-        else
-            hipLaunchKernelGGL(synth_generic<GPSIQ_SC08>, grid, block, 0, stream, desc, nchan, nsamp, d, block_stride, block0, tab, tiles, tile_samples,
-                               nz.tab, nz.seed, nz.block, nz.mult, nz.qmax);
-    }
-    return hipGetLastError();
-}
+// tile / seg (64 rows per chunk, a window per row) and segh (32 rows, two windows per row), packed and plain-add core, per family
+struct Plain { template <int F, int N, int R, int H, bool FA> static constexpr TileFn      fn = synth_tile<F, N, R, H, FA>; };
+struct Noise { template <int F, int N, int R, int H, bool FA> static constexpr TileNoiseFn fn = synth_tile_noise<F, N, R, H, FA>; };
+struct Level { template <int F, int N, int R, int H, bool FA> static constexpr TileLevelFn fn = synth_tile_level<F, N, R, H, FA>; };
 
+template <class K, int F, int... N> constexpr auto tile_fns(Ints<N...>)
+{
+    using Fn = std::remove_const_t<decltype(K::template fn<F, 4, 64, 1, false>)>;
+    return std::array<Fn, 4 * sizeof...(N)>{K::template fn<F, N, 64, 1, false>..., K::template fn<F, N, 64, 1, true>...,
+                                            K::template fn<F, N, 32, 2, false>..., K::template fn<F, N, 32, 2, true>...};
+}
+template <class K> static auto tile_lookup(int fmt, int slots, bool half, bool fast)
+{
+    static constexpr auto t08 = tile_fns<K, GPSIQ_SC08>(Slots{}), t16 = tile_fns<K, GPSIQ_SC16>(Slots{});
+    const int s = index_of(Slots{}, slots);
+    return pick(t08, t16, fmt, s < 0 ? -1 : ((half ? 2 : 0) + (fast ? 1 : 0)) * 4 + s);
+}
+TileFn      tile_kernel(int fmt, int slots, bool half, bool fast) { return tile_lookup<Plain>(fmt, slots, half, fast); }
+TileNoiseFn tile_noise_kernel(int fmt, int slots, bool half, bool fast) { return tile_lookup<Noise>(fmt, slots, half, fast); }
+TileLevelFn tile_level_kernel(int fmt, int slots, bool half, bool fast) { return tile_lookup<Level>(fmt, slots, half, fast); }
+
+template <int F, int... N> constexpr std::array<TileFn, sizeof...(N)> both_fns(Ints<N...>) { return {synth_tile<F, N, both_rows(N), 1, true, kWaves, true>...}; }
+template <int F, int... N> constexpr std::array<MaskFn, sizeof...(N)> mask_fns(Ints<N...>) { return {synth_mask<F, N>...}; }
+template <int F, int... N> constexpr std::array<RowsFn, sizeof...(N)> rowsx_fns(Ints<N...>) { return {synth_rowsx<F, N>...}; }
+
+TileFn both_kernel(int fmt, int slots)
+{
+    static constexpr auto t08 = both_fns<GPSIQ_SC08>(Slots{}), t16 = both_fns<GPSIQ_SC16>(Slots{});
+    return pick(t08, t16, fmt, index_of(Slots{}, slots));
+}
+MaskFn mask_kernel(int fmt, int slots)
+{
+    static constexpr auto t08 = mask_fns<GPSIQ_SC08>(Slots{}), t16 = mask_fns<GPSIQ_SC16>(Slots{});
+    return pick(t08, t16, fmt, index_of(Slots{}, slots));
+}
+RowsFn rowsx_kernel(int fmt, int slots)
+{
+    static constexpr auto t08 = rowsx_fns<GPSIQ_SC08>(SlotsX{}), t16 = rowsx_fns<GPSIQ_SC16>(SlotsX{});
+    return pick(t08, t16, fmt, index_of(SlotsX{}, slots));
+}
+RowsFn      rows_kernel(int fmt) { return fmt == GPSIQ_SC16 ? synth_rows<GPSIQ_SC16> : fmt == GPSIQ_SC08 ? synth_rows<GPSIQ_SC08> : nullptr; }
+GenericFn   generic_kernel(int fmt) { return fmt == GPSIQ_SC16 ? synth_generic<GPSIQ_SC16> : fmt == GPSIQ_SC08 ? synth_generic<GPSIQ_SC08> : nullptr; }
+PatchFn     patch_kernel(int fmt) { return fmt == GPSIQ_SC16 ? apply_patches<GPSIQ_SC16> : fmt == GPSIQ_SC08 ? apply_patches<GPSIQ_SC08> : nullptr; }
+SignMasksFn sign_masks_kernel() { return sign_masks; }
 }  // namespace gpsiq

@@ -62,7 +62,7 @@
             else      lut[c][e] = (((uint32_t) tc << kPre) & 0xffffu) | ((uint32_t) ts << (16 + kPre));
         }
     }
-    for (int e = tid; e < NCH * kPrnExtWords; e += kRowsThreads) {
+    for (int e = tid; e < NCH * kPrnExtWords; e += kThreads) {
         const int c = e / kPrnExtWords, w = e % kPrnExtWords;
         ext[c][w] = qs[c].prn ? tab->prn_ext[qs[c].prn - 1][w] : 0u;
     }

@@ -8,10 +8,10 @@ for cfg in "cfg3 10000000" "cfg5 25000000"; do
   OUT=$REPO/gpurun_out/prof_$name
   mkdir -p $OUT
   BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-extra --launches 6 --steps 10 --fs $fs --sample-size 2"
-  $BENCH > $OUT/bench.json 2> $OUT/bench.err; tail -1 $OUT/bench.json | cut -c1-300
-  rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
-  rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/pmc_write.log 2>&1
-  rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/pmc_fetch.log 2>&1
+  timeout -k 10 400 $BENCH > $OUT/bench.json 2> $OUT/bench.err || exit 1; tail -1 $OUT/bench.json | cut -c1-300
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1 || exit 1
+  timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/pmc_write.log 2>&1 || exit 1
+  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/pmc_fetch.log 2>&1 || exit 1
   nb=$(python -c "import json,sys; print(json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])['config']['blocks_per_launch'])")
   ( cd $REPO && PMC_KEY=${fs}_16_2_${nb} python scripts/prof_summary.py gpurun_out/prof_$name ${PROF_TAG:-r02}_$name > $OUT/summary.log 2>&1; tail -2 $OUT/summary.log )
   find $OUT -name "*.db" -size +20M -delete

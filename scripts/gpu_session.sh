@@ -10,6 +10,7 @@
 #   rates    throughput over the BASELINE / front-end sample rates
 #   exactprof rocprofv3 kernel trace + HBM traffic of the GPSIQ_NCO_REFERENCE batch call (scripts/exact_call_prof.py)
 #   soakeval tests/soak_device_eval.py, 3 seeds: device evaluation == host evaluation (== the reference's own loop) on random runs
+#   dispatches the kernel trace of a fixed list of launches (scripts/launch_dispatches.py): run at two commits, then `compare` the two directories
 #   eval     the device evaluation: tests/test_gpu_device_eval.py, scripts/eval_timing.py (all threads, then GPSIQ_THREADS=2)
 TAG=${TAG:-r06}
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -27,6 +28,9 @@ for step in "$@"; do
       ( cd /tmp && export TMPDIR=/tmp && O=$REPO/$LOGS/chain_pmc && mkdir -p $O &&
         timeout 150 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY \
           -d $O/a -o pmc -- python $REPO/scripts/chain_pmc.py > $O/a.log 2>&1; grep Msps $O/a.log ) ;;
+    dispatches)
+      ( cd /tmp && export TMPDIR=/tmp && O=$REPO/$LOGS/${TAG}_dispatches && rm -rf $O && mkdir -p $O &&
+        timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O -o kt -- python $REPO/scripts/launch_dispatches.py render > $O/render.log 2>&1; tail -2 $O/render.log ) ;;
     eval)
       ( timeout 1500 python -m pytest tests/test_gpu_device_eval.py -m gpu -x -q 2>&1 | tail -40 ) > $LOGS/${TAG}_eval_tests.log 2>&1; tail -25 $LOGS/${TAG}_eval_tests.log
       ( timeout 600 python scripts/eval_timing.py ) > $LOGS/${TAG}_eval_timing.log 2>&1; grep -v "trace\] descriptors" $LOGS/${TAG}_eval_timing.log
@@ -34,9 +38,9 @@ for step in "$@"; do
     exactprof)
       ( cd /tmp && export TMPDIR=/tmp && O=$REPO/$LOGS/exact_prof && rm -rf $O && mkdir -p $O &&
         echo '{"calls": 6, "blocks": [2000, 4130], "nsamp": 260000, "ss": 1}' > $O/meta.json &&
-        EXACT_PROF_25M=1 timeout 200 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python $REPO/scripts/exact_call_prof.py 6 > $O/kt.log 2>&1; tail -3 $O/kt.log
-        timeout 200 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o pmc -- python $REPO/scripts/exact_call_prof.py 6 > $O/pmc_write.log 2>&1
-        timeout 200 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o pmc -- python $REPO/scripts/exact_call_prof.py 6 > $O/pmc_fetch.log 2>&1
+        EXACT_PROF_25M=1 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python $REPO/scripts/exact_call_prof.py 6 > $O/kt.log 2>&1 || exit 1; tail -3 $O/kt.log
+        timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o pmc -- python $REPO/scripts/exact_call_prof.py 6 > $O/pmc_write.log 2>&1 || exit 1
+        timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o pmc -- python $REPO/scripts/exact_call_prof.py 6 > $O/pmc_fetch.log 2>&1 || exit 1
         cd $REPO && python scripts/exact_call_summary.py $LOGS/exact_prof $TAG > $O/summary.log 2>&1; tail -60 $O/summary.log
         find $O -name "*.db" -size +8M -delete
         mkdir -p $LOGS/profiles_out; cp profiles/${TAG}_exact_call_* profiles/pmc_traffic.json $LOGS/profiles_out/ ) ;;

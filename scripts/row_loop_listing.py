@@ -139,7 +139,9 @@ def kernel_hashes(lib, pattern):
             for f in re.split(r"\n(?=[0-9a-f]+ <[^>]+>:\n)", dis):
                 m = re.match(r"[0-9a-f]+ <([^>]+)>:", f.split("\n", 1)[0])
                 if m:
-                    funcs[m.group(1)] = [t for t in (ln.split("//")[0].strip() for ln in f.split("\n")[1:]) if t]
+                    # ("...": the zero padding up to the next function's alignment, which depends on the order of the functions in the
+                    # code object, not on this one's instructions)
+                    funcs[m.group(1)] = [t for t in (ln.split("//")[0].strip() for ln in f.split("\n")[1:]) if t and t != "..."]
             names = list(funcs)
             dem = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
             for n, d in zip(names, dem):

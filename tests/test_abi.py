@@ -147,6 +147,12 @@ def test_replayed_counters_are_bound_to_the_loaded_kernel(tmp_path, monkeypatch)
     csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
     devsrc = [l for l in open(os.path.join(csrc, "Makefile")) if l.startswith("DEVSRC")][0].split(":=")[1].split()     # every device source
     assert "gpsiq_kernels.hip" in devsrc and "gpsiq_chain_kernels.hip" in devsrc and "gpsiq_eval_kernels.hip" in devsrc and "gpsiq_lane.h" in devsrc
+    # the id is the identity of the device code: the geometry the kernels are compiled for is in, the launch planner and the
+    # launcher (host policy) are out, and nothing outside the device sources defines a kernel
+    assert "gpsiq_geometry.h" in devsrc and "gpsiq_launch.cpp" not in devsrc and "gpsiq_launch_plan.h" not in devsrc
+    for f in sorted(os.listdir(csrc)):
+        if f not in devsrc and os.path.isfile(os.path.join(csrc, f)):
+            assert "__global__" not in open(os.path.join(csrc, f), errors="replace").read(), f
     blob = b"".join(open(os.path.join(csrc, f), "rb").read() for f in devsrc)
     assert gpsiq.kernels_id() == hashlib.sha256(blob).hexdigest()[:16], "libgpsiq.so is older than its device sources: rebuild"
     sys.path.insert(0, ROOT)
