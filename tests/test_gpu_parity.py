@@ -605,7 +605,6 @@ def test_an_error_in_a_late_piece_of_a_batch(ctx, oracle, monkeypatch, mode):
     call returns), and the context goes on working."""
     import torch
     monkeypatch.setenv("GPSIQ_PIECE_BLOCKS", "3")
-    monkeypatch.setenv("GPSIQ_PIECE_BLOCKS", "3")
     fs, ns, nb, nc = 2.6e6, 26000, 11, 6
     d = synth_blocks(nb, nc, seed=91)
     bad = d.copy()
