@@ -6,84 +6,90 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "gpsiq_internal.h"
 #include "gpsiq_evalctl.h"
 #include "gpsiq_noise.h"
+#include "gpsiq_own.h"
 
 struct gpsiq_ctx {
+    template <typename T> using DevBuf = gpsiq::DevBuf<T>;
+    template <typename T> using PinnedBuf = gpsiq::PinnedBuf<T>;
+    using Event = gpsiq::Event;
+    using Stream = gpsiq::Stream;
+
     int           device = -1;
-    hipStream_t   stream = nullptr;
-    hipStream_t   stream2 = nullptr;                     // every other piece of a batch in pieces (piece_stream below)
-    gpsiq::DeviceTables *d_tab = nullptr;
-    hipStream_t   copy_stream[2] = {nullptr, nullptr};   // device-to-host copies of the batch calls
+    Stream        stream;
+    Stream        stream2;                               // every other piece of a batch in pieces (piece_stream below)
+    DevBuf<gpsiq::DeviceTables> d_tab;
+    Stream        copy_stream[2];                        // device-to-host copies of the batch calls
     // resident descriptors, kSets buffers taken in turn: a new set is staged and uploaded into a buffer the latest launches
     // are NOT reading, so gpsiq_set_descriptors never waits for the device to go idle -- only, if it is still in flight, for the
     // launch from kSets sets ago that used the same buffer.  Four: the pieces of a batch alternate between two streams and a
     // piece's kernel shares the device with its neighbour's, so with two sets piece k+2 waited for a piece k that had been
     // slowed down by piece k+1 (GPSIQ_DESC_SETS=2 for the A/B, read per set)
     struct DescBuf {
-        gpsiq_qchan_t *d = nullptr;  size_t cap = 0;      // device copy, in descriptors
-        gpsiq_qchan_t *h = nullptr;  size_t hcap = 0;     // page-locked staging of the compacted descriptors
+        DevBuf<gpsiq_qchan_t>    d;                       // device copy, in descriptors
+        PinnedBuf<gpsiq_qchan_t> h;                       // page-locked staging of the compacted descriptors
         // one event per stream that has launched on this buffer since it was last known idle: a launch on stream B must
         // not hide a longer one still running on stream A (when more than kUses streams are in play the extra ones
         // are chained behind the first, which then covers them)
-        struct Use { hipStream_t s = nullptr; hipEvent_t ev = nullptr; bool active = false; };
+        struct Use { hipStream_t s = nullptr; Event ev; bool active = false; };      // (s: the caller's, not ours)
         static constexpr int kUses = 4;
         Use            use[kUses];
         bool           in_use = false;
         std::vector<uint8_t> active_per_block;            // active channels of every resident block (patch validation)
         // patches that go with this set (GPSIQ_NCO_REFERENCE): per buffer, so that the next set's list can be uploaded
         // while launches of this one are still applying theirs
-        gpsiq_patch_t *d_patch = nullptr;
-        size_t         patch_cap = 0;
-        int            npatch = 0;
-        gpsiq_patch_t *h_patch = nullptr;  size_t h_patch_cap = 0;   // page-locked staging of the list (asynchronous sets)
+        DevBuf<gpsiq_patch_t>    d_patch;
+        int                      npatch = 0;
+        PinnedBuf<gpsiq_patch_t> h_patch;                 // page-locked staging of the list (asynchronous sets)
         // a set staged without waiting (the pieces of a batch): the uploads are on up_stream, `uploaded` is recorded behind
         // them, and every launch on the set waits for it on its own stream
-        hipEvent_t     uploaded = nullptr;
+        Event          uploaded;
         bool           upload_pending = false;
     } buf[4];
     static constexpr int kSets = 4;
-    hipStream_t    up_stream = nullptr;  // descriptor / patch uploads: never behind a running kernel
+    Stream         up_stream;           // descriptor / patch uploads: never behind a running kernel
     int            cur = 0;             // buf[cur] holds the resident set
-    gpsiq_qchan_t *d_desc = nullptr;    // == buf[cur].d
+    gpsiq_qchan_t *d_desc = nullptr;    // == buf[cur].d.get()
     int            nblocks = 0, nchan = 0;
     gpsiq::SynthClass cls;              // what the resident set contributes to the choice of kernel (gpsiq_launch_plan.h)
     int            nco_mode = GPSIQ_NCO_FIXED;
     // receiver noise (gpsiq_set_noise): on while sigma > 0; next_block is the absolute index the next drop-in call's block 0
-    // gets, call_block that of the running call's block 0 (every path of the call numbers its blocks from it)
+    // gets, call_block that of the running call's block 0 (every path of the call numbers its blocks from it).  Settings only:
+    // the table they stand for on the context's device is d_noise_tab (gpsiq::noise::kTabEntries)
     struct Noise {
         uint64_t seed = 0, next_block = 0;
         double   sigma = 0.0;
         long     max_z = 0;                            // S_tail[63] = max |z|
-        gpsiq::noise::Entry *d_tab = nullptr;          // gpsiq::noise::kTabEntries, on the context's device
     } noise;
+    DevBuf<gpsiq::noise::Entry> d_noise_tab;
     uint64_t       call_block = 0;
-    // output level stage (gpsiq_set_level, include/gpsiq_rows.h): on while mult != 0.  d_zero is the all-zero noise table the
+    // output level stage (gpsiq_set_level, include/gpsiq_rows.h): on while mult != 0.  d_zero_tab is the all-zero noise table the
     // kernels read while the level is on and the noise is off
     struct Level {
         uint32_t mult = 0;
         int32_t  qmax = 0;
-        gpsiq::noise::Entry *d_zero = nullptr;
     } level;
-    // scratch of the kernel variants that need some (segm: the sign masks of one launch)
-    void          *d_scratch = nullptr;
-    size_t         scratch_cap = 0;
-    // staging of the batch calls' output (PieceOut below)
-    void          *d_out = nullptr;
-    size_t         out_cap = 0;
-    hipEvent_t     chunk_done[2] = {nullptr, nullptr};
+    DevBuf<gpsiq::noise::Entry> d_zero_tab;
+    // scratch of the kernel variants that need some (segm: the sign masks of one launch), in bytes
+    DevBuf<uint8_t> d_scratch;
+    // staging of the batch calls' output (PieceOut below), in bytes
+    DevBuf<uint8_t> d_out;
+    Event           chunk_done[2];
     // gpsiq_generate_block_async: a small ring of per-block descriptor / output staging, each with the event that
-    // says its block has landed
+    // says its block has landed.  Every member is reserved / ensured on its own by every call: a call that failed half-way
+    // leaves nothing that looks complete
     struct AsyncSlot {
-        gpsiq_qchan_t *d = nullptr, *h = nullptr;
-        gpsiq_patch_t *d_patch = nullptr, *h_patch = nullptr;   // GPSIQ_NCO_REFERENCE: the block's patches, staged page-locked
-        size_t         patch_cap = 0;
-        void          *out = nullptr;
-        size_t         out_cap = 0;
-        hipEvent_t     done = nullptr;
+        DevBuf<gpsiq_qchan_t>    d;
+        PinnedBuf<gpsiq_qchan_t> h;
+        DevBuf<gpsiq_patch_t>    d_patch;                 // GPSIQ_NCO_REFERENCE: the block's patches ...
+        PinnedBuf<gpsiq_patch_t> h_patch;                 // ... staged page-locked
+        DevBuf<uint8_t>          out;                     // bytes
+        Event          done;
         bool           busy = false;
     } aslot[4];
     int anext = 0;
@@ -98,36 +104,45 @@ struct gpsiq_ctx {
     // the carrier chain of GPSIQ_NCO_REFERENCE on the device (gpsiq_chain_maps_device): inputs, estimates and maps of the
     // timeline being worked through, device side and page-locked staging, kept between calls
     struct Chain {
-        size_t             cap = 0;                    // blocks x channels all of these hold
-        gpsiq_chain_in_t  *d_in = nullptr, *h_in = nullptr;
-        void              *d_prep = nullptr;           // lane::Prep, 32 bytes each
-        gpsiq_chain_map_t *d_maps = nullptr, *h_maps = nullptr;
-        gpsiq_chain_est_t *d_est = nullptr, *h_est = nullptr;       // [3][GPSIQ_MAX_CHAN]: start, end of the first launch (= start of a second), end
-        double            *d_c_before = nullptr;
-        hipStream_t        stream = nullptr, back = nullptr;   // uploads + kernels; the maps' way back + the callbacks (never in the kernels' way)
-        hipEvent_t         t0 = nullptr, t1 = nullptr, landed = nullptr;   // landed: the maps of the last range queued are in h_maps
-        hipEvent_t         walked[2] = {nullptr, nullptr};     // a launch's kernels are done
-        float              last_ms = 0.0f;             // device time of the last call's two kernels
+        DevBuf<gpsiq_chain_in_t>     d_in;              // these five hold the same number of blocks x channels (reserve)
+        PinnedBuf<gpsiq_chain_in_t>  h_in;
+        DevBuf<uint8_t>              d_prep;            // lane::Prep, kPrepBytes each
+        DevBuf<gpsiq_chain_map_t>    d_maps;
+        PinnedBuf<gpsiq_chain_map_t> h_maps;
+        DevBuf<gpsiq_chain_est_t>    d_est;             // [kEvalMaxPieces + 1][GPSIQ_MAX_CHAN]: start, end of the first launch (= start of a second), end
+        PinnedBuf<gpsiq_chain_est_t> h_est;
+        DevBuf<double>               d_c_before;
+        Stream             stream, back;                // uploads + kernels; the maps' way back + the callbacks (never in the kernels' way)
+        Event              t0, t1, landed;              // landed: the maps of the last range queued are in h_maps
+        Event              walked[2];                   // a launch's kernels are done
+        float              last_ms = 0.0f;              // device time of the last call's two kernels
+        static constexpr size_t kPrepBytes = 32;
+        int reserve(size_t n);                          // first use + room for n blocks x channels
     } chain;
     // batch calls whose descriptors are quantised / evaluated on the device (gpsiq_evaldev.cpp; shares chain's buffers and streams)
     struct EvalDev {
-        size_t          cap = 0;                       // block-channels d_chan / h_chan hold
-        void           *d_chan = nullptr, *h_chan = nullptr;   // ev::DChan rows: device, page-locked staging (host-packed sources)
-        gpsiq_chan_t   *d_raw = nullptr;  size_t raw_cap = 0;   // page-locked sources: the raw descriptors in HBM
-        double         *d_seeds = nullptr; size_t seeds_cap = 0; // start states given by the caller (gpsiq_generate_seeded)
-        gpsiq::EvalCtrl *d_ctrl = nullptr, *h_ctrl = nullptr;   // h_ctrl[kEvalMaxPieces + 1]: a snapshot behind every piece, one at the end
-        gpsiq::LinkCarry *d_link = nullptr, *h_link = nullptr;  // [GPSIQ_MAX_CHAN]
-        gpsiq::FixedCarry *d_fix = nullptr, *h_fix = nullptr;
-        gpsiq_patch_t  *d_patches = nullptr, *h_patches = nullptr;  unsigned patch_cap = 0;
-        gpsiq::EvalHostItem *d_host = nullptr, *h_host = nullptr;   unsigned host_cap = 0;
-        gpsiq_chan_t   *h_items = nullptr;  unsigned items_cap = 0;                       // device-resident descriptors the host walker needs, page-locked
-        gpsiq::EvalSlotRow *d_slot = nullptr, *h_slot = nullptr;  size_t slot_cap = 0;    // repair: one slot's column (+ one row before), device and page-locked
-        double         *d_col = nullptr, *h_col = nullptr;                                 // ... and its start states on the way back
-        hipStream_t     eval_stream = nullptr, chain_stream = nullptr;   // highest priority: beside the synthesis, ahead of its workgroups
-        hipEvent_t      linked[gpsiq::kEvalMaxPieces] = {}, evaluated[gpsiq::kEvalMaxPieces] = {}, joined = nullptr, t_synth0 = nullptr, t_synth1 = nullptr;
+        static constexpr size_t kChanBytes = 64;        // sizeof(ev::DChan) (gpsiq_eval.h)
+        static constexpr unsigned kPatchCap = 1u << 16, kHostCap = 1u << 13;
+        DevBuf<uint8_t>    d_chan;                      // ev::DChan rows, in bytes: device ...
+        PinnedBuf<uint8_t> h_chan;                      // ... and page-locked staging (host-packed sources), the same size
+        DevBuf<gpsiq_chan_t> d_raw;                     // page-locked sources: the raw descriptors in HBM
+        DevBuf<double>     d_seeds;                     // start states given by the caller (gpsiq_generate_seeded)
+        DevBuf<gpsiq::EvalCtrl>    d_ctrl;
+        PinnedBuf<gpsiq::EvalCtrl> h_ctrl;              // [kEvalMaxPieces + 2]: a snapshot behind every piece, one at the end, the zeroed one
+        DevBuf<gpsiq::LinkCarry>   d_link;  PinnedBuf<gpsiq::LinkCarry>  h_link;     // [GPSIQ_MAX_CHAN]
+        DevBuf<gpsiq::FixedCarry>  d_fix;   PinnedBuf<gpsiq::FixedCarry> h_fix;
+        DevBuf<gpsiq_patch_t>      d_patches;  PinnedBuf<gpsiq_patch_t>  h_patches;  // [kPatchCap]
+        DevBuf<gpsiq::EvalHostItem> d_host;  PinnedBuf<gpsiq::EvalHostItem> h_host;  // [kHostCap]
+        PinnedBuf<gpsiq_chan_t>    h_items;             // device-resident descriptors the host walker needs, page-locked
+        DevBuf<gpsiq::EvalSlotRow> d_slot;  PinnedBuf<gpsiq::EvalSlotRow> h_slot;    // repair: one slot's column (+ one row before), device and page-locked
+        DevBuf<double>     d_col;  PinnedBuf<double> h_col;                          // ... and its start states on the way back (one size, reserve_repair)
+        Stream             eval_stream, chain_stream;   // highest priority: beside the synthesis, ahead of its workgroups
+        Event              linked[gpsiq::kEvalMaxPieces], evaluated[gpsiq::kEvalMaxPieces], joined, t_synth0, t_synth1;
         // statistics of the last call (gpsiq_evaldev_stats)
         double          host_ms = 0.0;                 // host thread-time spent on the call's descriptors (pack, repair, walker)
         unsigned        last_nhost = 0, last_npatch = 0, last_repaired = 0;
+        int reserve(size_t n, bool pinned_source, bool seeds);     // first use + room for n blocks x channels
+        int reserve_repair(size_t rows);
     } evd;
 };
 
@@ -135,9 +150,81 @@ struct gpsiq_ctx {
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess)                                                                \
-            return fail(GPSIQ_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));             \
+            return gpsiq::fail(GPSIQ_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
 
+// ---- first use and growth of the chain's and the device evaluation's resources ------------------------------------------------
+// Every member is ensured / reserved by every call, each a compare once it exists: a call that fails part-way returns its error,
+// and the next call makes what is still missing instead of taking a half-made set for a whole one.  Members that share a
+// capacity are grown in one step that is entered while ANY of them lacks room for n (the smallest of their capacities): after a
+// step that failed part-way -- forget before free leaves the member it failed at empty, the ones behind it at their old size --
+// every later call enters it again, whatever its n.
+inline int gpsiq_ctx::Chain::reserve(size_t n)
+{
+    // (equal priorities: with the synthesis stream above the chain's, the second launch's maps came back late -- 0.98 ms
+    // instead of 0.78 -- and the pieces behind the head waited for them: 2.6 ms per call instead of 2.4, profiles/r05_chain_ab.txt)
+    HIP_TRY(stream.ensure());
+    HIP_TRY(back.ensure());
+    for (auto &e : walked) HIP_TRY(e.ensure());
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(landed.ensure());
+    HIP_TRY(d_est.reserve((gpsiq::kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN));
+    HIP_TRY(h_est.reserve((gpsiq::kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN));
+    HIP_TRY(d_c_before.reserve(gpsiq::kEvalMaxPieces * GPSIQ_MAX_CHAN));
+    if (n <= std::min({d_in.cap(), h_in.cap(), d_prep.cap() / kPrepBytes, d_maps.cap(), h_maps.cap()})) return GPSIQ_OK;
+    const size_t cap = n + n / 4 + 256;
+    HIP_TRY(d_in.reserve(cap));
+    HIP_TRY(h_in.reserve(cap));
+    HIP_TRY(d_prep.reserve(cap * kPrepBytes));
+    HIP_TRY(d_maps.reserve(cap));
+    HIP_TRY(h_maps.reserve(cap));
+    return GPSIQ_OK;
+}
+
+inline int gpsiq_ctx::EvalDev::reserve(size_t n, bool pinned_source, bool seeds)
+{
+    // Chain and evaluation run BESIDE the synthesis, which floods the device with workgroups: their streams get the highest
+    // priority, so that the few workgroups of prepare / lanes / link / evaluation are dispatched as synthesis workgroups retire
+    // instead of behind all of them (the patches have to be there when the synthesis ends, not some time after it).
+    // (MI355X, 2.6 Msps, 2 000 blocks: 1.82 ms per call against 2.20 at equal priorities; 25 Msps: 1.54 against 2.61)
+    HIP_TRY(eval_stream.ensure_greatest());
+    HIP_TRY(chain_stream.ensure_greatest());
+    HIP_TRY(t_synth0.ensure(hipEventDefault));
+    HIP_TRY(t_synth1.ensure(hipEventDefault));
+    for (auto &ev_ : linked) HIP_TRY(ev_.ensure());
+    for (auto &ev_ : evaluated) HIP_TRY(ev_.ensure());
+    HIP_TRY(joined.ensure());
+    HIP_TRY(d_ctrl.reserve(1));
+    HIP_TRY(h_ctrl.reserve(gpsiq::kEvalMaxPieces + 2));
+    HIP_TRY(d_link.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(h_link.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(d_fix.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(h_fix.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(d_patches.reserve(kPatchCap));
+    HIP_TRY(h_patches.reserve(kPatchCap));
+    HIP_TRY(d_host.reserve(kHostCap));
+    HIP_TRY(h_host.reserve(kHostCap));
+    if (n * kChanBytes > std::min(d_chan.cap(), h_chan.cap())) {
+        const size_t cap = n + n / 4 + 256;
+        HIP_TRY(d_chan.reserve(cap * kChanBytes));
+        HIP_TRY(h_chan.reserve(cap * kChanBytes));
+    }
+    if (pinned_source && n > d_raw.cap()) HIP_TRY(d_raw.reserve(n + n / 4 + 16));
+    if (seeds && n > d_seeds.cap()) HIP_TRY(d_seeds.reserve(n + n / 4 + 16));
+    return GPSIQ_OK;
+}
+
+inline int gpsiq_ctx::EvalDev::reserve_repair(size_t rows)
+{
+    if (rows <= std::min({d_slot.cap(), h_slot.cap(), d_col.cap(), h_col.cap()})) return GPSIQ_OK;
+    const size_t cap = rows + 256;
+    HIP_TRY(d_slot.reserve(cap));
+    HIP_TRY(h_slot.reserve(cap));
+    HIP_TRY(d_col.reserve(cap));
+    HIP_TRY(h_col.reserve(cap));
+    return GPSIQ_OK;
+}
 
 // helpers of gpsiq_device.cpp the other translation unit uses
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
@@ -151,7 +238,7 @@ int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s);
 // (four sets taken in turn; piece k+2 follows piece k on the same stream), so consecutive pieces alternate
 // between two streams and the next piece's first workgroups fill the compute units the last ones of this piece leave.
 // (One stream against two: profiles/r05_chain_ab.txt.)
-inline hipStream_t gpsiq_piece_stream(gpsiq_ctx *c, int k) { return (k & 1) ? c->stream2 : c->stream; }
+inline hipStream_t gpsiq_piece_stream(gpsiq_ctx *c, int k) { return ((k & 1) ? c->stream2 : c->stream).get(); }
 
 // The output of one batch call: its blocks are rendered straight into the caller's device memory where the rows are ours
 // (direct: 16-byte rows, 4-byte aligned), else into c->d_out with 16-byte rows and copied across on the context's two copy
@@ -165,12 +252,15 @@ struct PieceOut {
     bool       dst_is_device = false, direct = false;
 
     int begin(gpsiq_ctx *ctx, int nblocks, int nsamp, int sample_size, void *dst, int dst_is_device);   // sizes the staging
-    uint8_t *target(int b0) const { return (direct ? dst : static_cast<uint8_t *>(c->d_out)) + (size_t) b0 * stride; }   // where block b0 is rendered
+    uint8_t *target(int b0) const { return (direct ? dst : c->d_out.get()) + (size_t) b0 * stride; }   // where block b0 is rendered
     int rendered(int b0, int nb, hipStream_t s);                 // blocks [b0, b0 + nb) cross once their kernel on s is done
     int whole(hipStream_t s);                                    // every block, behind the kernel on s (one kernel, one copy)
     int again(hipStream_t s, const std::vector<gpsiq_patch_t> &patches);   // the blocks patched on s (sorted by block) once more
     int finish(const char *label, int rc = GPSIQ_OK);            // rc != GPSIQ_OK: the call has failed, its error text stands
 };
+
+// what a patch list of n entries (n > 0) asks its buffers for
+inline size_t gpsiq_patch_room(size_t n) { return n < 256 ? 256 : n; }
 
 // the fixed-point carrier: whether slot i continues what the context handed out (the caller gave back what it was given) ...
 inline bool gpsiq_continues(const gpsiq_ctx *c, int i, const gpsiq_chan_t &ch)
@@ -185,7 +275,6 @@ inline void gpsiq_hand_back(gpsiq_ctx *c, int i, int prn, uint64_t phase, double
     c->handed[i] = prn ? gpsiq::carr_phase_to_double(phase) : 0.0;
     if (carr_phase_out) carr_phase_out[i] = c->handed[i];
 }
-int gpsiq_chain_reserve(gpsiq_ctx *c, size_t n);
 double gpsiq_rate_kernel();
 void gpsiq_note_kernel_rate(double channel_samples_per_s);      // a measured rate of the synthesis kernel (running mean)
 // GPSIQ_NCO_REFERENCE batch with chain link and evaluation on host threads (the path of rounds 4-5; fallback of the device path)
@@ -195,7 +284,6 @@ int gpsiq_generate_reference_host(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblo
 // not taken (too short a batch, switched off), the caller goes on with the host path
 int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                           void *dst, int dst_is_device, double *carr_phase_out, const double *seeds, int *handled);
-void gpsiq_evaldev_destroy(gpsiq_ctx *c);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns

@@ -30,12 +30,12 @@ static double wall_ms()
 static int wait_idle(gpsiq_ctx::DescBuf &b)
 {
     if (b.upload_pending) {              // also when nothing was ever launched on the set: its staging is about to be rewritten
-        HIP_TRY(hipEventSynchronize(b.uploaded));
+        HIP_TRY(hipEventSynchronize(b.uploaded.get()));
         b.upload_pending = false;
     }
     if (!b.in_use) return GPSIQ_OK;
     for (auto &u : b.use)
-        if (u.active) { HIP_TRY(hipEventSynchronize(u.ev)); u.active = false; }
+        if (u.active) { HIP_TRY(hipEventSynchronize(u.ev.get())); u.active = false; }
     b.in_use = false;
     return GPSIQ_OK;
 }
@@ -52,10 +52,10 @@ static int mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s)
     if (!slot) {
         // more streams than events: put this stream behind the first tracked one, whose event it then re-records
         slot = &b.use[0];
-        HIP_TRY(hipStreamWaitEvent(s, slot->ev, 0));
+        HIP_TRY(hipStreamWaitEvent(s, slot->ev.get(), 0));
     }
-    if (!slot->ev) HIP_TRY(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(slot->ev, s));
+    HIP_TRY(slot->ev.ensure());
+    HIP_TRY(hipEventRecord(slot->ev.get(), s));
     slot->s = s; slot->active = true;
     b.in_use = true;
     return GPSIQ_OK;
@@ -128,15 +128,15 @@ int gpsiq_create(gpsiq_ctx_t **out, int device)
     DeviceTables *h = new (std::nothrow) DeviceTables;
     if (!h) { delete c; return fail(GPSIQ_E_NOMEM, "out of memory"); }
     build_device_tables(h);
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking);
+    e = c->stream.ensure();
+    if (e == hipSuccess) e = c->stream2.ensure();
+    if (e == hipSuccess) e = c->up_stream.ensure();
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipStreamCreateWithFlags(&c->copy_stream[i], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->chunk_done[i], hipEventDisableTiming);
+        e = c->copy_stream[i].ensure();
+        if (e == hipSuccess) e = c->chunk_done[i].ensure();
     }
-    if (e == hipSuccess) e = hipMalloc((void **) &c->d_tab, sizeof(DeviceTables));
-    if (e == hipSuccess) e = hipMemcpy(c->d_tab, h, sizeof(DeviceTables), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->d_tab.reserve(1);
+    if (e == hipSuccess) e = hipMemcpy(c->d_tab.get(), h, sizeof(DeviceTables), hipMemcpyHostToDevice);
     delete h;
     if (e != hipSuccess) {
         gpsiq_destroy(c);
@@ -146,55 +146,13 @@ int gpsiq_create(gpsiq_ctx_t **out, int device)
     return GPSIQ_OK;
 }
 
+// (every member of the context owns what it holds, gpsiq_own.h: nothing is listed here -- also for a context that
+// gpsiq_create gave up on half-way)
 void gpsiq_destroy(gpsiq_ctx_t *c)
 {
     if (!c) return;
-    if (c->device >= 0) (void) hipSetDevice(c->device);
+    (void) hipSetDevice(c->device);
     (void) hipDeviceSynchronize();
-    if (c->d_tab) (void) hipFree(c->d_tab);
-    if (c->d_out) (void) hipFree(c->d_out);
-    if (c->d_scratch) (void) hipFree(c->d_scratch);
-    for (auto &a : c->aslot) {
-        if (a.d) (void) hipFree(a.d);
-        if (a.h) (void) hipHostFree(a.h);
-        if (a.d_patch) (void) hipFree(a.d_patch);
-        if (a.h_patch) (void) hipHostFree(a.h_patch);
-        if (a.out) (void) hipFree(a.out);
-        if (a.done) (void) hipEventDestroy(a.done);
-    }
-    for (int i = 0; i < gpsiq_ctx::kSets; ++i) {
-        if (c->buf[i].d) (void) hipFree(c->buf[i].d);
-        if (c->buf[i].h) (void) hipHostFree(c->buf[i].h);
-        if (c->buf[i].d_patch) (void) hipFree(c->buf[i].d_patch);
-        if (c->buf[i].h_patch) (void) hipHostFree(c->buf[i].h_patch);
-        if (c->buf[i].uploaded) (void) hipEventDestroy(c->buf[i].uploaded);
-        for (auto &u : c->buf[i].use)
-            if (u.ev) (void) hipEventDestroy(u.ev);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (c->chunk_done[i]) (void) hipEventDestroy(c->chunk_done[i]);
-        if (c->copy_stream[i]) (void) hipStreamDestroy(c->copy_stream[i]);
-    }
-    gpsiq_evaldev_destroy(c);
-    if (c->chain.d_in) (void) hipFree(c->chain.d_in);
-    if (c->chain.h_in) (void) hipHostFree(c->chain.h_in);
-    if (c->chain.d_prep) (void) hipFree(c->chain.d_prep);
-    if (c->chain.d_maps) (void) hipFree(c->chain.d_maps);
-    if (c->chain.h_maps) (void) hipHostFree(c->chain.h_maps);
-    if (c->chain.d_est) (void) hipFree(c->chain.d_est);
-    if (c->chain.h_est) (void) hipHostFree(c->chain.h_est);
-    if (c->chain.d_c_before) (void) hipFree(c->chain.d_c_before);
-    if (c->chain.t0) (void) hipEventDestroy(c->chain.t0);
-    if (c->chain.t1) (void) hipEventDestroy(c->chain.t1);
-    if (c->chain.landed) (void) hipEventDestroy(c->chain.landed);
-    for (auto &e : c->chain.walked) if (e) (void) hipEventDestroy(e);
-    if (c->chain.back) (void) hipStreamDestroy(c->chain.back);
-    if (c->chain.stream) (void) hipStreamDestroy(c->chain.stream);
-    if (c->noise.d_tab) (void) hipFree(c->noise.d_tab);
-    if (c->level.d_zero) (void) hipFree(c->level.d_zero);
-    if (c->stream) (void) hipStreamDestroy(c->stream);
-    if (c->stream2) (void) hipStreamDestroy(c->stream2);
-    if (c->up_stream) (void) hipStreamDestroy(c->up_stream);
     delete c;
 }
 
@@ -243,19 +201,14 @@ static int set_descriptors_impl(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblo
     // the launch from kSets sets ago may still be reading this buffer (and its staging may still be
     // the source of an upload): wait for exactly that, not for the whole device
     { int wrc = wait_idle(nb); if (wrc) return wrc; }
-    if (n > nb.hcap) {
-        if (nb.h) HIP_TRY(hipHostFree(nb.h));
-        nb.h = nullptr; nb.hcap = 0;
-        HIP_TRY(hipHostMalloc((void **) &nb.h, n * sizeof(gpsiq_qchan_t), hipHostMallocDefault));
-        nb.hcap = n;
-    }
+    HIP_TRY(nb.h.reserve(n));
     // Device copy is compacted per block: active channels first, unused slots (zeroed)
     // after them.  The sum over channels is commutative modulo 2^16, so slot order is free.
     // Validation + compaction run on host threads straight into the page-locked staging buffer,
     // BEFORE anything resident is touched: a rejected set leaves the previous one in place.
     struct PJob { const gpsiq_qchan_t *q; gpsiq_qchan_t *out; uint8_t *active; int nchan; uint64_t mx; int max_active; long max_amp; int rc; size_t bad; };
     nb.active_per_block.resize((size_t) nblocks);
-    PJob pj = {q, nb.h, nb.active_per_block.data(), nchan, 0, 0, 0, GPSIQ_OK, 0};
+    PJob pj = {q, nb.h.get(), nb.active_per_block.data(), nchan, 0, 0, 0, GPSIQ_OK, 0};
     const bool trace = std::getenv("GPSIQ_TRACE") != nullptr;
     const double t0 = trace ? wall_ms() : 0.0;
     parallel_for(nblocks, 0, 128, [](void *p, int b0, int b1) {
@@ -289,45 +242,27 @@ static int set_descriptors_impl(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblo
         for (long cur = j.max_amp; max_amp > cur && !__sync_bool_compare_and_swap(&j.max_amp, cur, max_amp); cur = j.max_amp) {}
     }, &pj);
     if (pj.rc != GPSIQ_OK) return fail(pj.rc, "descriptor %zu outside the NCO format (prn %u)", pj.bad, q[pj.bad].prn);
-    const size_t need = n ? n : 1;
-    if (need > nb.cap) {
-        if (nb.d) HIP_TRY(hipFree(nb.d));
-        nb.d = nullptr; nb.cap = 0;
-        HIP_TRY(hipMalloc((void **) &nb.d, need * sizeof(gpsiq_qchan_t)));
-        nb.cap = need;
-    }
+    HIP_TRY(nb.d.reserve(n ? n : 1));
     if (npatch > 0) {                                   // before anything resident is touched, like the descriptors
         const int prc = check_patches(nb, nblocks, patches, npatch);
         if (prc) return prc;
-        if ((size_t) npatch > nb.patch_cap) {
-            if (nb.d_patch) HIP_TRY(hipFree(nb.d_patch));
-            nb.d_patch = nullptr; nb.patch_cap = 0;
-            const size_t cap = (size_t) npatch < 256 ? 256 : (size_t) npatch;
-            HIP_TRY(hipMalloc((void **) &nb.d_patch, cap * sizeof(gpsiq_patch_t)));
-            nb.patch_cap = cap;
-        }
-        if ((size_t) npatch > nb.h_patch_cap) {
-            if (nb.h_patch) HIP_TRY(hipHostFree(nb.h_patch));
-            nb.h_patch = nullptr; nb.h_patch_cap = 0;
-            const size_t cap = (size_t) npatch < 256 ? 256 : (size_t) npatch;
-            HIP_TRY(hipHostMalloc((void **) &nb.h_patch, cap * sizeof(gpsiq_patch_t), hipHostMallocDefault));
-            nb.h_patch_cap = cap;
-        }
-        std::memcpy(nb.h_patch, patches, (size_t) npatch * sizeof(gpsiq_patch_t));
+        HIP_TRY(nb.d_patch.reserve(gpsiq_patch_room((size_t) npatch)));
+        HIP_TRY(nb.h_patch.reserve(gpsiq_patch_room((size_t) npatch)));
+        std::memcpy(nb.h_patch.get(), patches, (size_t) npatch * sizeof(gpsiq_patch_t));
     }
     if (n) {
         const double t1 = trace ? wall_ms() : 0.0;
         // on the context's upload stream (non-blocking, nothing else ever queued on it): overlaps whatever the caller's
         // streams and the context's own kernels are doing
-        hipError_t e = hipMemcpyAsync(nb.d, nb.h, n * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, c->up_stream);
+        hipError_t e = hipMemcpyAsync(nb.d.get(), nb.h.get(), n * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, c->up_stream.get());
         if (e == hipSuccess && npatch > 0)
-            e = hipMemcpyAsync(nb.d_patch, nb.h_patch, (size_t) npatch * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->up_stream);
+            e = hipMemcpyAsync(nb.d_patch.get(), nb.h_patch.get(), (size_t) npatch * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->up_stream.get());
         if (e == hipSuccess && no_wait) {
-            if (!nb.uploaded) e = hipEventCreateWithFlags(&nb.uploaded, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(nb.uploaded, c->up_stream);
+            e = nb.uploaded.ensure();
+            if (e == hipSuccess) e = hipEventRecord(nb.uploaded.get(), c->up_stream.get());
             if (e == hipSuccess) nb.upload_pending = true;
         } else if (e == hipSuccess) {
-            e = hipStreamSynchronize(c->up_stream);
+            e = hipStreamSynchronize(c->up_stream.get());
         }
         if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "descriptor upload: %s", hipGetErrorString(e));
         if (trace)
@@ -335,7 +270,7 @@ static int set_descriptors_impl(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblo
                          nblocks, t1 - t0, no_wait ? "queued" : "done", wall_ms() - t1);
     }
     c->cur = next;
-    c->d_desc = nb.d;
+    c->d_desc = nb.d.get();
     c->nblocks = nblocks; c->nchan = nchan; c->cls = {pj.mx, pj.max_active, pj.max_amp};
     nb.npatch = n ? npatch : 0;
     return GPSIQ_OK;
@@ -358,15 +293,9 @@ int gpsiq_set_patches(gpsiq_ctx_t *c, const gpsiq_patch_t *patches, int n)
     if (n == 0) return GPSIQ_OK;                      // launches in flight took their count with them
     // launches of THIS set may still be applying the list that is replaced (the other buffer's launches have their own)
     { int wrc = wait_idle(cb); if (wrc) return wrc; }
-    if ((size_t) n > cb.patch_cap) {
-        if (cb.d_patch) HIP_TRY(hipFree(cb.d_patch));
-        cb.d_patch = nullptr; cb.patch_cap = 0;
-        const size_t cap = (size_t) n < 256 ? 256 : (size_t) n;
-        HIP_TRY(hipMalloc((void **) &cb.d_patch, cap * sizeof(gpsiq_patch_t)));
-        cb.patch_cap = cap;
-    }
-    hipError_t e = hipMemcpyAsync(cb.d_patch, patches, (size_t) n * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->up_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->up_stream);
+    HIP_TRY(cb.d_patch.reserve(gpsiq_patch_room((size_t) n)));
+    hipError_t e = hipMemcpyAsync(cb.d_patch.get(), patches, (size_t) n * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->up_stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->up_stream.get());
     if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "patch upload: %s", hipGetErrorString(e));
     cb.npatch = n;
     return GPSIQ_OK;
@@ -389,18 +318,13 @@ static int launch_on(gpsiq_ctx *c, int v, int block0, int nblocks, int nsamp, in
 {
     const gpsiq::noise::Launch nz = gpsiq_noise_at(c, nbase);
     const size_t need = variant_scratch_bytes(v, nsamp, nblocks);
-    if (need > c->scratch_cap) {
-        // growing is rare (the first launch of a shape); hipFree waits for whatever still uses the old buffer
-        if (c->d_scratch) HIP_TRY(hipFree(c->d_scratch));
-        c->d_scratch = nullptr; c->scratch_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_scratch, need));
-        c->scratch_cap = need;
-    }
-    if (c->buf[c->cur].upload_pending) HIP_TRY(hipStreamWaitEvent(s, c->buf[c->cur].uploaded, 0));    // a set staged without waiting
-    hipError_t e = launch_variant(v, c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, s,
-                                  c->cls, need ? c->d_scratch : nullptr, nz);
+    // growing is rare (the first launch of a shape); the free inside reserve() waits for whatever still uses the old buffer
+    HIP_TRY(c->d_scratch.reserve(need));
+    if (c->buf[c->cur].upload_pending) HIP_TRY(hipStreamWaitEvent(s, c->buf[c->cur].uploaded.get(), 0));    // a set staged without waiting
+    hipError_t e = launch_variant(v, c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab.get(), s,
+                                  c->cls, need ? c->d_scratch.get() : nullptr, nz);
     if (e == hipSuccess && c->buf[c->cur].npatch)
-        e = launch_patches(c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab, c->buf[c->cur].d_patch,
+        e = launch_patches(c->d_desc, c->nchan, nsamp, sample_size, dst, stride, block0, nblocks, c->d_tab.get(), c->buf[c->cur].d_patch.get(),
                            c->buf[c->cur].npatch, s, nz);
     if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "launch: %s", hipGetErrorString(e));
     if (nblocks > 0 && nsamp > 0) return mark_use(c->buf[c->cur], s);
@@ -442,18 +366,16 @@ int gpsiq_time_launches(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int 
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     const int v = pick_variant(c, variant);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     float ms = 0.f;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, s);
+    hipError_t e = e0.ensure(hipEventDefault);
+    if (e == hipSuccess) e = e1.ensure(hipEventDefault);
+    if (e == hipSuccess) e = hipEventRecord(e0.get(), s);
     for (int i = 0; i < iters && e == hipSuccess && rc == GPSIQ_OK; ++i)
         rc = launch_on(c, v, block0, nblocks, nsamp, sample_size, dst, block_stride_bytes, s, c->noise.next_block);
-    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventRecord(e1, s);
-    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventSynchronize(e1);
-    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void) hipEventDestroy(e0);                  // on every path
-    if (e1) (void) hipEventDestroy(e1);
+    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventRecord(e1.get(), s);
+    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventSynchronize(e1.get());
+    if (e == hipSuccess && rc == GPSIQ_OK) e = hipEventElapsedTime(&ms, e0.get(), e1.get());
     if (rc != GPSIQ_OK) return rc;
     if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "timing: %s", hipGetErrorString(e));
     *ms_per_launch = ms / (float) iters;
@@ -474,11 +396,7 @@ int PieceOut::begin(gpsiq_ctx *ctx, int nblocks_, int nsamp, int sample_size, vo
     direct = dst_is_device && stride == blk_bytes && !((uintptr_t) dst & 3);
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = stride * (size_t) nblocks;
-    if (direct || bytes <= c->out_cap) return GPSIQ_OK;       // (sized before anything is queued)
-    if (c->d_out) HIP_TRY(hipFree(c->d_out));
-    c->d_out = nullptr; c->out_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_out, bytes));
-    c->out_cap = bytes;
+    if (!direct) HIP_TRY(c->d_out.reserve(bytes));            // (sized before anything is queued)
     return GPSIQ_OK;
 }
 
@@ -496,9 +414,9 @@ int PieceOut::rendered(int b0, int nb, hipStream_t s)
 {
     if (direct) return GPSIQ_OK;
     const int k = copies++ & 1;
-    hipError_t e = hipEventRecord(c->chunk_done[k], s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream[k], c->chunk_done[k], 0);
-    if (e == hipSuccess) e = copy_rows(*this, b0, nb, c->copy_stream[k]);
+    hipError_t e = hipEventRecord(c->chunk_done[k].get(), s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream[k].get(), c->chunk_done[k].get(), 0);
+    if (e == hipSuccess) e = copy_rows(*this, b0, nb, c->copy_stream[k].get());
     return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "piece copy: %s", hipGetErrorString(e));
 }
 
@@ -516,8 +434,8 @@ int PieceOut::again(hipStream_t s, const std::vector<gpsiq_patch_t> &patches)
     if (direct || patches.empty()) return GPSIQ_OK;
     hipError_t e = hipSuccess;
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipEventRecord(c->chunk_done[k], c->copy_stream[k]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->chunk_done[k], 0);
+        e = hipEventRecord(c->chunk_done[k].get(), c->copy_stream[k].get());
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->chunk_done[k].get(), 0);
     }
     size_t touched = 0;
     for (size_t k = 0; k < patches.size(); ++k) touched += k == 0 || patches[k].block != patches[k - 1].block;
@@ -535,11 +453,11 @@ int PieceOut::finish(const char *label, int rc)
     if (!c) return rc;
     (void) hipSetDevice(c->device);
     hipError_t e = hipSuccess;
-    for (hipStream_t s : {c->copy_stream[0], c->copy_stream[1], c->stream, c->stream2})
+    for (hipStream_t s : {c->copy_stream[0].get(), c->copy_stream[1].get(), c->stream.get(), c->stream2.get()})
         { const hipError_t d = hipStreamSynchronize(s); if (e == hipSuccess) e = d; }
     // every launch waited for its set's upload on the device and has finished; a set that was staged but never launched on (an
     // error in between) may still be uploading: the upload stream is drained too before the flags are dropped
-    const hipError_t u = hipStreamSynchronize(c->up_stream);
+    const hipError_t u = hipStreamSynchronize(c->up_stream.get());
     if (e == hipSuccess && u == hipSuccess)
         for (auto &b : c->buf) b.upload_pending = false;
     if (rc != GPSIQ_OK) return rc;
@@ -563,13 +481,13 @@ static int run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nbloc
     rc = out.begin(c, nblocks, nsamp, sample_size, dst, dst_is_device);
     const int chunk = d2h_chunk_blocks(out.stride, piece_blocks_env());
     if (dst_is_device || chunk <= 0 || nblocks <= chunk) {
-        if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nblocks, nsamp, sample_size, out.target(0), out.stride, c->stream, kAuto, nbase);
-        if (rc == GPSIQ_OK) rc = out.whole(c->stream);
+        if (rc == GPSIQ_OK) rc = launch_abs(c, 0, nblocks, nsamp, sample_size, out.target(0), out.stride, c->stream.get(), kAuto, nbase);
+        if (rc == GPSIQ_OK) rc = out.whole(c->stream.get());
     } else
         for (int b0 = 0; b0 < nblocks && rc == GPSIQ_OK; b0 += chunk) {
             const int nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-            rc = launch_abs(c, b0, nb, nsamp, sample_size, out.target(b0), out.stride, c->stream, kAuto, nbase);
-            if (rc == GPSIQ_OK) rc = out.rendered(b0, nb, c->stream);
+            rc = launch_abs(c, b0, nb, nsamp, sample_size, out.target(b0), out.stride, c->stream.get(), kAuto, nbase);
+            if (rc == GPSIQ_OK) rc = out.rendered(b0, nb, c->stream.get());
         }
     return out.finish("batch pieces", rc);
 }
@@ -612,40 +530,7 @@ static double rate_kernel()
 }
 static double rate_chain_us() { return 2.2; }      // microseconds per block and channel of the serial walk on one host thread
 
-// ---- the carrier chain on the device -------------------------------------------------------------------------------
-static int chain_reserve(gpsiq_ctx *c, size_t n)
-{
-    gpsiq_ctx::Chain &k = c->chain;
-    if (!k.stream) {
-        // (equal priorities: with the synthesis stream above the chain's, the second launch's maps came back late -- 0.98 ms
-        // instead of 0.78 -- and the pieces behind the head waited for them: 2.6 ms per call instead of 2.4, profiles/r05_chain_ab.txt)
-        HIP_TRY(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&k.back, hipStreamNonBlocking));
-        for (auto &e : k.walked) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&k.t0));
-        HIP_TRY(hipEventCreate(&k.t1));
-        HIP_TRY(hipEventCreateWithFlags(&k.landed, hipEventDisableTiming));
-        HIP_TRY(hipMalloc((void **) &k.d_est, (kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN * sizeof(gpsiq_chain_est_t)));
-        HIP_TRY(hipHostMalloc((void **) &k.h_est, (kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN * sizeof(gpsiq_chain_est_t), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **) &k.d_c_before, kEvalMaxPieces * GPSIQ_MAX_CHAN * sizeof(double)));
-    }
-    if (n <= k.cap) return GPSIQ_OK;
-    if (k.d_in) (void) hipFree(k.d_in);
-    if (k.h_in) (void) hipHostFree(k.h_in);
-    if (k.d_prep) (void) hipFree(k.d_prep);
-    if (k.d_maps) (void) hipFree(k.d_maps);
-    if (k.h_maps) (void) hipHostFree(k.h_maps);
-    k.d_in = nullptr; k.h_in = nullptr; k.d_prep = nullptr; k.d_maps = nullptr; k.h_maps = nullptr; k.cap = 0;
-    const size_t cap = n + n / 4 + 256;
-    HIP_TRY(hipMalloc((void **) &k.d_in, cap * sizeof(gpsiq_chain_in_t)));
-    HIP_TRY(hipHostMalloc((void **) &k.h_in, cap * sizeof(gpsiq_chain_in_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&k.d_prep, cap * 32));
-    HIP_TRY(hipMalloc((void **) &k.d_maps, cap * sizeof(gpsiq_chain_map_t)));
-    HIP_TRY(hipHostMalloc((void **) &k.h_maps, cap * sizeof(gpsiq_chain_map_t), hipHostMallocDefault));
-    k.cap = cap;
-    return GPSIQ_OK;
-}
-
+// ---- the carrier chain on the device (its buffers, streams and events: gpsiq_ctx::Chain::reserve) ----------------------------
 // Level 1 of the chain for blocks [b0, b0 + nb) of the inputs staged in c->chain.h_in, queued on the chain stream without
 // waiting: upload, two kernels, the maps back into c->chain.h_maps (same rows), `landed` recorded behind them.  part 0 starts
 // from `start` (host, may be null: the timeline begins here); part 1 continues where part 0's scan ended, on the device.
@@ -657,32 +542,33 @@ static int chain_queue(gpsiq_ctx *c, int part, int b0, int nb, int nchan, double
         max_stretches = 32;
         if (const char *e = std::getenv("GPSIQ_CHAIN_STRETCHES")) { const int v = std::atoi(e); if (v >= 1 && v <= 32) max_stretches = v; }
     }
-    HIP_TRY(hipMemcpyAsync(k.d_in + off, k.h_in + off, n * sizeof(gpsiq_chain_in_t), hipMemcpyHostToDevice, k.stream));
+    HIP_TRY(hipMemcpyAsync(k.d_in.get() + off, k.h_in.get() + off, n * sizeof(gpsiq_chain_in_t), hipMemcpyHostToDevice, k.stream.get()));
+    gpsiq_chain_est_t *d_est = k.d_est.get(), *h_est = k.h_est.get();
     const gpsiq_chain_est_t *d_start = nullptr;
-    if (part == 1) d_start = k.d_est + GPSIQ_MAX_CHAN;
+    if (part == 1) d_start = d_est + GPSIQ_MAX_CHAN;
     else if (start) {
-        std::memcpy(k.h_est, start, (size_t) nchan * sizeof(gpsiq_chain_est_t));
-        HIP_TRY(hipMemcpyAsync(k.d_est, k.h_est, (size_t) nchan * sizeof(gpsiq_chain_est_t), hipMemcpyHostToDevice, k.stream));
-        d_start = k.d_est;
+        std::memcpy(h_est, start, (size_t) nchan * sizeof(gpsiq_chain_est_t));
+        HIP_TRY(hipMemcpyAsync(d_est, h_est, (size_t) nchan * sizeof(gpsiq_chain_est_t), hipMemcpyHostToDevice, k.stream.get()));
+        d_start = d_est;
     }
-    if (part == 0) HIP_TRY(hipEventRecord(k.t0, k.stream));
-    HIP_TRY(launch_chain(k.d_in + off, (int) sizeof(gpsiq_chain_in_t), nb, nchan, 1.0 / fs, nsamp, d_start, max_stretches, static_cast<char *>(k.d_prep) + off * 32,
-                         k.d_c_before + part * GPSIQ_MAX_CHAN, k.d_est + (part + 1) * GPSIQ_MAX_CHAN, k.d_maps + off, k.stream));
-    HIP_TRY(hipEventRecord(k.t1, k.stream));
+    if (part == 0) HIP_TRY(hipEventRecord(k.t0.get(), k.stream.get()));
+    HIP_TRY(launch_chain(k.d_in.get() + off, (int) sizeof(gpsiq_chain_in_t), nb, nchan, 1.0 / fs, nsamp, d_start, max_stretches, k.d_prep.get() + off * k.kPrepBytes,
+                         k.d_c_before.get() + part * GPSIQ_MAX_CHAN, d_est + (part + 1) * GPSIQ_MAX_CHAN, k.d_maps.get() + off, k.stream.get()));
+    HIP_TRY(hipEventRecord(k.t1.get(), k.stream.get()));
     // the maps' way back on a stream of its own: the next launch's kernels follow these at once (a callback queued between
     // them held the second launch up by ~0.1 ms)
-    HIP_TRY(hipEventRecord(k.walked[part], k.stream));
-    HIP_TRY(hipStreamWaitEvent(k.back, k.walked[part], 0));
-    HIP_TRY(hipMemcpyAsync(k.h_maps + off, k.d_maps + off, n * sizeof(gpsiq_chain_map_t), hipMemcpyDeviceToHost, k.back));
-    HIP_TRY(hipMemcpyAsync(k.h_est + (part + 1) * GPSIQ_MAX_CHAN, k.d_est + (part + 1) * GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t),
-                           hipMemcpyDeviceToHost, k.back));
-    HIP_TRY(hipEventRecord(k.landed, k.back));
+    HIP_TRY(hipEventRecord(k.walked[part].get(), k.stream.get()));
+    HIP_TRY(hipStreamWaitEvent(k.back.get(), k.walked[part].get(), 0));
+    HIP_TRY(hipMemcpyAsync(k.h_maps.get() + off, k.d_maps.get() + off, n * sizeof(gpsiq_chain_map_t), hipMemcpyDeviceToHost, k.back.get()));
+    HIP_TRY(hipMemcpyAsync(h_est + (part + 1) * GPSIQ_MAX_CHAN, d_est + (part + 1) * GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t),
+                           hipMemcpyDeviceToHost, k.back.get()));
+    HIP_TRY(hipEventRecord(k.landed.get(), k.back.get()));
     return GPSIQ_OK;
 }
 
 static int chain_drain(gpsiq_ctx *c)
 {
-    const hipError_t a = hipStreamSynchronize(c->chain.stream), b = hipStreamSynchronize(c->chain.back);
+    const hipError_t a = hipStreamSynchronize(c->chain.stream.get()), b = hipStreamSynchronize(c->chain.back.get());
     if (a != hipSuccess || b != hipSuccess) return fail(GPSIQ_E_DEVICE, "carrier chain, level 1: %s", hipGetErrorString(a != hipSuccess ? a : b));
     return GPSIQ_OK;
 }
@@ -696,8 +582,8 @@ static int chain_maps_staged(gpsiq_ctx *c, int nblocks, int nchan, double fs, in
     if (rc) { (void) chain_drain(c); return rc; }
     rc = chain_drain(c);
     if (rc) return rc;
-    (void) hipEventElapsedTime(&k.last_ms, k.t0, k.t1);
-    if (end) std::memcpy(end, k.h_est + GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t));
+    (void) hipEventElapsedTime(&k.last_ms, k.t0.get(), k.t1.get());
+    if (end) std::memcpy(end, k.h_est.get() + GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t));
     return GPSIQ_OK;
 }
 
@@ -711,12 +597,12 @@ extern "C" int gpsiq_chain_maps_device(gpsiq_ctx_t *c, const gpsiq_chain_in_t *i
     if (nblocks == 0) return GPSIQ_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t) nblocks * (size_t) nchan;
-    int rc = chain_reserve(c, n);
+    int rc = c->chain.reserve(n);
     if (rc) return rc;
-    std::memcpy(c->chain.h_in, in, n * sizeof(gpsiq_chain_in_t));
+    std::memcpy(c->chain.h_in.get(), in, n * sizeof(gpsiq_chain_in_t));
     rc = chain_maps_staged(c, nblocks, nchan, fs, nsamp, start, max_stretches, end);
     if (rc) return rc;
-    std::memcpy(maps, c->chain.h_maps, n * sizeof(gpsiq_chain_map_t));
+    std::memcpy(maps, c->chain.h_maps.get(), n * sizeof(gpsiq_chain_map_t));
     if (kernel_ms) *kernel_ms = c->chain.last_ms;
     return GPSIQ_OK;
 }
@@ -741,7 +627,7 @@ static bool chain_on_device(int nblocks, int nsamp, int nchan)
 // of each -- memory-bound, so spread over the pool
 static void chain_stage_inputs(gpsiq_ctx *c, const gpsiq_chan_t *ch, int b0, int b1, int nchan)
 {
-    struct Job { const gpsiq_chan_t *ch; gpsiq_chain_in_t *out; } job = {ch + (size_t) b0 * nchan, c->chain.h_in + (size_t) b0 * nchan};
+    struct Job { const gpsiq_chan_t *ch; gpsiq_chain_in_t *out; } job = {ch + (size_t) b0 * nchan, c->chain.h_in.get() + (size_t) b0 * nchan};
     parallel_for((b1 - b0) * nchan, (b1 - b0) * nchan >= 8192 ? 0 : 1, 2048, [](void *p, int k0, int k1) {
         const Job &j = *static_cast<Job *>(p);
         gpsiq_chain_inputs(j.ch + k0, k1 - k0, j.out + k0);
@@ -790,7 +676,7 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
     double t_chain[3] = {};
     int head = nblocks;
     if (dev_chain) {
-        rc = chain_reserve(c, (size_t) nblocks * (size_t) nchan);
+        rc = c->chain.reserve((size_t) nblocks * (size_t) nchan);
         if (rc) return rc;
         head = ref_head(ends, nblocks, nsamp, nchan, rate_kernel());
     }
@@ -806,14 +692,14 @@ static int generate_reference(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks,
         l->w->release_maps(l->upto);
     };
     if (dev_chain) {
-        w.in = c->chain.h_in; w.maps = c->chain.h_maps; w.maps_upto.store(0);
+        w.in = c->chain.h_in.get(); w.maps = c->chain.h_maps.get(); w.maps_upto.store(0);
         chain_stage_inputs(c, ch, 0, head, nchan);
         rc = chain_queue(c, 0, 0, head, nchan, fs, nsamp, nullptr, 0);
-        if (rc == GPSIQ_OK && hipLaunchHostFunc(c->chain.back, on_landed, &landed[0]) != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "hipLaunchHostFunc");
+        if (rc == GPSIQ_OK && hipLaunchHostFunc(c->chain.back.get(), on_landed, &landed[0]) != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "hipLaunchHostFunc");
         if (rc == GPSIQ_OK && head < nblocks) {
             chain_stage_inputs(c, ch, head, nblocks, nchan);                               // under the head's kernels
             rc = chain_queue(c, 1, head, nblocks - head, nchan, fs, nsamp, nullptr, 0);
-            if (rc == GPSIQ_OK && hipLaunchHostFunc(c->chain.back, on_landed, &landed[1]) != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "hipLaunchHostFunc");
+            if (rc == GPSIQ_OK && hipLaunchHostFunc(c->chain.back.get(), on_landed, &landed[1]) != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "hipLaunchHostFunc");
         }
         if (rc) { (void) chain_drain(c); return rc; }
         if (trace) t_chain[0] = wall_ms() - t0;
@@ -894,7 +780,7 @@ int gpsiq_generate_block(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan, int 
     if (rc) return rc;
     if (nsamp > 0) {
         gpsiq_ctx::AsyncSlot &a = c->aslot[slot];
-        const hipError_t e = hipEventSynchronize(a.done);
+        const hipError_t e = hipEventSynchronize(a.done.get());
         a.busy = false;
         if (e != hipSuccess) {
             std::memcpy(c->carry, carry0, sizeof carry0);
@@ -933,11 +819,11 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
         }
     }
     gpsiq_ctx::AsyncSlot &a = c->aslot[c->anext];
-    if (a.busy) { HIP_TRY(hipEventSynchronize(a.done)); a.busy = false; }     // the ring is full: wait for its oldest block
+    if (a.busy) { HIP_TRY(hipEventSynchronize(a.done.get())); a.busy = false; }     // the ring is full: wait for its oldest block
     // each piece on its own: a call that failed half-way must not leave a slot that looks complete
-    if (!a.d) HIP_TRY(hipMalloc((void **) &a.d, GPSIQ_MAX_CHAN * sizeof(gpsiq_qchan_t)));
-    if (!a.h) HIP_TRY(hipHostMalloc((void **) &a.h, GPSIQ_MAX_CHAN * sizeof(gpsiq_qchan_t), hipHostMallocDefault));
-    if (!a.done) HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
+    HIP_TRY(a.d.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(a.h.reserve(GPSIQ_MAX_CHAN));
+    HIP_TRY(a.done.ensure());
     // compact (active channels first) and take the launch parameters, as gpsiq_set_descriptors does for a batch
     int na = 0;
     SynthClass cls;
@@ -951,38 +837,28 @@ int gpsiq_generate_block_async(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nchan
     for (int i = na; i < nchan; ++i) std::memset(&a.h[i], 0, sizeof(gpsiq_qchan_t));
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size;
     const size_t stride = (blk_bytes + 15) & ~(size_t) 15;
-    if (stride > a.out_cap) {
-        if (a.out) HIP_TRY(hipFree(a.out));
-        a.out = nullptr; a.out_cap = 0;
-        HIP_TRY(hipMalloc(&a.out, stride ? stride : 16));
-        a.out_cap = stride ? stride : 16;
-    }
-    if (!patches.empty() && patches.size() > a.patch_cap) {      // the slot is idle here (its event was waited for above)
-        // each pointer is forgotten before its free can fail: a second call (or gpsiq_destroy) must not free it again
-        { gpsiq_patch_t *dp = a.d_patch, *hp = a.h_patch; a.d_patch = a.h_patch = nullptr; a.patch_cap = 0;
-          const hipError_t f0 = dp ? hipFree(dp) : hipSuccess, f1 = hp ? hipHostFree(hp) : hipSuccess;
-          if (f0 != hipSuccess || f1 != hipSuccess) return fail(GPSIQ_E_DEVICE, "patch staging: %s", hipGetErrorString(f0 != hipSuccess ? f0 : f1)); }
-        const size_t cap = patches.size() < 256 ? 256 : patches.size();
-        HIP_TRY(hipMalloc((void **) &a.d_patch, cap * sizeof(gpsiq_patch_t)));
-        HIP_TRY(hipHostMalloc((void **) &a.h_patch, cap * sizeof(gpsiq_patch_t), hipHostMallocDefault));
-        a.patch_cap = cap;
+    if (stride > a.out.cap()) HIP_TRY(a.out.reserve(stride ? stride : 16));
+    if (!patches.empty()) {                                      // the slot is idle here (its event was waited for above)
+        HIP_TRY(a.d_patch.reserve(gpsiq_patch_room(patches.size())));
+        HIP_TRY(a.h_patch.reserve(gpsiq_patch_room(patches.size())));
     }
     if (nsamp > 0) {
         cls.max_active = na;
         // once the first copy is queued a failure must not return with work in flight on the slot's page-locked staging (the next
         // call would rewrite it under the copy): the stream is drained first
-        hipError_t e = hipMemcpyAsync(a.d, a.h, (size_t) nchan * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, c->stream);
+        hipStream_t s = c->stream.get();
+        hipError_t e = hipMemcpyAsync(a.d.get(), a.h.get(), (size_t) nchan * sizeof(gpsiq_qchan_t), hipMemcpyHostToDevice, s);
         const gpsiq::noise::Launch nz = gpsiq_noise_at(c, c->noise.next_block);
-        if (e == hipSuccess) e = launch_variant(auto_variant(cls.max_code_step), a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, c->stream, cls, nullptr, nz);
+        if (e == hipSuccess) e = launch_variant(auto_variant(cls.max_code_step), a.d.get(), nchan, nsamp, sample_size, a.out.get(), stride, 0, 1, c->d_tab.get(), s, cls, nullptr, nz);
         if (e == hipSuccess && !patches.empty()) {
-            std::memcpy(a.h_patch, patches.data(), patches.size() * sizeof(gpsiq_patch_t));
-            e = hipMemcpyAsync(a.d_patch, a.h_patch, patches.size() * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = launch_patches(a.d, nchan, nsamp, sample_size, a.out, stride, 0, 1, c->d_tab, a.d_patch, (int) patches.size(), c->stream, nz);
+            std::memcpy(a.h_patch.get(), patches.data(), patches.size() * sizeof(gpsiq_patch_t));
+            e = hipMemcpyAsync(a.d_patch.get(), a.h_patch.get(), patches.size() * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = launch_patches(a.d.get(), nchan, nsamp, sample_size, a.out.get(), stride, 0, 1, c->d_tab.get(), a.d_patch.get(), (int) patches.size(), s, nz);
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, a.out, blk_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(a.done, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, a.out.get(), blk_bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(a.done.get(), s);
         if (e != hipSuccess) {
-            (void) hipStreamSynchronize(c->stream);
+            (void) hipStreamSynchronize(s);
             return fail(GPSIQ_E_DEVICE, "block: %s", hipGetErrorString(e));
         }
         a.busy = true;
@@ -1006,7 +882,7 @@ int gpsiq_wait(gpsiq_ctx_t *c)
 {
     if (!c) return fail(GPSIQ_E_ARG, "null context");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     for (auto &a : c->aslot) a.busy = false;
     return GPSIQ_OK;
 }
@@ -1167,8 +1043,7 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
         rc = generate_batch_multi(ctx, ndev, ch, nblocks, nchan, nsamp, fs, sample_size, host_dst, dev_dst, carr_phase_out);
     if (rc == GPSIQ_OK) ctx[0]->noise.next_block += (uint64_t) nblocks;
     for (int i = 1; i < ndev; ++i) {
-        ctx[i]->level.mult = own_level[(size_t) i].mult;           // (the zero table stays: it belongs to the context's device)
-        ctx[i]->level.qmax = own_level[(size_t) i].qmax;
+        ctx[i]->level = own_level[(size_t) i];
         const gpsiq_ctx::Noise &o = own[(size_t) i];
         if (ctx[i]->noise.seed != o.seed || ctx[i]->noise.sigma != o.sigma) {
             char err[400];
@@ -1261,14 +1136,14 @@ static int generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_c
         const bool dev_chain = chain_on_device(nblocks, nsamp, nchan);
         int crc = GPSIQ_OK;
         if (dev_chain) {
-            crc = hipSetDevice(c0->device) == hipSuccess ? chain_reserve(c0, (size_t) nblocks * (size_t) nchan) : fail(GPSIQ_E_DEVICE, "hipSetDevice");
+            crc = hipSetDevice(c0->device) == hipSuccess ? c0->chain.reserve((size_t) nblocks * (size_t) nchan) : fail(GPSIQ_E_DEVICE, "hipSetDevice");
             if (crc == GPSIQ_OK) {
                 chain_stage_inputs(c0, ch, 0, nblocks, nchan);
                 crc = chain_maps_staged(c0, nblocks, nchan, fs, nsamp, nullptr, 0, nullptr);
             }
         }
         RefWalk w(ch, nblocks, nchan, 1.0 / fs, nsamp, q.data(), nullptr, nullptr, ends);
-        if (dev_chain && crc == GPSIQ_OK) { w.in = c0->chain.h_in; w.maps = c0->chain.h_maps; }     // (a failed level 1: the serial walk)
+        if (dev_chain && crc == GPSIQ_OK) { w.in = c0->chain.h_in.get(); w.maps = c0->chain.h_maps.get(); }     // (a failed level 1: the serial walk)
         pthread_t wth;
         const bool threaded = pthread_create(&wth, nullptr, run_walk, &w) == 0;
         if (!threaded) w.run();
@@ -1375,9 +1250,9 @@ static int set_noise_impl(gpsiq_ctx *c, uint64_t seed, double sigma)
     if (sigma > 0.0) {
         gpsiq::noise::Entry tab[gpsiq::noise::kTabEntries];
         const long max_z = noise_table(sigma, tab);
-        if (!c->noise.d_tab) HIP_TRY(hipMalloc(&c->noise.d_tab, sizeof tab));
+        HIP_TRY(c->d_noise_tab.reserve(gpsiq::noise::kTabEntries));
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(c->noise.d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_noise_tab.get(), tab, sizeof tab, hipMemcpyHostToDevice));
         c->noise.max_z = max_z;
     } else {
         c->noise.max_z = 0;
@@ -1408,11 +1283,10 @@ int gpsiq_set_noise(gpsiq_ctx_t *c, const gpsiq_noise_t *nz)
 // ---- output level (include/gpsiq_rows.h; libgpsiq_rows.so's gpsiq_set_level arrives here through the plumbing entry "set_level") ----
 static int set_level_impl(gpsiq_ctx *c, uint32_t mult, int32_t qmax)
 {
-    if (mult && !c->level.d_zero) {
+    if (mult && !c->d_zero_tab.get()) {
         HIP_TRY(hipSetDevice(c->device));
-        const size_t bytes = sizeof(gpsiq::noise::Entry) * gpsiq::noise::kTabEntries;
-        HIP_TRY(hipMalloc(&c->level.d_zero, bytes));
-        HIP_TRY(hipMemset(c->level.d_zero, 0, bytes));
+        HIP_TRY(c->d_zero_tab.reserve(gpsiq::noise::kTabEntries));
+        HIP_TRY(hipMemset(c->d_zero_tab.get(), 0, sizeof(gpsiq::noise::Entry) * gpsiq::noise::kTabEntries));
         HIP_TRY(hipDeviceSynchronize());
     }
     c->level.mult = mult;
@@ -1463,7 +1337,7 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
 {
     gpsiq::noise::Launch nz;
     if (c->noise.sigma > 0.0) {
-        nz.tab = c->noise.d_tab;
+        nz.tab = c->d_noise_tab.get();
         nz.seed = c->noise.seed;
         nz.block = block;
         nz.max_z = c->noise.max_z;
@@ -1471,7 +1345,7 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
     if (c->level.mult) {
         nz.mult = c->level.mult;
         nz.qmax = c->level.qmax;
-        if (!nz.tab) { nz.tab = c->level.d_zero; nz.block = block; }     // noise off: the level kernels draw zeros
+        if (!nz.tab) { nz.tab = c->d_zero_tab.get(); nz.block = block; }     // noise off: the level kernels draw zeros
     }
     return nz;
 }
@@ -1480,7 +1354,6 @@ gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block)
 double gpsiq_wall_ms() { return wall_ms(); }
 int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b) { return wait_idle(b); }
 int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s) { return mark_use(b, s); }
-int gpsiq_chain_reserve(gpsiq_ctx *c, size_t n) { return chain_reserve(c, n); }
 double gpsiq_rate_kernel() { return rate_kernel(); }
 void gpsiq_note_kernel_rate(double channel_samples_per_s)
 {

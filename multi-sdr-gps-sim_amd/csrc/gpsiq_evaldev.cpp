@@ -47,63 +47,8 @@ SrcKind classify(const void *p, int device, const void **dev_ptr)
     return kSrcPageable;               // unregistered, managed, another device's: through the host
 }
 
-constexpr unsigned kPatchCap = 1u << 16, kHostCap = 1u << 13;
-
-int evd_reserve(gpsiq_ctx *c, size_t n, SrcKind kind, bool seeds)
-{
-    gpsiq_ctx::EvalDev &e = c->evd;
-    int rc = gpsiq_chain_reserve(c, n);
-    if (rc) return rc;
-    if (!e.eval_stream) {
-        // Chain and evaluation run BESIDE the synthesis, which floods the device with workgroups: their streams get the highest
-        // priority, so that the few workgroups of prepare / lanes / link / evaluation are dispatched as synthesis workgroups retire
-        // instead of behind all of them (the patches have to be there when the synthesis ends, not some time after it).
-        int least = 0, greatest = 0;
-        (void) hipDeviceGetStreamPriorityRange(&least, &greatest);
-        // (MI355X, 2.6 Msps, 2 000 blocks: 1.82 ms per call against 2.20 at equal priorities; 25 Msps: 1.54 against 2.61)
-        HIP_TRY(hipStreamCreateWithPriority(&e.eval_stream, hipStreamNonBlocking, greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&e.chain_stream, hipStreamNonBlocking, greatest));
-        HIP_TRY(hipEventCreate(&e.t_synth0));
-        HIP_TRY(hipEventCreate(&e.t_synth1));
-        for (auto &ev_ : e.linked) HIP_TRY(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-        for (auto &ev_ : e.evaluated) HIP_TRY(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e.joined, hipEventDisableTiming));
-        HIP_TRY(hipMalloc((void **) &e.d_ctrl, sizeof(EvalCtrl)));
-        HIP_TRY(hipHostMalloc((void **) &e.h_ctrl, (kEvalMaxPieces + 2) * sizeof(EvalCtrl), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **) &e.d_link, GPSIQ_MAX_CHAN * sizeof(LinkCarry)));
-        HIP_TRY(hipHostMalloc((void **) &e.h_link, GPSIQ_MAX_CHAN * sizeof(LinkCarry), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **) &e.d_fix, GPSIQ_MAX_CHAN * sizeof(FixedCarry)));
-        HIP_TRY(hipHostMalloc((void **) &e.h_fix, GPSIQ_MAX_CHAN * sizeof(FixedCarry), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **) &e.d_patches, kPatchCap * sizeof(gpsiq_patch_t)));
-        HIP_TRY(hipHostMalloc((void **) &e.h_patches, kPatchCap * sizeof(gpsiq_patch_t), hipHostMallocDefault));
-        e.patch_cap = kPatchCap;
-        HIP_TRY(hipMalloc((void **) &e.d_host, kHostCap * sizeof(EvalHostItem)));
-        HIP_TRY(hipHostMalloc((void **) &e.h_host, kHostCap * sizeof(EvalHostItem), hipHostMallocDefault));
-        e.host_cap = kHostCap;
-    }
-    if (n > e.cap) {
-        if (e.d_chan) (void) hipFree(e.d_chan);
-        if (e.h_chan) (void) hipHostFree(e.h_chan);
-        e.d_chan = nullptr; e.h_chan = nullptr; e.cap = 0;
-        const size_t cap = n + n / 4 + 256;
-        HIP_TRY(hipMalloc(&e.d_chan, cap * sizeof(ev::DChan)));
-        HIP_TRY(hipHostMalloc(&e.h_chan, cap * sizeof(ev::DChan), hipHostMallocDefault));
-        e.cap = cap;
-    }
-    if (kind == kSrcPinned && n > e.raw_cap) {
-        if (e.d_raw) (void) hipFree(e.d_raw);
-        e.d_raw = nullptr; e.raw_cap = 0;
-        HIP_TRY(hipMalloc((void **) &e.d_raw, (n + n / 4 + 16) * sizeof(gpsiq_chan_t)));
-        e.raw_cap = n + n / 4 + 16;
-    }
-    if (seeds && n > e.seeds_cap) {
-        if (e.d_seeds) (void) hipFree(e.d_seeds);
-        e.d_seeds = nullptr; e.seeds_cap = 0;
-        HIP_TRY(hipMalloc((void **) &e.d_seeds, (n + n / 4 + 16) * sizeof(double)));
-        e.seeds_cap = n + n / 4 + 16;
-    }
-    return GPSIQ_OK;
-}
+static_assert(sizeof(ev::DChan) == gpsiq_ctx::EvalDev::kChanBytes, "the rows d_chan / h_chan are sized for");
+constexpr unsigned kPatchCap = gpsiq_ctx::EvalDev::kPatchCap, kHostCap = gpsiq_ctx::EvalDev::kHostCap;
 
 // descriptors in pageable memory: cut down to ev::DChan on the pool, with the synthesis kernel's launch parameters on the way
 struct PackJob { const gpsiq_chan_t *ch; ev::DChan *out; const double *seeds; int nchan; double delt; uint64_t mx; int max_active; long max_amp; };
@@ -187,38 +132,6 @@ extern "C" void gpsiq_device_eval_stats(uint64_t out[6])
 
 extern "C" double gpsiq_device_eval_host_ms(const gpsiq_ctx_t *c) { return c ? c->evd.host_ms : 0.0; }
 
-void gpsiq_evaldev_destroy(gpsiq_ctx *c)
-{
-    gpsiq_ctx::EvalDev &e = c->evd;
-    if (e.d_chan) (void) hipFree(e.d_chan);
-    if (e.h_chan) (void) hipHostFree(e.h_chan);
-    if (e.d_raw) (void) hipFree(e.d_raw);
-    if (e.d_seeds) (void) hipFree(e.d_seeds);
-    if (e.d_ctrl) (void) hipFree(e.d_ctrl);
-    if (e.h_ctrl) (void) hipHostFree(e.h_ctrl);
-    if (e.d_link) (void) hipFree(e.d_link);
-    if (e.h_link) (void) hipHostFree(e.h_link);
-    if (e.d_fix) (void) hipFree(e.d_fix);
-    if (e.h_fix) (void) hipHostFree(e.h_fix);
-    if (e.d_patches) (void) hipFree(e.d_patches);
-    if (e.h_patches) (void) hipHostFree(e.h_patches);
-    if (e.d_slot) (void) hipFree(e.d_slot);
-    if (e.h_slot) (void) hipHostFree(e.h_slot);
-    if (e.d_col) (void) hipFree(e.d_col);
-    if (e.h_col) (void) hipHostFree(e.h_col);
-    if (e.h_items) (void) hipHostFree(e.h_items);
-    if (e.d_host) (void) hipFree(e.d_host);
-    if (e.h_host) (void) hipHostFree(e.h_host);
-    for (auto &ev_ : e.linked) if (ev_) (void) hipEventDestroy(ev_);
-    for (auto &ev_ : e.evaluated) if (ev_) (void) hipEventDestroy(ev_);
-    if (e.joined) (void) hipEventDestroy(e.joined);
-    if (e.t_synth0) (void) hipEventDestroy(e.t_synth0);
-    if (e.t_synth1) (void) hipEventDestroy(e.t_synth1);
-    if (e.eval_stream) (void) hipStreamDestroy(e.eval_stream);
-    if (e.chain_stream) (void) hipStreamDestroy(e.chain_stream);
-    e = gpsiq_ctx::EvalDev();
-}
-
 // how many entries the patch / host lists of a call may hold.  (-DGPSIQ_TEST_HOOKS: GPSIQ_TEST_LIST_CAP=n makes the lists n entries
 // short, so that a test can see what a call does when they overflow -- the whole call again on the host path.)
 static inline unsigned list_cap(unsigned cap)
@@ -258,7 +171,8 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     const double delt = 1.0 / fs;
     const void *dev_src = nullptr;
     const SrcKind kind = classify(ch, c->device, &dev_src);
-    int rc = evd_reserve(c, n, kind, seeds != nullptr);
+    int rc = c->chain.reserve(n);
+    if (rc == GPSIQ_OK) rc = e.reserve(n, kind == kSrcPinned, seeds != nullptr);
     if (rc) return rc;
     *handled = 1;
     __atomic_fetch_add(&g_evd_stats[0], 1, __ATOMIC_RELAXED);
@@ -287,18 +201,26 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     gpsiq_ctx::DescBuf &nb_ = c->buf[next];
     rc = gpsiq_wait_idle(nb_);
     if (rc) return rc;
-    if (n > nb_.cap) {
-        if (nb_.d) HIP_TRY(hipFree(nb_.d));
-        nb_.d = nullptr; nb_.cap = 0;
-        HIP_TRY(hipMalloc((void **) &nb_.d, n * sizeof(gpsiq_qchan_t)));
-        nb_.cap = n;
-    }
+    HIP_TRY(nb_.d.reserve(n));
 
     std::vector<int> ends;
     device_piece_ends(nblocks, nsamp, nchan, kind != kSrcDevice, reference, gpsiq_rate_kernel(), piece_blocks_env(), kEvalMaxPieces, &ends);
     const int npieces = (int) ends.size();
-    hipStream_t S = e.chain_stream, E = e.eval_stream;
-    ev::DChan *d_chan = static_cast<ev::DChan *>(e.d_chan), *h_chan = static_cast<ev::DChan *>(e.h_chan);
+    hipStream_t S = e.chain_stream.get(), E = e.eval_stream.get();
+    ev::DChan *d_chan = reinterpret_cast<ev::DChan *>(e.d_chan.get()), *h_chan = reinterpret_cast<ev::DChan *>(e.h_chan.get());
+    // the rest of what the call works in, under the names of its owners (reserved above, nothing grows before the repair)
+    gpsiq_qchan_t *const d_set = nb_.d.get();
+    const DeviceTables *const d_tab = c->d_tab.get();
+    gpsiq::EvalCtrl *const d_ctrl = e.d_ctrl.get(), *const h_ctrl = e.h_ctrl.get();
+    gpsiq::LinkCarry *const d_link = e.d_link.get(), *const h_link = e.h_link.get();
+    gpsiq::FixedCarry *const d_fix = e.d_fix.get(), *const h_fix = e.h_fix.get();
+    gpsiq_patch_t *const d_patches = e.d_patches.get(), *const h_patches = e.h_patches.get();
+    gpsiq::EvalHostItem *const d_host = e.d_host.get(), *const h_host = e.h_host.get();
+    gpsiq_chan_t *const d_raw = e.d_raw.get();
+    double *const d_seeds = e.d_seeds.get(), *const d_c_before = c->chain.d_c_before.get();
+    uint8_t *const d_prep = c->chain.d_prep.get();
+    gpsiq_chain_est_t *const d_est = c->chain.d_est.get();
+    gpsiq_chain_map_t *const d_maps = c->chain.d_maps.get();
 
     // ---- phase A: per piece stage the rows, estimate (chain_prepare), quantise from the estimate, render ------------------------
     // The synthesis of a piece waits for nothing but its own descriptors: in GPSIQ_NCO_REFERENCE they are seeded from
@@ -307,20 +229,20 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     EvalCtrl zero;
     std::memset(&zero, 0, sizeof zero);
     zero.err_key = ~0ull;
-    e.h_ctrl[kEvalMaxPieces + 1] = zero;
-    HIP_TRY(hipMemcpyAsync(e.d_ctrl, &e.h_ctrl[kEvalMaxPieces + 1], sizeof(EvalCtrl), hipMemcpyHostToDevice, S));
+    h_ctrl[kEvalMaxPieces + 1] = zero;
+    HIP_TRY(hipMemcpyAsync(d_ctrl, &h_ctrl[kEvalMaxPieces + 1], sizeof(EvalCtrl), hipMemcpyHostToDevice, S));
     bool cont0[GPSIQ_MAX_CHAN] = {};
     if (!reference) {
         for (int i = 0; i < nchan; ++i) {
             cont0[i] = gpsiq_continues(c, i, first[i]);
-            e.h_fix[i].phase = c->carry[i]; e.h_fix[i].prn = c->carry_prn[i]; e.h_fix[i].cont = cont0[i] ? 1 : 0;
+            h_fix[i].phase = c->carry[i]; h_fix[i].prn = c->carry_prn[i]; h_fix[i].cont = cont0[i] ? 1 : 0;
         }
-        HIP_TRY(hipMemcpyAsync(e.d_fix, e.h_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyHostToDevice, S));
+        HIP_TRY(hipMemcpyAsync(d_fix, h_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyHostToDevice, S));
     }
-    if (seeds) HIP_TRY(hipMemcpyAsync(e.d_seeds, seeds, n * sizeof(double), hipMemcpyHostToDevice, S));
+    if (seeds) HIP_TRY(hipMemcpyAsync(d_seeds, seeds, n * sizeof(double), hipMemcpyHostToDevice, S));
     const bool chained = reference && !seeds;
     // where a block's descriptor takes its carrier phase from: Prep::est (32-byte rows, the double at offset 8), or the caller's states
-    const char *est_rows = seeds ? reinterpret_cast<const char *>(e.d_seeds) : static_cast<const char *>(c->chain.d_prep) + 8;
+    const char *est_rows = seeds ? reinterpret_cast<const char *>(d_seeds) : reinterpret_cast<const char *>(d_prep) + 8;
     const int est_stride = seeds ? 8 : 32;
     PackJob pj = {ch, h_chan, nullptr, nchan, delt, 0, 0, 0};
     hipError_t he = hipSuccess;
@@ -328,14 +250,14 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     SynthClass cls;                                         // of the pieces staged so far
     double t_first_launch = 0.0;
     int timed_blocks = 0;
-    hipEvent_t *staged = e.evaluated;                       // [k]: piece k's descriptors are in the set (and a snapshot of the control block behind them)
+    Event *staged = e.evaluated;                            // [k]: piece k's descriptors are in the set (and a snapshot of the control block behind them)
     for (int k = 0; k < npieces && rc == GPSIQ_OK; ++k) {
         const int b0 = k ? ends[k - 1] : 0, nb = ends[k] - b0;
         const size_t off = (size_t) b0 * nchan, cnt = (size_t) nb * nchan;
-        if (kind == kSrcDevice) he = launch_pack_raw(static_cast<const gpsiq_chan_t *>(dev_src) + off, nb, nchan, delt, d_chan + off, e.d_ctrl, S);
+        if (kind == kSrcDevice) he = launch_pack_raw(static_cast<const gpsiq_chan_t *>(dev_src) + off, nb, nchan, delt, d_chan + off, d_ctrl, S);
         else if (kind == kSrcPinned) {
-            he = hipMemcpyAsync(e.d_raw + off, ch + off, cnt * sizeof(gpsiq_chan_t), hipMemcpyHostToDevice, S);
-            if (he == hipSuccess) he = launch_pack_raw(e.d_raw + off, nb, nchan, delt, d_chan + off, e.d_ctrl, S);
+            he = hipMemcpyAsync(d_raw + off, ch + off, cnt * sizeof(gpsiq_chan_t), hipMemcpyHostToDevice, S);
+            if (he == hipSuccess) he = launch_pack_raw(d_raw + off, nb, nchan, delt, d_chan + off, d_ctrl, S);
         } else {
             const double tp = gpsiq_wall_ms();
             PackJob part = pj;
@@ -347,31 +269,31 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
             he = hipMemcpyAsync(d_chan + off, h_chan + off, cnt * sizeof(ev::DChan), hipMemcpyHostToDevice, S);
         }
         if (he == hipSuccess && chained)
-            he = launch_chain(d_chan + off, (int) sizeof(ev::DChan), nb, nchan, delt, nsamp, k ? c->chain.d_est + (size_t) k * GPSIQ_MAX_CHAN : nullptr, 0,
-                              static_cast<char *>(c->chain.d_prep) + off * 32, c->chain.d_c_before + (size_t) k * GPSIQ_MAX_CHAN,
-                              c->chain.d_est + (size_t) (k + 1) * GPSIQ_MAX_CHAN, c->chain.d_maps + off, S, 1);
+            he = launch_chain(d_chan + off, (int) sizeof(ev::DChan), nb, nchan, delt, nsamp, k ? d_est + (size_t) k * GPSIQ_MAX_CHAN : nullptr, 0,
+                              d_prep + off * c->chain.kPrepBytes, d_c_before + (size_t) k * GPSIQ_MAX_CHAN,
+                              d_est + (size_t) (k + 1) * GPSIQ_MAX_CHAN, d_maps + off, S, 1);
         if (he == hipSuccess) {
-            if (reference) he = launch_quantize_est(d_chan, b0, nb, nchan, delt, nsamp, est_rows, est_stride, nb_.d, e.d_ctrl, S);
-            else he = launch_quantize_fixed(d_chan, b0, nb, nchan, delt, nsamp, nb_.d, e.d_fix, e.d_ctrl, S);
+            if (reference) he = launch_quantize_est(d_chan, b0, nb, nchan, delt, nsamp, est_rows, est_stride, d_set, d_ctrl, S);
+            else he = launch_quantize_fixed(d_chan, b0, nb, nchan, delt, nsamp, d_set, d_fix, d_ctrl, S);
         }
-        if (he == hipSuccess && kind != kSrcPageable) he = hipMemcpyAsync(&e.h_ctrl[k], e.d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, S);
-        if (he == hipSuccess) he = hipEventRecord(staged[k], S);
+        if (he == hipSuccess && kind != kSrcPageable) he = hipMemcpyAsync(&h_ctrl[k], d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, S);
+        if (he == hipSuccess) he = hipEventRecord(staged[k].get(), S);
         // the launch parameters of the synthesis kernel: from the pool's pack at once, from the device's pack behind the event
-        if (he == hipSuccess && kind != kSrcPageable) he = hipEventSynchronize(staged[k]);
+        if (he == hipSuccess && kind != kSrcPageable) he = hipEventSynchronize(staged[k].get());
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d: %s", k, hipGetErrorString(he)); break; }
         if (kind == kSrcPageable) cls = {pj.mx, std::max(pj.max_active, 1), pj.max_amp};
         else {
-            const EvalCtrl &ck = e.h_ctrl[k];
+            const EvalCtrl &ck = h_ctrl[k];
             cls = {std::max<uint64_t>(cls.max_code_step, ck.max_code_step), std::max({cls.max_active, ck.max_active, 1}), std::max<long>(cls.max_amplitude, (long) ck.max_amp)};
         }
         hipStream_t s = gpsiq_piece_stream(c, k);
-        he = hipStreamWaitEvent(s, staged[k], 0);
+        he = hipStreamWaitEvent(s, staged[k].get(), 0);
         if (he == hipSuccess) {
             // the last piece's synthesis is timed: the rate the piece sizes are planned with is a measured one (gpsiq_note_kernel_rate)
-            if (k == npieces - 1) (void) hipEventRecord(e.t_synth0, s);
-            he = launch_variant(auto_variant(cls.max_code_step), nb_.d, nchan, nsamp, sample_size, out.target(b0), out.stride, b0, nb, c->d_tab, s, cls, nullptr,
+            if (k == npieces - 1) (void) hipEventRecord(e.t_synth0.get(), s);
+            he = launch_variant(auto_variant(cls.max_code_step), d_set, nchan, nsamp, sample_size, out.target(b0), out.stride, b0, nb, d_tab, s, cls, nullptr,
                                 gpsiq_noise_at(c, c->call_block));
-            if (k == npieces - 1) { (void) hipEventRecord(e.t_synth1, s); timed_blocks = nb; }
+            if (k == npieces - 1) { (void) hipEventRecord(e.t_synth1.get(), s); timed_blocks = nb; }
             if (trace && k == 0) t_first_launch = gpsiq_wall_ms() - t0;
         }
         // a piece crosses to the destination as soon as it is rendered (the next piece's kernel covers the copy); in
@@ -396,23 +318,23 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
         for (int k = 0; k < nchain && he == hipSuccess; ++k) {
             const int b0 = k ? chain_ends[k - 1] : 0, nb = chain_ends[k] - b0;
             const size_t off = (size_t) b0 * nchan;
-            he = launch_chain(d_chan + off, (int) sizeof(ev::DChan), nb, nchan, delt, nsamp, nullptr, max_seg, static_cast<char *>(c->chain.d_prep) + off * 32,
-                              c->chain.d_c_before + (size_t) k * GPSIQ_MAX_CHAN, nullptr, c->chain.d_maps + off, S, 2);
+            he = launch_chain(d_chan + off, (int) sizeof(ev::DChan), nb, nchan, delt, nsamp, nullptr, max_seg, d_prep + off * c->chain.kPrepBytes,
+                              d_c_before + (size_t) k * GPSIQ_MAX_CHAN, nullptr, d_maps + off, S, 2);
 #ifdef GPSIQ_TEST_HOOKS          // fault injection (tests/test_gpu_verify.py builds a library with it): one map made wrong without making it unusable
-            if (he == hipSuccess) he = launch_test_corrupt_map(c->chain.d_maps, b0, nb, nchan, S);
+            if (he == hipSuccess) he = launch_test_corrupt_map(d_maps, b0, nb, nchan, S);
 #endif
-            if (he == hipSuccess) he = launch_link_scan(d_chan, c->chain.d_maps, b0, nb, nchan, delt, e.d_link, e.d_ctrl, k, S);
-            if (he == hipSuccess) he = hipMemcpyAsync(&e.h_ctrl[k], e.d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, S);
-            if (he == hipSuccess) he = hipEventRecord(e.linked[k], S);
+            if (he == hipSuccess) he = launch_link_scan(d_chan, d_maps, b0, nb, nchan, delt, d_link, d_ctrl, k, S);
+            if (he == hipSuccess) he = hipMemcpyAsync(&h_ctrl[k], d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, S);
+            if (he == hipSuccess) he = hipEventRecord(e.linked[k].get(), S);
         }
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, chain: %s", hipGetErrorString(he)); }
     }
     for (int k = 0; k < nchain && rc == GPSIQ_OK && reference; ++k) {
         const int b0 = k ? chain_ends[k - 1] : 0, nb = chain_ends[k] - b0;
         if (chained) {
-            he = hipEventSynchronize(e.linked[k]);
+            he = hipEventSynchronize(e.linked[k].get());
             if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d: %s", k, hipGetErrorString(he)); break; }
-            const EvalCtrl &ck = e.h_ctrl[k];
+            const EvalCtrl &ck = h_ctrl[k];
             bool need = false;
             for (int i = 0; i < nchan; ++i) need = need || ck.unknown[k][i] > 0 || host_owned[i];
             if (need) {
@@ -423,41 +345,30 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
                 // the synthesis is not held up: it runs from the estimates.
                 const double tr = gpsiq_wall_ms();
                 const int lead = b0 > 0 ? 1 : 0;                                   // the row before the piece too: which satellite the slot had
-                if ((size_t) nb + 1 > e.slot_cap) {
-                    if (e.d_slot) (void) hipFree(e.d_slot);
-                    if (e.h_slot) (void) hipHostFree(e.h_slot);
-                    if (e.d_col) (void) hipFree(e.d_col);
-                    if (e.h_col) (void) hipHostFree(e.h_col);
-                    e.d_slot = nullptr; e.h_slot = nullptr; e.d_col = nullptr; e.h_col = nullptr; e.slot_cap = 0;
-                    const size_t cap = (size_t) nb + 1 + 256;
-                    he = hipMalloc((void **) &e.d_slot, cap * sizeof(EvalSlotRow));
-                    if (he == hipSuccess) he = hipHostMalloc((void **) &e.h_slot, cap * sizeof(EvalSlotRow), hipHostMallocDefault);
-                    if (he == hipSuccess) he = hipMalloc((void **) &e.d_col, cap * sizeof(double));
-                    if (he == hipSuccess) he = hipHostMalloc((void **) &e.h_col, cap * sizeof(double), hipHostMallocDefault);
-                    if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, repair buffers: %s", hipGetErrorString(he)); break; }
-                    e.slot_cap = cap;
-                }
+                if (e.reserve_repair((size_t) nb + 1) != GPSIQ_OK) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, repair buffers: %.300s", gpsiq_last_error()); break; }
+                EvalSlotRow *const d_slot = e.d_slot.get(), *const h_slot = e.h_slot.get();
+                double *const d_col = e.d_col.get(), *const h_col = e.h_col.get();
                 for (int i = 0; i < nchan && rc == GPSIQ_OK; ++i) {
                     if (!(ck.unknown[k][i] > 0 || host_owned[i])) continue;
                     // the slot's column (map + chain inputs + the starts the scan wrote), one small copy instead of every slot's rows
-                    he = launch_gather_slot(d_chan, c->chain.d_maps, b0 - lead, nb + lead, nchan, i, e.d_slot, E);
-                    if (he == hipSuccess) he = hipMemcpyAsync(e.h_slot, e.d_slot, (size_t) (nb + lead) * sizeof(EvalSlotRow), hipMemcpyDeviceToHost, E);
+                    he = launch_gather_slot(d_chan, d_maps, b0 - lead, nb + lead, nchan, i, d_slot, E);
+                    if (he == hipSuccess) he = hipMemcpyAsync(h_slot, d_slot, (size_t) (nb + lead) * sizeof(EvalSlotRow), hipMemcpyDeviceToHost, E);
                     if (he == hipSuccess) he = hipStreamSynchronize(E);
                     if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, repair: %s", hipGetErrorString(he)); break; }
                     if (!host_owned[i]) {
                         // the state the slot enters the piece with: the scan knew every start up to its first block that does not link
-                        host_last_prn[i] = lead && e.h_slot[0].prn > 0 ? e.h_slot[0].prn : 0;
-                        host_end[i] = e.h_slot[lead].start;
+                        host_last_prn[i] = lead && h_slot[0].prn > 0 ? h_slot[0].prn : 0;
+                        host_end[i] = h_slot[lead].start;
                     }
                     long linked = 0, walked = 0;
                     int bad = -1;
-                    if (!link_slot_host(e.h_slot + lead, b0, b0 + nb, delt, nsamp, &host_end[i], &host_last_prn[i], e.h_col, &linked, &walked, &bad)) {
+                    if (!link_slot_host(h_slot + lead, b0, b0 + nb, delt, nsamp, &host_end[i], &host_last_prn[i], h_col, &linked, &walked, &bad)) {
                         rc = GPSIQ_E_RANGE; std::snprintf(err, sizeof err, "block %d: carrier phase or Doppler outside the NCO format", bad);
                         break;
                     }
                     chain_count(linked, walked);
-                    he = hipMemcpyAsync(e.d_col, e.h_col, (size_t) nb * sizeof(double), hipMemcpyHostToDevice, E);
-                    if (he == hipSuccess) he = launch_scatter_starts(d_chan, b0, nb, nchan, i, e.d_col, E);
+                    he = hipMemcpyAsync(d_col, h_col, (size_t) nb * sizeof(double), hipMemcpyHostToDevice, E);
+                    if (he == hipSuccess) he = launch_scatter_starts(d_chan, b0, nb, nchan, i, d_col, E);
                     if (he == hipSuccess) he = hipStreamSynchronize(E);                   // (the staging is reused for the next slot)
                     if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, repair upload: %s", hipGetErrorString(he)); break; }
                     if (!host_owned[i]) { host_owned[i] = true; ++e.last_repaired; }
@@ -466,29 +377,29 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
                 if (rc != GPSIQ_OK) break;
             }
         }
-        he = hipStreamWaitEvent(E, chained ? e.linked[k] : staged[npieces - 1], 0);
+        he = hipStreamWaitEvent(E, chained ? e.linked[k].get() : staged[npieces - 1].get(), 0);
         if (he == hipSuccess)
-            he = launch_eval(d_chan, b0, nb, nchan, delt, nsamp, c->d_tab, est_rows, est_stride, e.d_patches, list_cap(e.patch_cap), e.d_host, list_cap(e.host_cap), e.d_ctrl,
-                             seeds ? e.d_seeds : nullptr, E);
+            he = launch_eval(d_chan, b0, nb, nchan, delt, nsamp, d_tab, est_rows, est_stride, d_patches, list_cap(kPatchCap), d_host, list_cap(kHostCap), d_ctrl,
+                             seeds ? d_seeds : nullptr, E);
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, piece %d evaluation: %s", k, hipGetErrorString(he)); }
     }
 
     // ---- the end of the evaluation: errors, the host walker's share, the patches -----------------------------------------------
-    EvalCtrl &fin = e.h_ctrl[kEvalMaxPieces];
+    EvalCtrl &fin = h_ctrl[kEvalMaxPieces];
     fin = zero;
     size_t npatch_total = 0;
     bool fall_back = false;
     if (rc == GPSIQ_OK) {
         // (the fixed model's kernels ran on the staging stream: the results' way back waits for the last piece's)
-        he = hipStreamWaitEvent(E, staged[npieces - 1], 0);
-        if (he == hipSuccess) he = hipMemcpyAsync(&fin, e.d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, E);
+        he = hipStreamWaitEvent(E, staged[npieces - 1].get(), 0);
+        if (he == hipSuccess) he = hipMemcpyAsync(&fin, d_ctrl, sizeof(EvalCtrl), hipMemcpyDeviceToHost, E);
         if (he == hipSuccess && reference) {
             // the first entries of both lists ride along (nearly always all there are)
-            he = hipMemcpyAsync(e.h_patches, e.d_patches, 1024 * sizeof(gpsiq_patch_t), hipMemcpyDeviceToHost, E);
-            if (he == hipSuccess) he = hipMemcpyAsync(e.h_host, e.d_host, 256 * sizeof(EvalHostItem), hipMemcpyDeviceToHost, E);
-            if (he == hipSuccess && !seeds) he = hipMemcpyAsync(e.h_link, e.d_link, (size_t) nchan * sizeof(LinkCarry), hipMemcpyDeviceToHost, E);
+            he = hipMemcpyAsync(h_patches, d_patches, 1024 * sizeof(gpsiq_patch_t), hipMemcpyDeviceToHost, E);
+            if (he == hipSuccess) he = hipMemcpyAsync(h_host, d_host, 256 * sizeof(EvalHostItem), hipMemcpyDeviceToHost, E);
+            if (he == hipSuccess && !seeds) he = hipMemcpyAsync(h_link, d_link, (size_t) nchan * sizeof(LinkCarry), hipMemcpyDeviceToHost, E);
         }
-        if (he == hipSuccess && !reference) he = hipMemcpyAsync(e.h_fix, e.d_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyDeviceToHost, E);
+        if (he == hipSuccess && !reference) he = hipMemcpyAsync(h_fix, d_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyDeviceToHost, E);
         if (he == hipSuccess) he = hipStreamSynchronize(E);
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, results: %s", hipGetErrorString(he)); }
     }
@@ -513,33 +424,28 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     }
     std::vector<gpsiq_patch_t> patches;
     if (rc == GPSIQ_OK && reference) {
-        if (fin.npatch > list_cap(e.patch_cap) || fin.nhost > list_cap(e.host_cap)) fall_back = true;       // more than the lists hold (a rate far outside the design range)
+        if (fin.npatch > list_cap(kPatchCap) || fin.nhost > list_cap(kHostCap)) fall_back = true;       // more than the lists hold (a rate far outside the design range)
         else {
-            if (fin.npatch > 1024) he = hipMemcpy(e.h_patches + 1024, e.d_patches + 1024, (size_t) (fin.npatch - 1024) * sizeof(gpsiq_patch_t), hipMemcpyDeviceToHost);
-            if (he == hipSuccess && fin.nhost > 256) he = hipMemcpy(e.h_host + 256, e.d_host + 256, (size_t) (fin.nhost - 256) * sizeof(EvalHostItem), hipMemcpyDeviceToHost);
+            if (fin.npatch > 1024) he = hipMemcpy(h_patches + 1024, d_patches + 1024, (size_t) (fin.npatch - 1024) * sizeof(gpsiq_patch_t), hipMemcpyDeviceToHost);
+            if (he == hipSuccess && fin.nhost > 256) he = hipMemcpy(h_host + 256, d_host + 256, (size_t) (fin.nhost - 256) * sizeof(EvalHostItem), hipMemcpyDeviceToHost);
             if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, lists: %s", hipGetErrorString(he)); }
         }
         if (rc == GPSIQ_OK && !fall_back) {
             const double th = gpsiq_wall_ms();
-            patches.assign(e.h_patches, e.h_patches + fin.npatch);
+            patches.assign(h_patches, h_patches + fin.npatch);
             if (fin.nhost) {
                 // what the device left to the host walker: those channels' patches from eval_block, in place of whatever the device
                 // had emitted for them before it gave up
                 std::vector<uint64_t> keys;
-                for (unsigned k = 0; k < fin.nhost; ++k) keys.push_back((uint64_t) e.h_host[k].block << 8 | e.h_host[k].slot);
+                for (unsigned k = 0; k < fin.nhost; ++k) keys.push_back((uint64_t) h_host[k].block << 8 | h_host[k].slot);
                 std::sort(keys.begin(), keys.end());
                 patches.erase(std::remove_if(patches.begin(), patches.end(), [&](const gpsiq_patch_t &p) {
                     return std::binary_search(keys.begin(), keys.end(), (uint64_t) p.block << 8 | p.slot); }), patches.end());
                 // (descriptors that lie in device memory: the few the walker needs come back in one go)
                 if (kind == kSrcDevice) {
-                    if (fin.nhost > e.items_cap) {
-                        if (e.h_items) (void) hipHostFree(e.h_items);
-                        e.h_items = nullptr; e.items_cap = 0;
-                        if (hipHostMalloc((void **) &e.h_items, ((size_t) fin.nhost + 64) * sizeof(gpsiq_chan_t), hipHostMallocDefault) == hipSuccess) e.items_cap = fin.nhost + 64;
-                    }
-                    he = e.items_cap >= fin.nhost ? hipSuccess : hipErrorOutOfMemory;
+                    he = fin.nhost > e.h_items.cap() ? e.h_items.reserve((size_t) fin.nhost + 64) : hipSuccess;
                     for (unsigned k = 0; k < fin.nhost && he == hipSuccess; ++k)
-                        he = hipMemcpyAsync(&e.h_items[k], ch + (size_t) e.h_host[k].block * nchan + e.h_host[k].chan, sizeof(gpsiq_chan_t), hipMemcpyDeviceToHost, E);
+                        he = hipMemcpyAsync(&e.h_items[k], ch + (size_t) h_host[k].block * nchan + h_host[k].chan, sizeof(gpsiq_chan_t), hipMemcpyDeviceToHost, E);
                     if (he == hipSuccess) he = hipStreamSynchronize(E);
                     if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, descriptors for the host walker: %s", hipGetErrorString(he)); }
                 }
@@ -549,7 +455,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
                     std::vector<std::vector<gpsiq_patch_t>> found(fin.nhost);
                     std::vector<int> rcs(fin.nhost, GPSIQ_OK);
                     std::vector<std::array<char, 300>> texts(fin.nhost);
-                    WJob wj = {e.h_host, kind == kSrcDevice ? e.h_items : nullptr, ch, nchan, nsamp, delt, found.data(), rcs.data(), texts.data()};
+                    WJob wj = {h_host, kind == kSrcDevice ? e.h_items.get() : nullptr, ch, nchan, nsamp, delt, found.data(), rcs.data(), texts.data()};
                     parallel_for((int) fin.nhost, 0, 1, [](void *p, int k0, int k1) {
                         WJob &j = *static_cast<WJob *>(p);
                         for (int k = k0; k < k1; ++k) {
@@ -574,24 +480,18 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     // the patches go behind the synthesis of every piece: join the two piece streams on the first
     if (rc == GPSIQ_OK && reference && !fall_back) {
         he = hipSuccess;
-        if (npieces > 1) { he = hipEventRecord(e.joined, c->stream2); if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, e.joined, 0); }
+        if (npieces > 1) { he = hipEventRecord(e.joined.get(), c->stream2.get()); if (he == hipSuccess) he = hipStreamWaitEvent(c->stream.get(), e.joined.get(), 0); }
         if (he == hipSuccess && npatch_total) {
-            if (npatch_total > nb_.patch_cap) {
-                if (nb_.d_patch) (void) hipFree(nb_.d_patch);
-                nb_.d_patch = nullptr; nb_.patch_cap = 0;
-                const size_t cap = npatch_total < 256 ? 256 : npatch_total;
-                he = hipMalloc((void **) &nb_.d_patch, cap * sizeof(gpsiq_patch_t));
-                if (he == hipSuccess) nb_.patch_cap = cap;
-            }
+            he = nb_.d_patch.reserve(gpsiq_patch_room(npatch_total));
             if (he == hipSuccess) {
-                std::memcpy(e.h_patches, patches.data(), npatch_total * sizeof(gpsiq_patch_t));
-                he = hipMemcpyAsync(nb_.d_patch, e.h_patches, npatch_total * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream);
+                std::memcpy(h_patches, patches.data(), npatch_total * sizeof(gpsiq_patch_t));
+                he = hipMemcpyAsync(nb_.d_patch.get(), h_patches, npatch_total * sizeof(gpsiq_patch_t), hipMemcpyHostToDevice, c->stream.get());
             }
-            if (he == hipSuccess) he = launch_patches(nb_.d, nchan, nsamp, sample_size, out.target(0), out.stride, 0, nblocks, c->d_tab, nb_.d_patch, (int) npatch_total,
-                                                       c->stream, gpsiq_noise_at(c, c->call_block));
+            if (he == hipSuccess) he = launch_patches(d_set, nchan, nsamp, sample_size, out.target(0), out.stride, 0, nblocks, d_tab, nb_.d_patch.get(), (int) npatch_total,
+                                                       c->stream.get(), gpsiq_noise_at(c, c->call_block));
         }
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, patches: %s", hipGetErrorString(he)); }
-        else if (out.again(c->stream, patches) != GPSIQ_OK) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, patches: %s", gpsiq_last_error()); }
+        else if (out.again(c->stream.get(), patches) != GPSIQ_OK) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, patches: %s", gpsiq_last_error()); }
     }
 
     // ---- GPSIQ_CHAIN_VERIFY=N: every N-th block that went through its certified map is also walked serially ---------------------
@@ -602,12 +502,12 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     if (rc == GPSIQ_OK && verify_n > 0) {
         const double tv = gpsiq_wall_ms();
         he = hipMemcpyAsync(h_chan, d_chan, n * sizeof(ev::DChan), hipMemcpyDeviceToHost, E);
-        if (he == hipSuccess) he = hipMemcpyAsync(e.h_link, e.d_link, (size_t) nchan * sizeof(LinkCarry), hipMemcpyDeviceToHost, E);
+        if (he == hipSuccess) he = hipMemcpyAsync(h_link, d_link, (size_t) nchan * sizeof(LinkCarry), hipMemcpyDeviceToHost, E);
         if (he == hipSuccess) he = hipStreamSynchronize(E);
         if (he != hipSuccess) { rc = GPSIQ_E_DEVICE; std::snprintf(err, sizeof err, "device evaluation, verify: %s", hipGetErrorString(he)); }
         else {
             struct VJob { const ev::DChan *ch; const LinkCarry *end; const bool *skip; int nblocks, nchan, nsamp, every; double delt; long bad; unsigned count; };
-            VJob vj = {h_chan, e.h_link, host_owned, nblocks, nchan, nsamp, verify_n, delt, -1, 0};
+            VJob vj = {h_chan, h_link, host_owned, nblocks, nchan, nsamp, verify_n, delt, -1, 0};
             parallel_for(nblocks, 4, 64, [](void *p, int b0, int b1) {
                 VJob &j = *static_cast<VJob *>(p);
                 unsigned count = 0;
@@ -648,7 +548,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     if (rc != GPSIQ_OK) return rc;
     if (timed_blocks > 0) {
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, e.t_synth0, e.t_synth1) == hipSuccess && ms > 0.02f)
+        if (hipEventElapsedTime(&ms, e.t_synth0.get(), e.t_synth1.get()) == hipSuccess && ms > 0.02f)
             gpsiq_note_kernel_rate((double) timed_blocks * (double) nsamp * (double) nchan / (ms * 1e-3));
     }
     if (fall_back) {
@@ -659,7 +559,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
 
     // ---- the resident set and the carried state ------------------------------------------------------------------------------
     c->cur = next;
-    c->d_desc = nb_.d;
+    c->d_desc = d_set;
     c->nblocks = nblocks; c->nchan = nchan; c->cls = cls;
     nb_.npatch = (int) npatch_total;
     nb_.active_per_block.assign((size_t) nblocks, (uint8_t) nchan);
@@ -668,11 +568,11 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
         if (carr_phase_out && !seeds)
             for (int i = 0; i < nchan; ++i) {
                 if (host_owned[i]) carr_phase_out[i] = host_last_prn[i] ? host_end[i] : last[i].carr_phase;
-                else carr_phase_out[i] = e.h_link[i].prn > 0 ? e.h_link[i].y : last[i].carr_phase;
+                else carr_phase_out[i] = h_link[i].prn > 0 ? h_link[i].y : last[i].carr_phase;
             }
         chain_count((long) fin.linked, 0);
     } else {
-        for (int i = 0; i < nchan; ++i) gpsiq_hand_back(c, i, e.h_fix[i].prn, e.h_fix[i].phase, carr_phase_out);
+        for (int i = 0; i < nchan; ++i) gpsiq_hand_back(c, i, h_fix[i].prn, h_fix[i].phase, carr_phase_out);
     }
     e.last_nhost = fin.nhost; e.last_npatch = (unsigned) npatch_total;
     __atomic_fetch_add(&g_evd_stats[1], (uint64_t) n, __ATOMIC_RELAXED);

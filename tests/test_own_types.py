@@ -1,0 +1,22 @@
+"""The owning types the device context is made of (csrc/gpsiq_own.h: DevBuf, PinnedBuf, Event, Stream) and the first-use routines
+of the carrier chain and the device evaluation (csrc/gpsiq_ctx.h), on the CPU.  tests/own_types.cpp defines the HIP entry points
+the two headers call as counting fakes over malloc / free, each with a "fail the k-th call" switch, and is built with the address
+and undefined-behaviour sanitizers; no HIP runtime is linked.  It checks that a reserve at or below the capacity makes no call,
+that growing is one free and one allocation of exactly the count given, that a failed allocation or a failed free leaves the
+buffer empty, reported and usable again, that ensure() is idempotent, that every first-use set completes on the attempt after a
+failure at any one of its resources, and that nothing is ever released twice or left alive."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
+
+
+def test_owning_types_and_first_use_sets(tmp_path):
+    exe = str(tmp_path / "own_types")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-D__HIP_PLATFORM_AMD__",
+                    "-I/opt/rocm/include", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tests", "own_types.cpp")], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr       # both sanitizers are silent
+    assert run.stdout.splitlines()[-1] == "own types ok"
