@@ -5,6 +5,8 @@ piece sizes, descriptors in pageable / page-locked / device memory, rough timeli
 slots, exact-tie addends: slots the host walker repairs), the run-time self-check on or off -- rendered through
 GPSIQ_EVAL=device and GPSIQ_EVAL=host (rounds 4-5's path, itself soaked against the reference's own loop): every byte and the
 carried phases must be equal; small runs are also held against the reference's own loop (oracle/_ref) directly.
+The edges beyond its 400 blocks (chunks of 256, rounds of 1 024 blocks, late pieces) are covered deterministically, against an
+independent reference, in tests/test_gpu_eval_edges.py.
 Not part of the test suite.   usage: python tests/soak_device_eval.py [seconds] [seed]"""
 import os
 import sys
