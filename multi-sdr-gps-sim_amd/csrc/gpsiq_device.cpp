@@ -583,7 +583,20 @@ static int chain_maps_staged(gpsiq_ctx *c, int nblocks, int nchan, double fs, in
     rc = chain_drain(c);
     if (rc) return rc;
     (void) hipEventElapsedTime(&k.last_ms, k.t0.get(), k.t1.get());
-    if (end) std::memcpy(end, k.h_est.get() + GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t));
+    if (end) {
+        std::memcpy(end, k.h_est.get() + GPSIQ_MAX_CHAN, (size_t) nchan * sizeof(gpsiq_chain_est_t));
+        // f_carr is that of the last block in which the slot held a satellite, as gpsiq_chain_maps reports it.  The kernel hands on
+        // the last block's: the same unless that block is unused -- then nothing on the device reads it (prn is 0), but a caller may
+        for (int i = 0; i < nchan; ++i) {
+            if (end[i].prn > 0) continue;
+            double f = start ? start[i].f_carr : 0.0;
+            for (int b = nblocks - 1; b >= 0; --b) {
+                const gpsiq_chain_in_t &d = k.h_in.get()[(size_t) b * nchan + i];
+                if (d.prn > 0) { f = d.f_carr; break; }
+            }
+            end[i].f_carr = f;
+        }
+    }
     return GPSIQ_OK;
 }
 

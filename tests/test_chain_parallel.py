@@ -174,7 +174,7 @@ def ctx():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("fs,nsamp,nblocks,nchan", [(2.6e6, 260000, 300, 16), (10e6, 1000000, 120, 12), (25e6, 2500000, 100, 16), (2.6e6, 33333, 700, 5)])
-@pytest.mark.parametrize("stretches", [3, 8, 16, 32])
+@pytest.mark.parametrize("stretches", [1, 3, 5, 8, 16, 17, 32])
 def test_device_maps_and_link_equal_the_serial_chain(ctx, fs, nsamp, nblocks, nchan, stretches):
     cin = timeline(nblocks + stretches, nblocks, nchan)
     want = gpsiq.reference_chain(cin, fs, nsamp)
