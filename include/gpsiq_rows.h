@@ -190,6 +190,49 @@ double gpsiq_composite_rms(const double *gain, int nchan, double sigma);
 /* the multiplier that takes rms_in to rms_out: rint(65536 * rms_out / rms_in), clamped to [1, 2^24 - 1] */
 uint32_t gpsiq_level_mult(double rms_in, double rms_out);
 
+/* ---- Despread: a device correlator that measures what a rendered stream holds ------------------------------------------------
+ * The receiver's first stage -- wipe off carrier, code and data bit with the replica the descriptors define, integrate and dump --
+ * over the resident descriptor set (gpsiq_set_descriptors) and a DEVICE stream laid out as gpsiq_launch writes it: block b at
+ * src + (b - block0) * block_stride_bytes, interleaved I,Q, int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16.  For every block, every
+ * ACTIVE slot k in device order (the block's active channels counted from 0, the rule of gpsiq_patch_t.slot) and every segment j:
+ *     (rI, rQ)(n) = what the closed form of include/gpsiq.h gives sample n for this channel alone with gain 1.0:
+ *                   s*cosTable512[idx], s*sinTable512[idx]     (s = -1 where neg, idx = P(n) >> 50)
+ *     sums[b][k][j].i = sum over n in segment j of  I(n)*rI(n) + Q(n)*rQ(n)
+ *     sums[b][k][j].q = sum over n in segment j of  Q(n)*rI(n) - I(n)*rQ(n)
+ * in exact int64 arithmetic; I(n), Q(n) are the stream's elements as stored (no << 4 for int8).  The data bit is part of neg: it is
+ * wiped, a whole block sums coherently.  The gain is NOT part of the replica, so a channel rendered with gain 0 is a legitimate
+ * noise-floor probe: it adds nothing to the stream and correlates like any other.  The replica is the closed form: patches of
+ * GPSIQ_NCO_REFERENCE (gpsiq_set_patches) are not applied to it.
+ * Segment j is samples [j*seg_len, min((j+1)*seg_len, nsamp)); nseg = ceil(nsamp / seg_len), and seg_len >= nsamp gives one segment
+ * per block.  seg_len must be a multiple of 64 and at least 64 (else GPSIQ_E_ARG): nothing in the estimate below needs a 1 ms
+ * boundary, and a row of 64 samples -- what one wave instruction of the kernels works on -- then lies in exactly one segment.
+ * sums is [nblocks][nchan][nseg] with nchan the resident set's; prn[b][k] is the satellite of slot k; for k at or past the block's
+ * active count prn is 0 and the sums are all zero.  stats (may be NULL) receives the stream's own statistics per block from the
+ * same pass: sums and sums of squares of the I and of the Q elements, and clip_i / clip_q, the number of elements with |x| >= clip.
+ * Bytes between the blocks (block_stride_bytes > 2*nsamp*sample_size) are never read.
+ * The kernels are queued on hip_stream (a hipStream_t, NULL = the null stream), i.e. behind the caller's gpsiq_launch on that
+ * stream; the call then waits, copies the results to the HOST arrays and returns: it is synchronous.  kernel_ms (may be NULL): the
+ * kernel's device time.  Every call overwrites its outputs; the same call twice gives the same answer.  Errors as gpsiq_launch's:
+ * GPSIQ_E_ARG for a bad argument, GPSIQ_E_STATE when the blocks are not resident.  (GPSIQ_DESPREAD_KERNEL=generic in the environment, read per call, takes the generic kernel where the row kernel would serve: the tests' cross-check;
+ * GPSIQ_DESPREAD_TARGET_WGS=N sets the grid size below which the planner shortens the waves' runs, csrc/gpsiq_despread_plan.h.) */
+typedef struct gpsiq_despread_sum { int64_t i, q; } gpsiq_despread_sum_t;
+typedef struct gpsiq_block_stats {
+    int64_t  sum_i, sum_q;
+    uint64_t sumsq_i, sumsq_q;
+    uint32_t clip_i, clip_q;
+} gpsiq_block_stats_t;
+int gpsiq_despread(gpsiq_ctx_t *ctx, int block0, int nblocks, int nsamp, int sample_size,
+                   const void *src, size_t block_stride_bytes, void *hip_stream, int seg_len, int clip,
+                   gpsiq_despread_sum_t *sums /* host [nblocks][nchan][nseg] */, uint8_t *prn /* host [nblocks][nchan] */,
+                   gpsiq_block_stats_t *stats /* host [nblocks], may be NULL */, float *kernel_ms /* may be NULL */);
+/* C/N0 of one channel from count >= 2 full-length segments of it (host arithmetic), with T = seg_len / fs:
+ *     m = mean(i)      v = (sum (i - m)^2 / (count - 1) + sum q^2 / count) / 2      cn0 = 10 log10(m^2 / (2 v T))
+ *     one_sigma_db = (10 / ln 10) * sqrt(1/count + 1/(count * T * 10^(cn0/10)))
+ * (a channel of amplitude a = 250*gain in noise of sigma per component: m = seg_len * a * 250, v = seg_len * sigma^2 * 250^2, and
+ * C/N0 = a^2 * fs / (2 sigma^2) = m^2 / (2 v T).)  GPSIQ_E_RANGE for count < 2, m <= 0 or v == 0. */
+int gpsiq_cn0_estimate(const gpsiq_despread_sum_t *sums, int count, int seg_len, double fs,
+                       double *cn0_dbhz, double *one_sigma_db);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

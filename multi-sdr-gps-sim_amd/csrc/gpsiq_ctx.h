@@ -144,6 +144,16 @@ struct gpsiq_ctx {
         int reserve(size_t n, bool pinned_source, bool seeds);     // first use + room for n blocks x channels
         int reserve_repair(size_t rows);
     } evd;
+    // gpsiq_despread (gpsiq_despread.cpp; include/gpsiq_rows.h, "Despread"): the sums, satellites and stream statistics of one call
+    // on the device and page-locked on their way back, and the two events its kernel is timed with
+    struct Despread {
+        DevBuf<gpsiq_despread_sum_t>    d_sums;   PinnedBuf<gpsiq_despread_sum_t> h_sums;       // [nblocks][nchan][nseg]
+        DevBuf<uint8_t>                 d_prn;    PinnedBuf<uint8_t>              h_prn;        // [nblocks][nchan]
+        DevBuf<gpsiq_block_stats_t>     d_stats;  PinnedBuf<gpsiq_block_stats_t>  h_stats;      // [nblocks]
+        Event          t0, t1;
+        int            last[4] = {-1, 0, 0, 0};        // the last call's plan: kernel, slots, grid, wave_rows (gpsiq_despread_last_plan)
+        int reserve(size_t nsums, size_t nprn, size_t nblocks);     // first use + room for one call
+    } dsp;
 };
 
 #define HIP_TRY(expr)                                                                        \
@@ -226,6 +236,29 @@ inline int gpsiq_ctx::EvalDev::reserve_repair(size_t rows)
     return GPSIQ_OK;
 }
 
+// (every pair grows together, device side first: a step that failed part-way is entered again by the next call, whatever its size)
+inline int gpsiq_ctx::Despread::reserve(size_t nsums, size_t nprn, size_t nblocks)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    if (nsums > std::min(d_sums.cap(), h_sums.cap())) {
+        const size_t cap = nsums + nsums / 4 + 256;
+        HIP_TRY(d_sums.reserve(cap));
+        HIP_TRY(h_sums.reserve(cap));
+    }
+    if (nprn > std::min(d_prn.cap(), h_prn.cap())) {
+        const size_t cap = nprn + nprn / 4 + 256;
+        HIP_TRY(d_prn.reserve(cap));
+        HIP_TRY(h_prn.reserve(cap));
+    }
+    if (nblocks > std::min(d_stats.cap(), h_stats.cap())) {
+        const size_t cap = nblocks + nblocks / 4 + 16;
+        HIP_TRY(d_stats.reserve(cap));
+        HIP_TRY(h_stats.reserve(cap));
+    }
+    return GPSIQ_OK;
+}
+
 // helpers of gpsiq_device.cpp the other translation unit uses
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
 gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
@@ -284,6 +317,10 @@ int gpsiq_generate_reference_host(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblo
 // not taken (too short a batch, switched off), the caller goes on with the host path
 int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                           void *dst, int dst_is_device, double *carr_phase_out, const double *seeds, int *handled);
+// gpsiq_despread.cpp: gpsiq_despread (include/gpsiq_rows.h) itself, behind the plumbing entry "despread"
+int gpsiq_despread_impl(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int sample_size, const void *src, size_t block_stride_bytes,
+                        void *hip_stream, int seg_len, int clip, gpsiq_despread_sum_t *sums, uint8_t *prn, gpsiq_block_stats_t *stats,
+                        float *kernel_ms);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
@@ -310,6 +347,12 @@ RowsFn      rowsx_kernel(int fmt, int slots);
 RowsFn      rows_kernel(int fmt);
 GenericFn   generic_kernel(int fmt);
 PatchFn     patch_kernel(int fmt);
+// the correlator kernels (gpsiq_despread_kernels.hip): kernel and slots as gpsiq_despread_plan.h names them.  Arguments: descriptors,
+// nchan, nsamp, src, block stride, block0, tables, workgroups per block, rows per wave, rows per segment, segments per block, clip,
+// sums, satellites, stream statistics (may be null)
+using DespreadFn  = void (*)(const gpsiq_qchan_t *, int, int, const uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int,
+                             gpsiq_despread_sum_t *, uint8_t *, gpsiq_block_stats_t *);
+DespreadFn  despread_kernel(int fmt, int kernel, int slots);
 
 // gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
 // of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)

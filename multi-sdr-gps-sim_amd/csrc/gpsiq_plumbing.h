@@ -24,7 +24,9 @@ void *gpsiq_plumbing(const char *name);
  * two libraries share ONE worker pool, ONE quantiser and ONE error text per thread (csrc/gpsiq_rows_link.cpp is the other end):
  * "set_error", "parallel_for", "quantize_one", "chain_carrier" (csrc/gpsiq_internal.h has their C++ signatures).
  * A fifth name, "set_level", is the implementation of gpsiq_set_level (include/gpsiq_rows.h, "Output level"), which libgpsiq_rows.so
- * exports because this library is at its export limit: int (gpsiq_ctx_t *, const gpsiq_level_t *). */
+ * exports because this library is at its export limit: int (gpsiq_ctx_t *, const gpsiq_level_t *).
+ * A sixth, "despread", is the implementation of gpsiq_despread (ibid., "Despread"; csrc/gpsiq_despread.cpp), exported by
+ * libgpsiq_rows.so for the same reason, with gpsiq_despread's own signature. */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -180,6 +182,10 @@ double gpsiq_device_eval_host_ms(const gpsiq_ctx_t *ctx);
  * iq[2n] = zI(n), iq[2n+1] = zQ(n) for samples n = 0..nsamp-1 of absolute block `block`, in accumulator units. */
 int gpsiq_noise_state(const gpsiq_ctx_t *ctx, gpsiq_noise_t *out);
 int gpsiq_noise_host(uint64_t seed, double sigma, uint64_t block, int nsamp, int32_t *iq);
+
+/* What the context's last gpsiq_despread took (csrc/gpsiq_despread_plan.h): out[0] the kernel (0 generic, 1 rows; -1: no call yet),
+ * out[1] the channel slots of the row kernel, out[2] the grid, out[3] the rows per wave. */
+int gpsiq_despread_last_plan(const gpsiq_ctx_t *ctx, int out[4]);
 
 #ifdef __cplusplus
 }

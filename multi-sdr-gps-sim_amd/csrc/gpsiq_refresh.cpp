@@ -670,4 +670,30 @@ uint32_t gpsiq_level_mult(double rms_in, double rms_out)
     return m > 16777215.0 ? 16777215u : (uint32_t) m;
 }
 
+// include/gpsiq_rows.h, "Despread": the signal is the mean of the in-phase sums, the noise per component the mean of their sample
+// variance and the quadrature sums' mean square; m^2 / v = seg_len * a^2 / sigma^2 and C/N0 = a^2 * fs / (2 sigma^2)
+int gpsiq_cn0_estimate(const gpsiq_despread_sum_t *sums, int count, int seg_len, double fs, double *cn0_dbhz, double *one_sigma_db)
+{
+    if (!cn0_dbhz || !one_sigma_db) return fail(GPSIQ_E_ARG, "null argument");
+    if (seg_len < 1 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad seg_len %d / fs %g", seg_len, fs);
+    if (count < 2) return fail(GPSIQ_E_RANGE, "C/N0 estimate needs two segments or more (have %d)", count);
+    if (!sums) return fail(GPSIQ_E_ARG, "null argument");
+    double m = 0.0;
+    for (int k = 0; k < count; ++k) m += (double) sums[k].i;
+    m /= (double) count;
+    double si = 0.0, sq = 0.0;
+    for (int k = 0; k < count; ++k) {
+        const double d = (double) sums[k].i - m, q = (double) sums[k].q;
+        si += d * d;
+        sq += q * q;
+    }
+    const double v = (si / (double) (count - 1) + sq / (double) count) / 2.0;
+    if (!(m > 0.0) || !(v > 0.0)) return fail(GPSIQ_E_RANGE, "C/N0 estimate: mean %g, noise variance %g: no signal or no noise", m, v);
+    const double T = (double) seg_len / fs;
+    const double cn0 = 10.0 * std::log10(m * m / (2.0 * v * T));
+    *cn0_dbhz = cn0;
+    *one_sigma_db = (10.0 / std::log(10.0)) * std::sqrt(1.0 / (double) count + 1.0 / ((double) count * T * std::pow(10.0, cn0 / 10.0)));
+    return GPSIQ_OK;
+}
+
 }  // extern "C"

@@ -59,3 +59,14 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_set_level(gpsiq_ctx_
     static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_level_t *)>("set_level");
     return f(ctx, lv);
 }
+
+// The correlator runs on the context's device and resident descriptors, which live in libgpsiq.so (csrc/gpsiq_despread.cpp); exported
+// here for the same reason (include/gpsiq_rows.h, "Despread").
+extern "C" __attribute__((visibility("default"))) int gpsiq_despread(gpsiq_ctx_t *ctx, int block0, int nblocks, int nsamp, int sample_size,
+                                                                     const void *src, size_t block_stride_bytes, void *hip_stream, int seg_len, int clip,
+                                                                     gpsiq_despread_sum_t *sums, uint8_t *prn, gpsiq_block_stats_t *stats, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, int, const void *, size_t, void *, int, int, gpsiq_despread_sum_t *, uint8_t *,
+                                              gpsiq_block_stats_t *, float *)>("despread");
+    return f(ctx, block0, nblocks, nsamp, sample_size, src, block_stride_bytes, hip_stream, seg_len, clip, sums, prn, stats, kernel_ms);
+}

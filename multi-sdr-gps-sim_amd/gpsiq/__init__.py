@@ -13,7 +13,7 @@ import numpy as np
 from .abi import (CHAN_DTYPE, QCHAN_DTYPE, SC08, SC16, SINK_HACKRF, SINK_IQFILE,  # noqa: F401
                   SINK_PLUTOSDR, HACKRF_CHUNK, MAX_CHAN, elem_dtype, EPHEM_DTYPE, IONO_DTYPE, TRACK_DTYPE,
                   NAV_EPH_DTYPE, NAV_UTC_DTYPE, NAV_ALM_DTYPE, NAV_STATE_DTYPE, RINEX_EPH_DTYPE, PATCH_DTYPE,
-                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE)
+                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPSIQ_LIB: another build of the library (tests/test_gpu_build.py loads the one it has just compiled on the GPU box)
@@ -151,6 +151,9 @@ _noise_sigma_for_cn0 = _sig("gpsiq_noise_sigma_for_cn0", _d, _d, _d, _d)
 _set_level = _sig("gpsiq_set_level", _i, _vp, _vp)
 _composite_rms = _sig("gpsiq_composite_rms", _d, _vp, _i, _d)
 _level_mult = _sig("gpsiq_level_mult", C.c_uint32, _d, _d)
+_despread = _sig("gpsiq_despread", _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_float))
+_despread_last_plan = _sig("gpsiq_despread_last_plan", _i, _vp, _vp)
+_cn0_estimate = _sig("gpsiq_cn0_estimate", _i, _vp, _i, _i, _d, C.POINTER(_d), C.POINTER(_d))
 
 
 class NoiseSettings(C.Structure):
@@ -617,6 +620,15 @@ def level_mult(rms_in, rms_out):
     return int(_level_mult(float(rms_in), float(rms_out)))
 
 
+def cn0_estimate(sums, seg_len, fs):
+    """gpsiq_cn0_estimate: (C/N0 in dB-Hz, its one-sigma in dB) of one channel from its full-length segments' sums (DESPREAD_SUM_DTYPE,
+    any shape: every element is one segment)."""
+    s = np.ascontiguousarray(sums, dtype=DESPREAD_SUM_DTYPE).ravel()
+    cn0, one = _d(0.0), _d(0.0)
+    _check(_cn0_estimate(_p(s) if s.size else None, int(s.size), int(seg_len), float(fs), C.byref(cn0), C.byref(one)))
+    return cn0.value, one.value
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -651,6 +663,7 @@ class Context:
         _check(_create(C.byref(h), int(device)))
         self._h = h
         self.device = device
+        self.resident_nchan = 0          # channel slots of the set set_descriptors() made resident (despread()'s output shape)
 
     def close(self):
         if self._h:
@@ -780,10 +793,33 @@ class Context:
         q = np.ascontiguousarray(q, dtype=QCHAN_DTYPE)
         nb, nc = q.shape
         _check(_set_descriptors(self._h, _p(q), nb, nc))
+        self.resident_nchan = nc
 
     def launch(self, block0, nblocks, nsamp, sample_size, device_ptr, block_stride, stream=None, variant=0):
         _check(_launch(self._h, int(block0), int(nblocks), int(nsamp), int(sample_size), _vp(device_ptr),
                        int(block_stride), _vp(stream or 0), int(variant)))
+
+    def despread(self, block0, nblocks, nsamp, sample_size, device_ptr, block_stride, seg_len, clip=0, stream=None, stats=True, nchan=None):
+        """gpsiq_despread: correlate the device stream at device_ptr (laid out as launch() writes it) with the replica of every
+        active channel of the resident blocks [block0, block0 + nblocks) -> (sums DESPREAD_SUM_DTYPE [nblocks][nchan][nseg],
+        prn uint8 [nblocks][nchan], stats BLOCK_STATS_DTYPE [nblocks] or None, kernel milliseconds).  Slots are in device order: a
+        block's active channels counted from 0.  nchan: the resident set's channel slots where another call than set_descriptors()
+        made it resident."""
+        nc = int(nchan or self.resident_nchan)
+        nseg = -(-int(nsamp) // int(seg_len)) if seg_len > 0 else 0
+        sums = np.zeros((int(nblocks), nc, max(nseg, 0)), dtype=DESPREAD_SUM_DTYPE)
+        prn = np.zeros((int(nblocks), nc), dtype=np.uint8)
+        st = np.zeros(int(nblocks), dtype=BLOCK_STATS_DTYPE) if stats else None
+        ms = C.c_float(0.0)
+        _check(_despread(self._h, int(block0), int(nblocks), int(nsamp), int(sample_size), _vp(device_ptr), int(block_stride), _vp(stream or 0),
+                         int(seg_len), int(clip), _p(sums), _p(prn), None if st is None else _p(st), C.byref(ms)))
+        return sums, prn, st, float(ms.value)
+
+    def despread_last_plan(self):
+        """What the last despread() took: (kernel name or None, channel slots of the row kernel, grid, rows per wave)."""
+        out = np.zeros(4, dtype=np.int32)
+        _check(_despread_last_plan(self._h, _p(out)))
+        return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def synchronize(self, stream=None):
         _check(_synchronize(self._h, _vp(stream or 0)))

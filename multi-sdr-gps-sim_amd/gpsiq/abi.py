@@ -86,3 +86,8 @@ RINEX_EPH_DTYPE = np.dtype([("vflg", "<i4"), ("sva", "<i4"), ("svh", "<i4"), ("c
                             ("orbit", EPHEM_DTYPE), ("nav", NAV_EPH_DTYPE)], align=True)
 assert RINEX_EPH_DTYPE.itemsize == 432
 EPHEM_SETS, MAX_SAT = 13, 32
+
+# gpsiq_despread (include/gpsiq_rows.h, "Despread")
+DESPREAD_SUM_DTYPE = np.dtype([("i", "<i8"), ("q", "<i8")], align=True)
+BLOCK_STATS_DTYPE = np.dtype([("sum_i", "<i8"), ("sum_q", "<i8"), ("sumsq_i", "<u8"), ("sumsq_q", "<u8"), ("clip_i", "<u4"), ("clip_q", "<u4")], align=True)
+assert DESPREAD_SUM_DTYPE.itemsize == 16 and BLOCK_STATS_DTYPE.itemsize == 40
