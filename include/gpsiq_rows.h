@@ -233,6 +233,54 @@ int gpsiq_despread(gpsiq_ctx_t *ctx, int block0, int nblocks, int nsamp, int sam
 int gpsiq_cn0_estimate(const gpsiq_despread_sum_t *sums, int count, int seg_len, double fs,
                        double *cn0_dbhz, double *one_sigma_db);
 
+/* ---- Packed streams: 4 and 2 bits per component, as narrow front ends and their players read them -----------------------------------
+ * Two packed formats of the interleaved I,Q stream; both hold two's-complement fields with I in the low bits:
+ *   GPSIQ_PK4   4 bits per component, one byte per complex sample:   byte n = (I(n) & 15) | ((Q(n) & 15) << 4)
+ *               field range -7..7; the code of -8 is never produced
+ *   GPSIQ_PK2   2 bits per component, two complex samples per byte:  byte m = nib(2m) | (nib(2m+1) << 4),
+ *               nib(n) = (I(n) & 3) | ((Q(n) & 3) << 2); field range -1..1, the 3-level stream of qmax 1; for an odd nsamp the
+ *               last byte's high nibble is 0
+ * gpsiq_packed_block_bytes(nsamp, bits): nsamp for 4 bits, (nsamp + 1) / 2 for 2 bits (0 for nsamp <= 0 or another `bits`).
+ *
+ * gpsiq_pack packs a DEVICE stream laid out as gpsiq_launch writes it (block b at src_dev + b * src_stride, int8 for GPSIQ_SC08 and
+ * int16 for GPSIQ_SC16; src_dev 4-byte aligned, the stride a multiple of 4) into device memory, block b at dst_dev + b * dst_stride
+ * (dst_dev 4-byte aligned, dst_stride >= gpsiq_packed_block_bytes and a multiple of 4).  The packer SATURATES: an element outside the
+ * field range is clamped to +-7 / +-1 (symmetric, like the output level's clamp: no DC), and such elements are COUNTED: *clipped
+ * (may be NULL) is their number over the whole call, so a stream that was not levelled, or levelled for another format, packs to
+ * something defined and the caller sees a non-zero count instead of a silent wrap.  Bytes past a block's packed length are never
+ * written, source bytes past 2*nsamp*sample_size never read.  The ranges must not overlap (GPSIQ_E_ARG).  The kernel is queued on
+ * hip_stream (a hipStream_t, NULL = the null stream), i.e. behind the caller's gpsiq_launch on that stream; the call then waits,
+ * fetches the count and returns: synchronous, like gpsiq_despread.  kernel_ms (may be NULL): the kernel's device time.  nblocks == 0
+ * or nsamp == 0 launches nothing and returns GPSIQ_OK with a count of 0.
+ * gpsiq_unpack is the inverse: the fields sign-extended into int8 / int16 elements, no shift, exactly 2*nsamp elements per block --
+ * what gpsiq_despread takes, so a packed stream can be measured.  unpack(pack(x)) is x clamped.
+ *
+ * gpsiq_generate_batch_packed is the run-ahead call (gpsiq_generate_batch, include/gpsiq.h) that delivers packed blocks to HOST
+ * memory, pageable or page-locked, block b at dst_host + b * dst_block_stride (any stride >= gpsiq_packed_block_bytes).  ch is
+ * [nblocks][nchan] in host memory.  It needs the output level on with qmax <= 7 for 4 bits and <= 1 for 2 bits, else GPSIQ_E_STATE:
+ * the packer then clamps nothing and the bytes are exactly the levelled int8 stream's (a packer that did clamp: GPSIQ_E_DEVICE).  The call
+ * works in pieces of about 32 MiB of rendered stream (GPSIQ_PACK_PIECE_BLOCKS=n in the environment, read per call: n blocks per piece):
+ * gpsiq_generate_batch renders a piece into device staging of the context's, the packer packs it, and its rows cross to the host
+ * while the next piece renders.  The result is byte for byte the pack of what ONE gpsiq_generate_batch call over the whole timeline
+ * writes at GPSIQ_SC08, in both NCO models, with noise and with patches; carrier continuation, the noise block counter and
+ * carr_phase_out are that call's.  When an inner call fails its error comes back as it is; dst_host is then undefined. */
+#define GPSIQ_PK4 4
+#define GPSIQ_PK2 2
+size_t gpsiq_packed_block_bytes(int nsamp, int bits);
+int gpsiq_pack(gpsiq_ctx_t *ctx, int nblocks, int nsamp, int sample_size,
+               const void *src_dev, size_t src_stride, int bits,
+               void *dst_dev, size_t dst_stride,
+               void *hip_stream, uint64_t *clipped /* may be NULL */, float *kernel_ms /* may be NULL */);
+int gpsiq_unpack(gpsiq_ctx_t *ctx, int nblocks, int nsamp, int bits,
+                 const void *src_dev, size_t src_stride, int sample_size,
+                 void *dst_dev, size_t dst_stride,
+                 void *hip_stream, float *kernel_ms /* may be NULL */);
+int gpsiq_generate_batch_packed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch,
+                                int nblocks, int nchan, int nsamp, double fs,
+                                int bits, void *dst_host,
+                                size_t dst_block_stride,
+                                double *carr_phase_out /* [nchan], may be NULL */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

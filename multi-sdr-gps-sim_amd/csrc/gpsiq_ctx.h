@@ -154,6 +154,19 @@ struct gpsiq_ctx {
         int            last[4] = {-1, 0, 0, 0};        // the last call's plan: kernel, slots, grid, wave_rows (gpsiq_despread_last_plan)
         int reserve(size_t nsums, size_t nprn, size_t nblocks);     // first use + room for one call
     } dsp;
+    // gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed (gpsiq_pack.cpp; include/gpsiq_rows.h, "Packed streams"): the counter of
+    // clamped elements on the device and page-locked on its way back, the two events a kernel is timed with, and what the batch call
+    // works through its pieces with -- two rendered and two packed staging buffers taken in turn, a stream for the packer, one for
+    // the copies, and per buffer pair the events "packed" and "copied"
+    struct Pack {
+        DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
+        DevBuf<uint8_t>               d_render[2], d_packed[2];                               // bytes
+        Stream         pack_stream, copy_stream;
+        Event          t0, t1, packed[2], copied[2];
+        std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+        long           last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, units per block, tiles per block, pieces (gpsiq_pack_last_plan)
+        int reserve(size_t render_bytes, size_t packed_bytes);      // first use + room for one call (0, 0: gpsiq_pack / gpsiq_unpack)
+    } pack;
 };
 
 #define HIP_TRY(expr)                                                                        \
@@ -259,6 +272,29 @@ inline int gpsiq_ctx::Despread::reserve(size_t nsums, size_t nprn, size_t nblock
     return GPSIQ_OK;
 }
 
+// (the counter, events and streams on first use; the staging pairs grow together, rendered side first)
+inline int gpsiq_ctx::Pack::reserve(size_t render_bytes, size_t packed_bytes)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(d_count.reserve(1));
+    HIP_TRY(h_count.reserve(1));
+    if (!render_bytes && !packed_bytes) return GPSIQ_OK;
+    HIP_TRY(pack_stream.ensure());
+    HIP_TRY(copy_stream.ensure());
+    for (auto &e : packed) HIP_TRY(e.ensure());
+    for (auto &e : copied) HIP_TRY(e.ensure());
+    if (render_bytes > std::min(d_render[0].cap(), d_render[1].cap())) {
+        const size_t cap = render_bytes + render_bytes / 4 + 256;
+        for (auto &b : d_render) HIP_TRY(b.reserve(cap));
+    }
+    if (packed_bytes > std::min(d_packed[0].cap(), d_packed[1].cap())) {
+        const size_t cap = packed_bytes + packed_bytes / 4 + 256;
+        for (auto &b : d_packed) HIP_TRY(b.reserve(cap));
+    }
+    return GPSIQ_OK;
+}
+
 // helpers of gpsiq_device.cpp the other translation unit uses
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
 gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
@@ -321,6 +357,14 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
 int gpsiq_despread_impl(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int sample_size, const void *src, size_t block_stride_bytes,
                         void *hip_stream, int seg_len, int clip, gpsiq_despread_sum_t *sums, uint8_t *prn, gpsiq_block_stats_t *stats,
                         float *kernel_ms);
+// gpsiq_pack.cpp: gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (include/gpsiq_rows.h) themselves, behind the plumbing
+// entries "pack", "unpack" and "generate_batch_packed"
+int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, const void *src_dev, size_t src_stride, int bits,
+                    void *dst_dev, size_t dst_stride, void *hip_stream, uint64_t *clipped, float *kernel_ms);
+int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const void *src_dev, size_t src_stride, int sample_size,
+                      void *dst_dev, size_t dst_stride, void *hip_stream, float *kernel_ms);
+int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int bits,
+                                     void *dst_host, size_t dst_block_stride, double *carr_phase_out);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
@@ -353,6 +397,12 @@ PatchFn     patch_kernel(int fmt);
 using DespreadFn  = void (*)(const gpsiq_qchan_t *, int, int, const uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int,
                              gpsiq_despread_sum_t *, uint8_t *, gpsiq_block_stats_t *);
 DespreadFn  despread_kernel(int fmt, int kernel, int slots);
+// the pack / unpack kernels (gpsiq_pack_kernels.hip).  Arguments: source and its block stride, destination and its block stride,
+// samples per block, units per block, tiles per block, tiles of the launch (gpsiq_pack_plan.h); pack: the counter of clamped elements
+using PackFn      = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, uint32_t, uint32_t, uint64_t, unsigned long long *);
+using UnpackFn    = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, uint32_t, uint32_t, uint64_t);
+PackFn      pack_kernel(int fmt, int bits);
+UnpackFn    unpack_kernel(int bits, int fmt);
 
 // gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
 // of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)

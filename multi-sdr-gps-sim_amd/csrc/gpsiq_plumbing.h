@@ -26,7 +26,9 @@ void *gpsiq_plumbing(const char *name);
  * A fifth name, "set_level", is the implementation of gpsiq_set_level (include/gpsiq_rows.h, "Output level"), which libgpsiq_rows.so
  * exports because this library is at its export limit: int (gpsiq_ctx_t *, const gpsiq_level_t *).
  * A sixth, "despread", is the implementation of gpsiq_despread (ibid., "Despread"; csrc/gpsiq_despread.cpp), exported by
- * libgpsiq_rows.so for the same reason, with gpsiq_despread's own signature. */
+ * libgpsiq_rows.so for the same reason, with gpsiq_despread's own signature.
+ * "pack", "unpack" and "generate_batch_packed" are gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (ibid., "Packed streams";
+ * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements. */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -186,6 +188,9 @@ int gpsiq_noise_host(uint64_t seed, double sigma, uint64_t block, int nsamp, int
 /* What the context's last gpsiq_despread took (csrc/gpsiq_despread_plan.h): out[0] the kernel (0 generic, 1 rows; -1: no call yet),
  * out[1] the channel slots of the row kernel, out[2] the grid, out[3] the rows per wave. */
 int gpsiq_despread_last_plan(const gpsiq_ctx_t *ctx, int out[4]);
+/* What the context's last gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed took (csrc/gpsiq_pack_plan.h): out[0] the grid (-1: nothing
+ * was launched, or no call yet), out[1] the units per block, out[2] the tiles per block, out[3] the pieces of a batch call (0: not one). */
+int gpsiq_pack_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
 
 #ifdef __cplusplus
 }

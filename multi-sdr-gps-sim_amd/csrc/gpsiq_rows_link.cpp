@@ -70,3 +70,35 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_despread(gpsiq_ctx_t
                                               gpsiq_block_stats_t *, float *)>("despread");
     return f(ctx, block0, nblocks, nsamp, sample_size, src, block_stride_bytes, hip_stream, seg_len, clip, sums, prn, stats, kernel_ms);
 }
+
+// The packed stream formats (include/gpsiq_rows.h, "Packed streams"): the block length is host arithmetic; packer, unpacker and the
+// packed batch call run on the context's device (csrc/gpsiq_pack.cpp) and are exported here like the correlator.
+extern "C" __attribute__((visibility("default"))) size_t gpsiq_packed_block_bytes(int nsamp, int bits)
+{
+    if (nsamp <= 0) return 0;
+    return bits == GPSIQ_PK4 ? (size_t) nsamp : bits == GPSIQ_PK2 ? ((size_t) nsamp + 1) / 2 : 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_pack(gpsiq_ctx_t *ctx, int nblocks, int nsamp, int sample_size, const void *src_dev,
+                                                                 size_t src_stride, int bits, void *dst_dev, size_t dst_stride, void *hip_stream,
+                                                                 uint64_t *clipped, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, const void *, size_t, int, void *, size_t, void *, uint64_t *, float *)>("pack");
+    return f(ctx, nblocks, nsamp, sample_size, src_dev, src_stride, bits, dst_dev, dst_stride, hip_stream, clipped, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_unpack(gpsiq_ctx_t *ctx, int nblocks, int nsamp, int bits, const void *src_dev,
+                                                                   size_t src_stride, int sample_size, void *dst_dev, size_t dst_stride,
+                                                                   void *hip_stream, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, const void *, size_t, int, void *, size_t, void *, float *)>("unpack");
+    return f(ctx, nblocks, nsamp, bits, src_dev, src_stride, sample_size, dst_dev, dst_stride, hip_stream, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_packed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan,
+                                                                                  int nsamp, double fs, int bits, void *dst_host,
+                                                                                  size_t dst_block_stride, double *carr_phase_out)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_chan_t *, int, int, int, double, int, void *, size_t, double *)>("generate_batch_packed");
+    return f(ctx, ch, nblocks, nchan, nsamp, fs, bits, dst_host, dst_block_stride, carr_phase_out);
+}

@@ -154,6 +154,11 @@ _level_mult = _sig("gpsiq_level_mult", C.c_uint32, _d, _d)
 _despread = _sig("gpsiq_despread", _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_float))
 _despread_last_plan = _sig("gpsiq_despread_last_plan", _i, _vp, _vp)
 _cn0_estimate = _sig("gpsiq_cn0_estimate", _i, _vp, _i, _i, _d, C.POINTER(_d), C.POINTER(_d))
+_packed_block_bytes = _sig("gpsiq_packed_block_bytes", _sz, _i, _i)
+_pack = _sig("gpsiq_pack", _i, _vp, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_unpack = _sig("gpsiq_unpack", _i, _vp, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp, C.POINTER(C.c_float))
+_generate_batch_packed = _sig("gpsiq_generate_batch_packed", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _sz, _vp)
+_pack_last_plan = _sig("gpsiq_pack_last_plan", _i, _vp, _vp)
 
 
 class NoiseSettings(C.Structure):
@@ -620,6 +625,11 @@ def level_mult(rms_in, rms_out):
     return int(_level_mult(float(rms_in), float(rms_out)))
 
 
+def packed_block_bytes(nsamp, bits):
+    """gpsiq_packed_block_bytes: bytes of one packed block (include/gpsiq_rows.h, "Packed streams")."""
+    return int(_packed_block_bytes(int(nsamp), int(bits)))
+
+
 def cn0_estimate(sums, seg_len, fs):
     """gpsiq_cn0_estimate: (C/N0 in dB-Hz, its one-sigma in dB) of one channel from its full-length segments' sums (DESPREAD_SUM_DTYPE,
     any shape: every element is one segment)."""
@@ -820,6 +830,43 @@ class Context:
         out = np.zeros(4, dtype=np.int32)
         _check(_despread_last_plan(self._h, _p(out)))
         return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def pack(self, nblocks, nsamp, sample_size, device_ptr, src_stride, bits, dst_device_ptr, dst_stride, stream=None):
+        """gpsiq_pack: the device stream at device_ptr (laid out as launch() writes it) packed to `bits` (4 or 2) per component at
+        dst_device_ptr -> (elements the packer had to clamp, kernel milliseconds)."""
+        clipped, ms = C.c_uint64(0), C.c_float(0.0)
+        _check(_pack(self._h, int(nblocks), int(nsamp), int(sample_size), _vp(device_ptr), int(src_stride), int(bits), _vp(dst_device_ptr),
+                     int(dst_stride), _vp(stream or 0), C.byref(clipped), C.byref(ms)))
+        return int(clipped.value), float(ms.value)
+
+    def unpack(self, nblocks, nsamp, bits, device_ptr, src_stride, sample_size, dst_device_ptr, dst_stride, stream=None):
+        """gpsiq_unpack: the packed device stream at device_ptr back into int8 / int16 elements at dst_device_ptr -> kernel milliseconds."""
+        ms = C.c_float(0.0)
+        _check(_unpack(self._h, int(nblocks), int(nsamp), int(bits), _vp(device_ptr), int(src_stride), int(sample_size), _vp(dst_device_ptr),
+                       int(dst_stride), _vp(stream or 0), C.byref(ms)))
+        return float(ms.value)
+
+    def generate_batch_packed(self, desc, nsamp, fs, bits, host_ptr=None, block_stride=None, carr_out=None):
+        """gpsiq_generate_batch_packed: the run-ahead call with packed blocks in host memory (the output level must be on with a
+        qmax inside the format).  Returns uint8 [nblocks][packed_block_bytes], or None when host_ptr names the caller's buffer
+        (pageable or page-locked; block_stride bytes between blocks, default: back to back)."""
+        desc = np.ascontiguousarray(desc, dtype=CHAN_DTYPE)
+        nb, nc = desc.shape
+        plen = packed_block_bytes(nsamp, bits)
+        stride = plen if block_stride is None else int(block_stride)
+        co = None if carr_out is None else _p(carr_out)
+        if host_ptr is not None:
+            _check(_generate_batch_packed(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(bits), _vp(host_ptr), stride, co))
+            return None
+        out = np.zeros((nb, stride), dtype=np.uint8)
+        _check(_generate_batch_packed(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(bits), _p(out), stride, co))
+        return out[:, :plen]
+
+    def pack_last_plan(self):
+        """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""
+        out = (C.c_long * 4)()
+        _check(_pack_last_plan(self._h, out))
+        return (None if out[0] < 0 else int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def synchronize(self, stream=None):
         _check(_synchronize(self._h, _vp(stream or 0)))

@@ -7,6 +7,7 @@ CA_SEQ_LEN = 1023
 CARR_FRAC_BITS = 59
 CODE_FRAC_BITS = 56
 SC08, SC16 = 1, 2
+PK4, PK2 = 4, 2          # packed stream formats (include/gpsiq_rows.h, "Packed streams"): bits per component
 SINK_IQFILE, SINK_HACKRF, SINK_PLUTOSDR = 1, 2, 3
 HACKRF_CHUNK = 262144
 

@@ -13,7 +13,8 @@
  *   gpsiq_nav_message(roll), next ephemeris set,
  *   allocate()                                   the 30 s refresh, gps.c:2870-2909
  *
- *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin>
+ *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
+ *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -33,6 +34,11 @@
  * noise has that rms per component, in output steps, and saturates instead of wrapping; --qmax <n> is the clamp (default: full scale
  * of the format, 127 or 32767).  The multiplier is fixed for the run from the first block (gpsiq_composite_rms, gpsiq_level_mult,
  * gpsiq_set_level), so the file stays a function of the arguments alone.  Without --level the stream is the reference's.
+ * Packed output (optional, same place): --pack 4 writes GPSIQ_PK4 (one byte per complex sample, fields -7..7), --pack 2 writes
+ * GPSIQ_PK2 (two complex samples per byte, fields -1..1), the blocks back to back, through gpsiq_generate_batch_packed
+ * (include/gpsiq_rows.h, "Packed streams").  It needs --level, sample size 1 and a --qmax inside the format (default: 7 or 1, the
+ * format's own), so that the packer clamps nothing: the file is the levelled int8 stream in fewer bytes.  Anything else prints the
+ * usage and exits with code 2.
  */
 #include <math.h>
 #include <stdint.h>
@@ -136,19 +142,27 @@ int main(int argc, char **argv)
     double cn0 = NAN;
     double level_rms = NAN;
     int qmax = 0;
+    int pack = 0, pack_given = 0;
     uint64_t noise_seed = 0;
-    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 ||
+    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
                         strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0)) {       /* trailing flags */
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
+        else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--qmax") == 0) qmax = atoi(argv[argc - 1]);
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
-    if (argc != 11 && argc != 12) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n]\n", argv[0]);
+    /* --pack: 4 or 2, with --level, sample size 1 and a clamp inside the format */
+    const int pack_qmax = pack == GPSIQ_PK4 ? 7 : 1;
+    const int pack_bad = pack_given && ((pack != GPSIQ_PK4 && pack != GPSIQ_PK2) || isnan(level_rms) || qmax < 0 || qmax > pack_qmax ||
+                                        (argc >= 10 && atoi(argv[9]) != 1));
+    if ((argc != 11 && argc != 12) || pack_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2]\n"
+                        "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n", argv[0]);
         return 2;
     }
+    if (pack && !qmax) qmax = pack_qmax;
     const int version = atoi(argv[2]), nchan = atoi(argv[7]), ss = atoi(argv[9]);
     int nblocks = atoi(argv[6]), week = atoi(argv[3]);
     double sec0 = atof(argv[4]);
@@ -220,7 +234,7 @@ int main(int argc, char **argv)
     if (!isnan(level_rms) && !(level_rms > 0.0)) { fprintf(stderr, "bad --level\n"); return 2; }
     if (qmax && isnan(level_rms)) { fprintf(stderr, "--qmax needs --level\n"); return 2; }
     int level_set = isnan(level_rms);                                          /* nothing to set without --level */
-    const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) ss;
+    const size_t blk_bytes = pack ? gpsiq_packed_block_bytes(nsamp, pack) : (size_t) 2 * (size_t) nsamp * (size_t) ss;      /* as written */
     void *buf = gpsiq_host_alloc(blk_bytes * BLOCKS_PER_CALL);
     gpsiq_chan_t *desc = malloc(sizeof *desc * BLOCKS_PER_CALL * (size_t) nchan);
     FILE *fo = fopen(argv[10], "wb");
@@ -254,7 +268,9 @@ int main(int argc, char **argv)
                 if (gpsiq_set_level(gq, &lv) != GPSIQ_OK) return die("level");
                 level_set = 1;
             }
-            if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
+            if (pack) {
+                if (gpsiq_generate_batch_packed(gq, desc, nb, nchan, nsamp, fs, pack, buf, blk_bytes, carr) != GPSIQ_OK) return die("generate packed");
+            } else if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
             if (fwrite(buf, blk_bytes, (size_t) nb, fo) != (size_t) nb) { fprintf(stderr, "short write\n"); return 1; }
         }
