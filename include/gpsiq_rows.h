@@ -281,6 +281,61 @@ int gpsiq_generate_batch_packed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch,
                                 size_t dst_block_stride,
                                 double *carr_phase_out /* [nchan], may be NULL */);
 
+/* ---- Acquisition: a blind code-phase and Doppler search on the device -------------------------------------------------------------
+ * What a receiver that knows nothing does first.  gpsiq_acquire searches ONE contiguous span of a DEVICE stream -- interleaved I,Q,
+ * int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16, elements as stored (no << 4 for int8), nsamp complex samples at src, the base 4-byte
+ * aligned and no more, as gpsiq_launch leaves a block -- for a list of satellites over a grid of ndopp Doppler bins and nshift sample
+ * shifts.  It needs no resident descriptors and no NCO mode; a stream from gpsiq_unpack is as good as any.  Every quantity up to the
+ * power is an exact integer:
+ *     ca[p][n]  = +1 where chip ((n * code_step) >> 56) % 1023 of satellite prn[p] (gpsiq_prn_code) is 0, -1 where it is 1 (the sign a
+ *                 channel with data bit 0 is rendered with: include/gpsiq.h's neg), for n in [0, ncoh); n * code_step is the exact
+ *                 product, code_step in units of 2^-56 chip per sample as gpsiq_qchan_t.code_step.  There is no data bit.
+ *     carrier of bin d at absolute sample m (m = 0 at src):  idx = ((m * (carr_step0 + d * carr_step_inc)) mod 2^59) >> 50, the steps
+ *                 in units of 2^-59 cycle per sample as gpsiq_qchan_t.carr_step (the sum and the product are integers; mod takes the
+ *                 non-negative residue, so only the steps' residues mod 2^59 matter);
+ *                 (rI, rQ) = (cosTable512[idx], sinTable512[idx]), the unit table gpsiq_despread uses (gain 1.0)
+ *     yi(m) = I(m)*rI + Q(m)*rQ        yq(m) = Q(m)*rI - I(m)*rQ                       (gpsiq_despread's formulas and signs)
+ *     for satellite p, bin d, shift s in [0, nshift) and dwell k in [0, nnoncoh):
+ *     Xi = sum over n < ncoh of yi(s + k*hop + n) * ca[p][n]         Xq = the same sum with yq          both exact int64
+ *     power[p][d][s], an IEEE double:  acc = 0.0; for k ascending:  acc = fl(acc + fl(fl(double(Xi)*double(Xi)) + fl(double(Xq)*double(Xq))))
+ * with no fused multiply-add anywhere (|X| < 2^44: the conversions are exact), so that a sequential float64 loop gives the same bits.
+ * Arguments: sample_size GPSIQ_SC08 or GPSIQ_SC16; ncoh a multiple of 64 with 64 <= ncoh <= 2^20; nshift >= 1, nnoncoh >= 1, hop >= 1;
+ * 1 <= ndopp <= 1024; (nshift - 1) + (nnoncoh - 1)*hop + ncoh <= nsamp; 1 <= nprn <= 32 and every prn[p] in 1..32 (a satellite may be
+ * listed twice); src not NULL and 4-byte aligned; prn and peaks not NULL: anything else is GPSIQ_E_ARG.  Bytes past
+ * 2*nsamp*sample_size are never read (nor are samples at or past (nshift - 1) + (nnoncoh - 1)*hop + ncoh).
+ * Outputs, all HOST memory:
+ *     peaks[nprn][ndopp]     the maximum of power over s and the shift it is at, the lowest s on a tie; reserved is 0
+ *     power (may be NULL)    the whole grid [nprn][ndopp][nshift], 8 bytes a cell
+ *     corr  (may be NULL)    the X themselves, gpsiq_despread_sum_t [nprn][ndopp][nnoncoh][nshift]: 16 * nprn * ndopp * nnoncoh * nshift
+ *                            bytes, also of device memory for the call -- for tests and small searches (32 satellites x 41 bins x 4
+ *                            dwells x 2600 shifts: 218 MB)
+ *     kernel_ms (may be NULL) the kernels' device time
+ * The kernels are queued on hip_stream (a hipStream_t, NULL = the null stream), i.e. behind the caller's gpsiq_launch on that stream;
+ * the call then waits, copies the results to the host arrays and returns: it is synchronous, like gpsiq_despread.  Every call
+ * overwrites its outputs; the same call twice gives the same bytes.  src may also be page-locked host memory of gpsiq_host_alloc,
+ * which the device reads in place (gpsiq_runahead --acquire searches one block so; far too slow for more than that).  (GPSIQ_ACQUIRE_KERNEL=generic in the environment, read per call,
+ * takes the generic kernel where the matrix kernels would serve: the tests' cross-check; GPSIQ_ACQUIRE_KERNEL=mfma takes the matrix
+ * kernels wherever they can serve, csrc/gpsiq_acquire_plan.h.) */
+typedef struct gpsiq_acquire_peak {
+    double  power;
+    int32_t shift;
+    int32_t reserved;
+} gpsiq_acquire_peak_t;
+int gpsiq_acquire(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                  const uint8_t *prn /* host [nprn] */, int nprn, uint64_t code_step, int64_t carr_step0, int64_t carr_step_inc, int ndopp,
+                  int nshift, int ncoh, int nnoncoh, int hop,
+                  gpsiq_acquire_peak_t *peaks /* host [nprn][ndopp] */, double *power /* host [nprn][ndopp][nshift], may be NULL */,
+                  gpsiq_despread_sum_t *corr /* host [nprn][ndopp][nnoncoh][nshift], may be NULL */, float *kernel_ms /* may be NULL */);
+/* The steps of a search at sample rate fs whose bins are f0_hz + d * df_hz (host arithmetic): rint(1.023e6 / fs * 2^56),
+ * rint(f0_hz / fs * 2^59) and rint(df_hz / fs * 2^59).  GPSIQ_E_RANGE where gpsiq_qchan_t's ranges would be left: a code step of 0
+ * or of 2^57 and more, |carr_step0| or |carr_step_inc| of 2^58 and more; GPSIQ_E_ARG for fs that is not positive and finite. */
+int gpsiq_acquire_steps(double fs, double f0_hz, double df_hz, uint64_t *code_step, int64_t *carr_step0, int64_t *carr_step_inc);
+/* The decision on one satellite's grid power[ndopp][nshift] (host arithmetic): *dopp, *shift the best cell (the lowest d, then the
+ * lowest s, on a tie); *ratio the best cell divided by the largest cell, in any bin, whose shift is more than guard samples from the
+ * best shift (|s - *shift| > guard, no wrap-around).  GPSIQ_E_RANGE if no such cell exists or that cell is 0; GPSIQ_E_ARG for a NULL
+ * argument, ndopp < 1, nshift < 1 or guard < 0. */
+int gpsiq_acquire_decide(const double *power, int ndopp, int nshift, int guard, int *dopp, int *shift, double *ratio);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -167,6 +167,21 @@ struct gpsiq_ctx {
         long           last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, units per block, tiles per block, pieces (gpsiq_pack_last_plan)
         int reserve(size_t render_bytes, size_t packed_bytes);      // first use + room for one call (0, 0: gpsiq_pack / gpsiq_unpack)
     } pack;
+    // gpsiq_acquire (gpsiq_acquire.cpp; include/gpsiq_rows.h, "Acquisition"): the satellite list, the power grid, the peaks and (where
+    // the caller asks for them) the correlations of one call on the device, the digit planes of the matrix path, the page-locked
+    // staging of list and peaks (grid and correlations cross straight into the caller's arrays), and the events the kernels are timed with
+    struct Acquire {
+        DevBuf<uint8_t>                 d_prn;    PinnedBuf<uint8_t>              h_prn;        // [nprn]
+        DevBuf<double>                  d_power;                                                // [nprn][ndopp][nshift]
+        DevBuf<gpsiq_acquire_peak_t>    d_peaks;  PinnedBuf<gpsiq_acquire_peak_t> h_peaks;      // [nprn][ndopp]
+        DevBuf<gpsiq_despread_sum_t>    d_corr;                                                 // [nprn][ndopp][nnoncoh][nshift]
+        DevBuf<uint8_t>                 d_planes;                                               // bytes (gpsiq_acquire_plan.h: scratch_bytes)
+        Event          t0, t1, t2;                      // before stage one, between the stages, behind the peaks
+        long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, scratch bytes, grid of the main kernel, k-steps
+        float          last_ms[2] = {0.0f, 0.0f};       // the last call's device time: stage one (0 for the generic kernel), the rest
+        // first use + room for one call (corr_cells 0: the correlations are not asked for; plane_bytes 0: the generic kernel)
+        int reserve(size_t cells, size_t peaks, size_t corr_cells, size_t plane_bytes);
+    } acq;
 };
 
 #define HIP_TRY(expr)                                                                        \
@@ -295,6 +310,25 @@ inline int gpsiq_ctx::Pack::reserve(size_t render_bytes, size_t packed_bytes)
     return GPSIQ_OK;
 }
 
+// (the satellite list, events and peaks on first use; every pair grows together, device side first)
+inline int gpsiq_ctx::Acquire::reserve(size_t cells, size_t npeaks, size_t corr_cells, size_t plane_bytes)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(t2.ensure(hipEventDefault));
+    HIP_TRY(d_prn.reserve(32));
+    HIP_TRY(h_prn.reserve(32));
+    if (cells > d_power.cap()) HIP_TRY(d_power.reserve(cells + cells / 4 + 256));
+    if (npeaks > std::min(d_peaks.cap(), h_peaks.cap())) {
+        const size_t cap = npeaks + npeaks / 4 + 64;
+        HIP_TRY(d_peaks.reserve(cap));
+        HIP_TRY(h_peaks.reserve(cap));
+    }
+    if (corr_cells > d_corr.cap()) HIP_TRY(d_corr.reserve(corr_cells + corr_cells / 4 + 256));
+    if (plane_bytes > d_planes.cap()) HIP_TRY(d_planes.reserve(plane_bytes + plane_bytes / 4 + 256));
+    return GPSIQ_OK;
+}
+
 // helpers of gpsiq_device.cpp the other translation unit uses
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
 gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
@@ -365,6 +399,10 @@ int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const vo
                       void *dst_dev, size_t dst_stride, void *hip_stream, float *kernel_ms);
 int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int bits,
                                      void *dst_host, size_t dst_block_stride, double *carr_phase_out);
+// gpsiq_acquire.cpp: gpsiq_acquire (include/gpsiq_rows.h) itself, behind the plumbing entry "acquire"
+int gpsiq_acquire_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, void *hip_stream, const uint8_t *prn, int nprn,
+                       uint64_t code_step, int64_t carr_step0, int64_t carr_step_inc, int ndopp, int nshift, int ncoh, int nnoncoh, int hop,
+                       gpsiq_acquire_peak_t *peaks, double *power, gpsiq_despread_sum_t *corr, float *kernel_ms);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
@@ -403,6 +441,20 @@ using PackFn      = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, ui
 using UnpackFn    = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, uint32_t, uint32_t, uint64_t);
 PackFn      pack_kernel(int fmt, int bits);
 UnpackFn    unpack_kernel(int bits, int fmt);
+// the acquisition kernels (gpsiq_acquire_kernels.hip).  generic: stream, tables, satellites, nshift, ncoh, nnoncoh, hop, ndopp, code step,
+// carrier step of bin 0 and between bins (mod 2^64), power grid, correlations (may be null).  wipe: stream, tables, span, plane length,
+// ndopp, row tiles, the carrier steps, planes.  mfma: planes, tables, satellites, plane length, row tiles, nshift, ncoh, nnoncoh, hop,
+// ndopp, code step, k-steps, power grid, correlations (may be null).  peaks: power grid, its rows, nshift, peaks
+using AcquireGenericFn = void (*)(const uint8_t *, const DeviceTables *, const uint8_t *, int, int, int, int, int, uint64_t, uint64_t, uint64_t,
+                                  double *, gpsiq_despread_sum_t *);
+using AcquireWipeFn    = void (*)(const uint8_t *, const DeviceTables *, uint64_t, uint64_t, int, int, uint64_t, uint64_t, uint8_t *);
+using AcquireMfmaFn    = void (*)(const uint8_t *, const DeviceTables *, const uint8_t *, uint64_t, int, int, int, int, int, int, uint64_t, int,
+                                  double *, gpsiq_despread_sum_t *);
+using AcquirePeaksFn   = void (*)(const double *, uint64_t, int, gpsiq_acquire_peak_t *);
+AcquireGenericFn acquire_generic_kernel(int fmt);
+AcquireWipeFn    acquire_wipe_kernel(int fmt);
+AcquireMfmaFn    acquire_mfma_kernel(int digits);
+AcquirePeaksFn   acquire_peaks_kernel();
 
 // gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
 // of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)

@@ -28,7 +28,8 @@ void *gpsiq_plumbing(const char *name);
  * A sixth, "despread", is the implementation of gpsiq_despread (ibid., "Despread"; csrc/gpsiq_despread.cpp), exported by
  * libgpsiq_rows.so for the same reason, with gpsiq_despread's own signature.
  * "pack", "unpack" and "generate_batch_packed" are gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (ibid., "Packed streams";
- * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements. */
+ * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements.
+ * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise. */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -191,6 +192,10 @@ int gpsiq_despread_last_plan(const gpsiq_ctx_t *ctx, int out[4]);
 /* What the context's last gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed took (csrc/gpsiq_pack_plan.h): out[0] the grid (-1: nothing
  * was launched, or no call yet), out[1] the units per block, out[2] the tiles per block, out[3] the pieces of a batch call (0: not one). */
 int gpsiq_pack_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
+/* What the context's last gpsiq_acquire took (csrc/gpsiq_acquire_plan.h): out[0] the kernel (0 generic, 1 mfma; -1: no call yet, or one
+ * that failed), out[1] the bytes of digit planes, out[2] the workgroups of the main kernel, out[3] the k-steps of the matrix kernel;
+ * ms (may be NULL): the device time of stage one (0 for the generic kernel) and of the rest. */
+int gpsiq_acquire_last_plan(const gpsiq_ctx_t *ctx, long long out[4], float ms[2]);
 
 #ifdef __cplusplus
 }

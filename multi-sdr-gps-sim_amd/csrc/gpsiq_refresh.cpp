@@ -696,4 +696,47 @@ int gpsiq_cn0_estimate(const gpsiq_despread_sum_t *sums, int count, int seg_len,
     return GPSIQ_OK;
 }
 
+// include/gpsiq_rows.h, "Acquisition": the steps of a search, in gpsiq_qchan_t's units and ranges
+int gpsiq_acquire_steps(double fs, double f0_hz, double df_hz, uint64_t *code_step, int64_t *carr_step0, int64_t *carr_step_inc)
+{
+    if (!code_step || !carr_step0 || !carr_step_inc) return fail(GPSIQ_E_ARG, "null argument");
+    if (!(fs > 0.0) || !std::isfinite(fs)) return fail(GPSIQ_E_ARG, "bad fs %g", fs);
+    const double cs = std::rint(1.023e6 / fs * std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS));
+    const double c0 = std::rint(f0_hz / fs * std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS)), ci = std::rint(df_hz / fs * std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS));
+    const double lim = std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS - 1);
+    if (!(cs >= 1.0 && cs < std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS + 1)))
+        return fail(GPSIQ_E_RANGE, "code step %g at fs %g outside (0, 2^57)", cs, fs);
+    if (!(std::fabs(c0) < lim) || !(std::fabs(ci) < lim))
+        return fail(GPSIQ_E_RANGE, "carrier steps %g, %g at fs %g: |f / fs| must stay below 0.5", c0, ci, fs);
+    *code_step = (uint64_t) cs;
+    *carr_step0 = (int64_t) c0;
+    *carr_step_inc = (int64_t) ci;
+    return GPSIQ_OK;
+}
+
+// ibid.: the best cell of one satellite's grid against the largest cell away from its shift
+int gpsiq_acquire_decide(const double *power, int ndopp, int nshift, int guard, int *dopp, int *shift, double *ratio)
+{
+    if (!power || !dopp || !shift || !ratio) return fail(GPSIQ_E_ARG, "null argument");
+    if (ndopp < 1 || nshift < 1 || guard < 0) return fail(GPSIQ_E_ARG, "bad grid %d x %d / guard %d", ndopp, nshift, guard);
+    int bd = 0, bs = 0;
+    double best = power[0];
+    for (int d = 0; d < ndopp; ++d)
+        for (int s = 0; s < nshift; ++s)
+            if (power[(size_t) d * (size_t) nshift + (size_t) s] > best) { best = power[(size_t) d * (size_t) nshift + (size_t) s]; bd = d; bs = s; }
+    *dopp = bd; *shift = bs;
+    bool have = false;
+    double floor_max = 0.0;
+    for (int d = 0; d < ndopp; ++d)
+        for (int s = 0; s < nshift; ++s) {
+            if ((int64_t) s - bs <= guard && (int64_t) bs - s <= guard) continue;
+            const double v = power[(size_t) d * (size_t) nshift + (size_t) s];
+            if (!have || v > floor_max) { floor_max = v; have = true; }
+        }
+    if (!have) return fail(GPSIQ_E_RANGE, "no cell more than %d samples from shift %d", guard, bs);
+    if (!(floor_max > 0.0)) return fail(GPSIQ_E_RANGE, "the largest cell away from the peak is %g", floor_max);
+    *ratio = best / floor_max;
+    return GPSIQ_OK;
+}
+
 }  // extern "C"

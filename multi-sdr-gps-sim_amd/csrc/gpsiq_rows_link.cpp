@@ -102,3 +102,16 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_packe
     static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_chan_t *, int, int, int, double, int, void *, size_t, double *)>("generate_batch_packed");
     return f(ctx, ch, nblocks, nchan, nsamp, fs, bits, dst_host, dst_block_stride, carr_phase_out);
 }
+
+// The acquisition search runs on the context's device (csrc/gpsiq_acquire.cpp) and is exported here like the correlator (include/gpsiq_rows.h,
+// "Acquisition"); its two helpers, plain arithmetic, are in gpsiq_refresh.cpp beside gpsiq_cn0_estimate.
+extern "C" __attribute__((visibility("default"))) int gpsiq_acquire(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                                                                    const uint8_t *prn, int nprn, uint64_t code_step, int64_t carr_step0,
+                                                                    int64_t carr_step_inc, int ndopp, int nshift, int ncoh, int nnoncoh, int hop,
+                                                                    gpsiq_acquire_peak_t *peaks, double *power, gpsiq_despread_sum_t *corr, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, const void *, void *, const uint8_t *, int, uint64_t, int64_t, int64_t, int, int, int,
+                                              int, int, gpsiq_acquire_peak_t *, double *, gpsiq_despread_sum_t *, float *)>("acquire");
+    return f(ctx, nsamp, sample_size, src, hip_stream, prn, nprn, code_step, carr_step0, carr_step_inc, ndopp, nshift, ncoh, nnoncoh, hop, peaks, power, corr,
+             kernel_ms);
+}

@@ -13,7 +13,7 @@ import numpy as np
 from .abi import (CHAN_DTYPE, QCHAN_DTYPE, SC08, SC16, SINK_HACKRF, SINK_IQFILE,  # noqa: F401
                   SINK_PLUTOSDR, HACKRF_CHUNK, MAX_CHAN, elem_dtype, EPHEM_DTYPE, IONO_DTYPE, TRACK_DTYPE,
                   NAV_EPH_DTYPE, NAV_UTC_DTYPE, NAV_ALM_DTYPE, NAV_STATE_DTYPE, RINEX_EPH_DTYPE, PATCH_DTYPE,
-                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE)
+                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE, ACQ_PEAK_DTYPE)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPSIQ_LIB: another build of the library (tests/test_gpu_build.py loads the one it has just compiled on the GPU box)
@@ -159,6 +159,10 @@ _pack = _sig("gpsiq_pack", _i, _vp, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp, C.P
 _unpack = _sig("gpsiq_unpack", _i, _vp, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp, C.POINTER(C.c_float))
 _generate_batch_packed = _sig("gpsiq_generate_batch_packed", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _sz, _vp)
 _pack_last_plan = _sig("gpsiq_pack_last_plan", _i, _vp, _vp)
+_acquire = _sig("gpsiq_acquire", _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_uint64, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_float))
+_acquire_last_plan = _sig("gpsiq_acquire_last_plan", _i, _vp, _vp, _vp)
+_acquire_steps = _sig("gpsiq_acquire_steps", _i, _d, _d, _d, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_acquire_decide = _sig("gpsiq_acquire_decide", _i, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d))
 
 
 class NoiseSettings(C.Structure):
@@ -639,6 +643,23 @@ def cn0_estimate(sums, seg_len, fs):
     return cn0.value, one.value
 
 
+def acquire_steps(fs, f0_hz, df_hz):
+    """gpsiq_acquire_steps: (code_step, carr_step0, carr_step_inc) of a search at sample rate fs whose bins are f0_hz + d * df_hz."""
+    cs, c0, ci = C.c_uint64(0), C.c_int64(0), C.c_int64(0)
+    _check(_acquire_steps(float(fs), float(f0_hz), float(df_hz), C.byref(cs), C.byref(c0), C.byref(ci)))
+    return int(cs.value), int(c0.value), int(ci.value)
+
+
+def acquire_decide(power, guard):
+    """gpsiq_acquire_decide on one satellite's grid power[ndopp][nshift]: (bin, shift, ratio of the best cell to the largest cell more
+    than `guard` samples from its shift)."""
+    g = np.ascontiguousarray(power, dtype=np.float64)
+    assert g.ndim == 2
+    d, s, r = _i(0), _i(0), _d(0.0)
+    _check(_acquire_decide(_p(g) if g.size else None, int(g.shape[0]), int(g.shape[1]), int(guard), C.byref(d), C.byref(s), C.byref(r)))
+    return d.value, s.value, r.value
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -861,6 +882,31 @@ class Context:
         out = np.zeros((nb, stride), dtype=np.uint8)
         _check(_generate_batch_packed(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(bits), _p(out), stride, co))
         return out[:, :plen]
+
+    def acquire(self, nsamp, sample_size, device_ptr, prn, code_step, carr_step0, carr_step_inc, ndopp, nshift, ncoh, nnoncoh=1, hop=None,
+                stream=None, power=True, corr=False):
+        """gpsiq_acquire: search the nsamp complex samples at device_ptr for the satellites `prn` over ndopp bins and nshift shifts ->
+        (peaks ACQ_PEAK_DTYPE [nprn][ndopp], power float64 [nprn][ndopp][nshift] or None, corr DESPREAD_SUM_DTYPE
+        [nprn][ndopp][nnoncoh][nshift] or None, kernel milliseconds).  hop: samples between dwells (default ncoh)."""
+        prn = np.ascontiguousarray(prn, dtype=np.uint8).ravel()
+        hop = int(ncoh if hop is None else hop)
+        shape = (len(prn), max(int(ndopp), 0))
+        peaks = np.zeros(shape, dtype=ACQ_PEAK_DTYPE)
+        pw = np.zeros(shape + (max(int(nshift), 0),), dtype=np.float64) if power else None
+        cr = np.zeros(shape + (max(int(nnoncoh), 0), max(int(nshift), 0)), dtype=DESPREAD_SUM_DTYPE) if corr else None
+        ms = C.c_float(0.0)
+        _check(_acquire(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(stream or 0), _p(prn) if len(prn) else None, len(prn),
+                        int(code_step), int(carr_step0), int(carr_step_inc), int(ndopp), int(nshift), int(ncoh), int(nnoncoh), hop, _p(peaks),
+                        None if pw is None else _p(pw), None if cr is None else _p(cr), C.byref(ms)))
+        return peaks, pw, cr, float(ms.value)
+
+    def acquire_last_plan(self):
+        """What the last acquire() took: (kernel name or None, bytes of digit planes, workgroups of the main kernel, k-steps,
+        milliseconds of stage one, milliseconds of the rest)."""
+        out = (C.c_longlong * 4)()
+        ms = (C.c_float * 2)()
+        _check(_acquire_last_plan(self._h, out, ms))
+        return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3]), float(ms[0]), float(ms[1])
 
     def pack_last_plan(self):
         """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""

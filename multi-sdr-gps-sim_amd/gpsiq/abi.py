@@ -92,3 +92,6 @@ EPHEM_SETS, MAX_SAT = 13, 32
 DESPREAD_SUM_DTYPE = np.dtype([("i", "<i8"), ("q", "<i8")], align=True)
 BLOCK_STATS_DTYPE = np.dtype([("sum_i", "<i8"), ("sum_q", "<i8"), ("sumsq_i", "<u8"), ("sumsq_q", "<u8"), ("clip_i", "<u4"), ("clip_q", "<u4")], align=True)
 assert DESPREAD_SUM_DTYPE.itemsize == 16 and BLOCK_STATS_DTYPE.itemsize == 40
+# gpsiq_acquire (include/gpsiq_rows.h, "Acquisition"): gpsiq_acquire_peak_t
+ACQ_PEAK_DTYPE = np.dtype([("power", "<f8"), ("shift", "<i4"), ("reserved", "<i4")], align=True)
+assert ACQ_PEAK_DTYPE.itemsize == 16

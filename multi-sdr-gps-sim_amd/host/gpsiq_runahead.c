@@ -14,7 +14,7 @@
  *   allocate()                                   the 30 s refresh, gps.c:2870-2909
  *
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
- *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2]
+ *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -39,6 +39,12 @@
  * (include/gpsiq_rows.h, "Packed streams").  It needs --level, sample size 1 and a --qmax inside the format (default: 7 or 1, the
  * format's own), so that the packer clamps nothing: the file is the levelled int8 stream in fewer bytes.  Anything else prints the
  * usage and exits with code 2.
+ * Acquisition (optional, same place, no value): --acquire searches the run's FIRST block, as rendered, for every satellite 1..32 the way
+ * a receiver that knows nothing would (gpsiq_acquire, include/gpsiq_rows.h, "Acquisition"): 21 Doppler bins of 500 Hz over +-5 kHz, every
+ * shift of one millisecond, 4 dwells one millisecond apart, each the largest multiple of 64 samples within a millisecond; and prints one
+ * line per satellite -- the best bin in Hz, its shift, and gpsiq_acquire_decide's ratio at a guard of 3 samples (" rendered gain g" behind
+ * the satellites the block holds, g the descriptor's gain: with --cn0 c such a satellite is at c + 20 log10 g dB-Hz).  The block is searched where it lies: the page-locked buffer of gpsiq_host_alloc is device-accessible.
+ * Not with --pack (the search reads int8 / int16 elements); it needs 64 samples or more in a millisecond and five milliseconds in a block.
  */
 #include <math.h>
 #include <stdint.h>
@@ -137,6 +143,34 @@ static int refresh_ephemeris(struct host_state *h, double t)
     return 0;
 }
 
+/* --acquire: the blind search of one rendered block (page-locked, so the device reads it in place), one line per satellite */
+#define ACQ_BINS 21
+static int run_acquire(gpsiq_ctx_t *gq, const void *block, int nsamp, int ss, double fs, int ms, int ncoh, const gpsiq_chan_t *desc, int nchan)
+{
+    uint8_t prn[GPSIQ_MAX_SAT];
+    static gpsiq_acquire_peak_t peaks[GPSIQ_MAX_SAT][ACQ_BINS];
+    uint64_t code_step;
+    int64_t step0, step_inc;
+    for (int p = 0; p < GPSIQ_MAX_SAT; ++p) prn[p] = (uint8_t) (p + 1);
+    if (gpsiq_acquire_steps(fs, -5000.0, 500.0, &code_step, &step0, &step_inc) != GPSIQ_OK) return -1;
+    double *power = malloc(sizeof(double) * GPSIQ_MAX_SAT * ACQ_BINS * (size_t) ms);
+    if (!power) return -1;
+    if (gpsiq_acquire(gq, nsamp, ss, block, NULL, prn, GPSIQ_MAX_SAT, code_step, step0, step_inc, ACQ_BINS, ms, ncoh, 4, ms, &peaks[0][0], power, NULL,
+                      NULL) != GPSIQ_OK) { free(power); return -1; }
+    for (int p = 0; p < GPSIQ_MAX_SAT; ++p) {
+        int bin = 0, shift = 0, rendered = 0;
+        double ratio = 0.0, gain = 0.0;
+        if (gpsiq_acquire_decide(power + (size_t) p * ACQ_BINS * (size_t) ms, ACQ_BINS, ms, 3, &bin, &shift, &ratio) != GPSIQ_OK) ratio = 0.0;
+        for (int i = 0; i < nchan; ++i)
+            if (desc[i].prn == p + 1) { rendered = 1; gain = desc[i].gain; }
+        printf("acquire PRN %2d  %+6.0f Hz  shift %5d  ratio %.4f", p + 1, -5000.0 + 500.0 * bin, shift, ratio);
+        if (rendered) printf("  rendered gain %.4f", gain);
+        printf("\n");
+    }
+    free(power);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     double cn0 = NAN;
@@ -144,8 +178,11 @@ int main(int argc, char **argv)
     int qmax = 0;
     int pack = 0, pack_given = 0;
     uint64_t noise_seed = 0;
-    while (argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
-                        strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0)) {       /* trailing flags */
+    int acquire = 0;
+    for (;;) {                                                                                                   /* trailing flags */
+        if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
+        if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
+                        strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
@@ -153,13 +190,17 @@ int main(int argc, char **argv)
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
+    /* --acquire: rendered elements, a millisecond of 64 samples or more, five of them in a block */
+    const int acq_ms = argc >= 9 ? (int) floor(atof(argv[8]) / 1000.0 + 0.5) : 0, acq_ncoh = acq_ms / 64 * 64;
+    const int acq_bad = acquire && (pack_given || (argc >= 9 && (acq_ncoh < 64 || (int) floor(atof(argv[8]) / 10.0 + 0.5) < 4 * acq_ms + acq_ncoh)));
     /* --pack: 4 or 2, with --level, sample size 1 and a clamp inside the format */
     const int pack_qmax = pack == GPSIQ_PK4 ? 7 : 1;
     const int pack_bad = pack_given && ((pack != GPSIQ_PK4 && pack != GPSIQ_PK2) || isnan(level_rms) || qmax < 0 || qmax > pack_qmax ||
                                         (argc >= 10 && atoi(argv[9]) != 1));
-    if ((argc != 11 && argc != 12) || pack_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2]\n"
-                        "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n", argv[0]);
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire]\n"
+                        "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
+                        "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -272,6 +313,7 @@ int main(int argc, char **argv)
                 if (gpsiq_generate_batch_packed(gq, desc, nb, nchan, nsamp, fs, pack, buf, blk_bytes, carr) != GPSIQ_OK) return die("generate packed");
             } else if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
+            if (acquire && done == 0 && b == 0 && run_acquire(gq, buf, nsamp, ss, fs, acq_ms, acq_ncoh, desc, nchan) != 0) return die("acquire");
             if (fwrite(buf, blk_bytes, (size_t) nb, fo) != (size_t) nb) { fprintf(stderr, "short write\n"); return 1; }
         }
         done += n;
