@@ -17,42 +17,12 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_acquire_geometry.h"
+#include "gpsiq_signal.h"
 
 namespace gpsiq {
 namespace {
 
 typedef int acq_i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint64_t kAcqCarrMask = (UINT64_C(1) << GPSIQ_CARR_FRAC_BITS) - 1;
-constexpr uint64_t kAcqCodeFracMask = (UINT64_C(1) << GPSIQ_CODE_FRAC_BITS) - 1;
-
-__device__ __forceinline__ int acq_sin512(const int16_t *qw, int k)
-{
-    k &= 511;
-    const int h = k & 255;
-    const int v = qw[h < 128 ? h : 255 - h];
-    return k < 256 ? v : -v;
-}
-
-// the unit table: entry k = cosTable512[k] | sinTable512[k] << 16 (gain 1.0), as the correlator stages it
-__device__ __forceinline__ void acq_stage_unit(const DeviceTables *__restrict__ tab, uint32_t *unit)
-{
-    for (int k = threadIdx.x; k < 512; k += kAcqThreads)
-        unit[k] = ((uint32_t) acq_sin512(tab->quarter_wave, k + 128) & 0xffffu) | ((uint32_t) acq_sin512(tab->quarter_wave, k) << 16);
-}
-
-// sample m of the stream as stored; the caller guarantees m < nsamp
-template <int FMT>
-__device__ __forceinline__ void acq_load_iq(const uint8_t *__restrict__ src, uint64_t m, int *i, int *q)
-{
-    if (FMT == GPSIQ_SC16) {
-        const uint32_t v = reinterpret_cast<const uint32_t *>(src)[m];
-        *i = (int16_t) (v & 0xffffu); *q = (int32_t) v >> 16;
-    } else {
-        const uint32_t v = reinterpret_cast<const uint16_t *>(src)[m];
-        *i = (int8_t) (v & 0xffu); *q = (int8_t) (v >> 8);
-    }
-}
 
 // +1 / -1 of replica sample n: chip ((n * code_step) >> 56) % 1023 of the satellite whose packed code is ext (bit set: -1)
 __device__ __forceinline__ int acq_code(const uint32_t *ext, uint64_t code_step, uint32_t n)
@@ -77,7 +47,7 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_generic(
     __shared__ uint32_t unit[512];
     __shared__ uint32_t ext[kPrnExtWords];
     const int p = blockIdx.z, d = blockIdx.y;
-    acq_stage_unit(tab, unit);
+    stage_unit<kAcqThreads>(tab, unit);
     if (threadIdx.x < kPrnExtWords) ext[threadIdx.x] = tab->prn_ext[prns[p] - 1][threadIdx.x];
     __syncthreads();
     const uint64_t s = (uint64_t) blockIdx.x * kAcqThreads + threadIdx.x;
@@ -93,17 +63,17 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_generic(
         uint32_t chip = 0;
         for (int n = 0; n < ncoh; ++n) {
             int si, sq;
-            acq_load_iq<FMT>(src, m0 + (uint64_t) n, &si, &sq);
-            const uint32_t v = unit[(uint32_t) ((P & kAcqCarrMask) >> (GPSIQ_CARR_FRAC_BITS - 9))];
+            load_iq<FMT>(src, m0 + (uint64_t) n, &si, &sq);           // (every sample a shift reads lies inside the stream)
+            const uint32_t v = unit[(uint32_t) ((P & kCarrFracMask) >> (GPSIQ_CARR_FRAC_BITS - 9))];
             const int rc = (int16_t) (v & 0xffffu), rs = (int32_t) v >> 16;
             const bool neg = (ext[chip >> 5] >> (chip & 31)) & 1u;
             const int yi = si * rc + sq * rs, yq = sq * rc - si * rs;      // each product below 2^24
             xi += (int64_t) (neg ? -yi : yi);
             xq += (int64_t) (neg ? -yq : yq);
             P += step;
-            frac += code_step & kAcqCodeFracMask;
+            frac += code_step & kCodeFracMask;
             chip += (uint32_t) (code_step >> GPSIQ_CODE_FRAC_BITS) + (uint32_t) (frac >> GPSIQ_CODE_FRAC_BITS);      // at most 256 chips on
-            frac &= kAcqCodeFracMask;
+            frac &= kCodeFracMask;
             if (chip >= GPSIQ_CA_SEQ_LEN) chip -= GPSIQ_CA_SEQ_LEN;
         }
         if (corr) {
@@ -131,7 +101,7 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_wipe(
 {
     constexpr int ND = FMT == GPSIQ_SC16 ? 4 : 3;
     __shared__ uint32_t unit[512];
-    acq_stage_unit(tab, unit);
+    stage_unit<kAcqThreads>(tab, unit);
     __syncthreads();
     const uint64_t quads = npad / 4;
     const uint64_t t = (uint64_t) blockIdx.x * kAcqThreads + threadIdx.x;
@@ -146,8 +116,8 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_wipe(
             const uint64_t m = m4 + (uint64_t) j;
             if (m >= span) break;
             int si, sq;
-            acq_load_iq<FMT>(src, m, &si, &sq);
-            const uint32_t v = unit[(uint32_t) (((m * step) & kAcqCarrMask) >> (GPSIQ_CARR_FRAC_BITS - 9))];
+            load_iq<FMT>(src, m, &si, &sq);
+            const uint32_t v = unit[(uint32_t) (((m * step) & kCarrFracMask) >> (GPSIQ_CARR_FRAC_BITS - 9))];
             const int rc = (int16_t) (v & 0xffffu), rs = (int32_t) v >> 16;
             int y[2] = {si * rc + sq * rs, sq * rc - si * rs};
 #pragma unroll

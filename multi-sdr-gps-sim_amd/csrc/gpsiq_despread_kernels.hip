@@ -6,7 +6,7 @@
 //   despread_generic   one sample per lane per step, every quantity of the closed form at full width (any rate): the fallback for
 //                      sample rates too low for the row kernel, and the second implementation the tests hold the row kernel against
 //   despread_rows      the synthesis row loop run backwards: a row is 64 consecutive samples, a wave owns a run of rows, per channel
-//                      two 64-bit NCO words per lane and one 32-chip sign window per row (built as synth_rows builds them)
+//                      two 64-bit NCO words per lane and one 32-chip sign window per row (gpsiq_signal.h)
 // The replica comes from ONE unit table for all channels (512 entries, cos | sin << 16, 2 KB of LDS).  No MFMA: per sample and
 // channel the work is one 2x2 integer rotation, two v_dot2_i32_i16.
 #include <hip/hip_runtime.h>
@@ -15,45 +15,15 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_despread_geometry.h"
+#include "gpsiq_signal.h"
 
 namespace gpsiq {
 namespace {
 
 constexpr int kDsMaxChan = GPSIQ_MAX_CHAN;
-constexpr uint64_t kDsCodeFracMask = (UINT64_C(1) << GPSIQ_CODE_FRAC_BITS) - 1;
 constexpr int kDsThreads = kDespreadWaves * 64;
 
 typedef short ds_s16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int ds_sin512(const int16_t *qw, int k)
-{
-    k &= 511;
-    const int h = k & 255;
-    const int v = qw[h < 128 ? h : 255 - h];
-    return k < 256 ? v : -v;
-}
-
-// the unit table: entry k = cosTable512[k] | sinTable512[k] << 16, what (int)(table * 1.0) gives
-__device__ __forceinline__ void stage_unit(const DeviceTables *__restrict__ tab, uint32_t *unit)
-{
-    for (int k = threadIdx.x; k < 512; k += kDsThreads)
-        unit[k] = ((uint32_t) ds_sin512(tab->quarter_wave, k + 128) & 0xffffu) | ((uint32_t) ds_sin512(tab->quarter_wave, k) << 16);
-}
-
-// one sample of the stream as stored (no << 4 for int8); lanes past the block end read nothing: the guard bytes never enter a sum
-template <int FMT>
-__device__ __forceinline__ void load_iq(const uint8_t *__restrict__ blk_src, uint32_t n, bool valid, int *i, int *q)
-{
-    *i = 0; *q = 0;
-    if (!valid) return;
-    if (FMT == GPSIQ_SC16) {
-        const uint32_t v = reinterpret_cast<const uint32_t *>(blk_src)[n];
-        *i = (int16_t) (v & 0xffffu); *q = (int32_t) v >> 16;
-    } else {
-        const uint32_t v = reinterpret_cast<const uint16_t *>(blk_src)[n];
-        *i = (int8_t) (v & 0xffu); *q = (int8_t) (v >> 8);
-    }
-}
 
 __device__ __forceinline__ int64_t wave_sum(int64_t v)
 {
@@ -112,7 +82,7 @@ __global__ __launch_bounds__(kDsThreads) void despread_generic(
     for (int i = tid; i < nchan * 12; i += kDsThreads)
         reinterpret_cast<uint32_t *>(qs)[i] = reinterpret_cast<const uint32_t *>(q_blk)[i];
     __syncthreads();
-    stage_unit(tab, unit);
+    stage_unit<kDsThreads>(tab, unit);
     for (int e = tid; e < nchan * kPrnExtWords; e += kDsThreads) {
         const int c = e / kPrnExtWords, w = e % kPrnExtWords;
         ext[c][w] = qs[c].prn ? tab->prn_ext[qs[c].prn - 1][w] : 0u;
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(kDsThreads) void despread_generic(
         for (int r = 0; r < rows; ++r) {
             const uint32_t n = n0 + (uint32_t) r * 64u;
             int si, sq;
-            load_iq<FMT>(blk_src, n, n < (uint32_t) nsamp, &si, &sq);
+            load_iq<FMT>(blk_src, n, &si, &sq, n < (uint32_t) nsamp);
             st.add(si, sq, n < (uint32_t) nsamp, clip);
         }
         st.flush(stats + blk, lane);
@@ -147,13 +117,10 @@ __global__ __launch_bounds__(kDsThreads) void despread_generic(
         for (int r = 0; r < rows; ++r) {
             const uint32_t n = n0 + (uint32_t) r * 64u;
             int si, sq;
-            load_iq<FMT>(blk_src, n, n < (uint32_t) nsamp, &si, &sq);
-            const uint64_t P = q.carr_phase + (uint64_t) q.carr_step * (uint64_t) n;
-            const uint32_t idx = (uint32_t) (P >> (GPSIQ_CARR_FRAC_BITS - 9)) & 511u;
-            const unsigned __int128 T = (unsigned __int128) q.code_frac + (unsigned __int128) q.code_step * (unsigned __int128) n;
-            const uint64_t A = (uint64_t) q.chip0 + (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-            const uint32_t chip = (uint32_t) (A % GPSIQ_CA_SEQ_LEN);
-            const uint32_t bit = (uint32_t) ((q.icode + A / GPSIQ_CA_SEQ_LEN) / 20);
+            load_iq<FMT>(blk_src, n, &si, &sq, n < (uint32_t) nsamp);
+            const uint32_t idx = carrier_index(q, n);
+            const uint64_t A = chip_count(q, n);
+            const uint32_t chip = code_chip(A), bit = data_bit(q, A);
             const uint32_t neg = ((ext[c][chip >> 5] >> (chip & 31)) ^ (q.nav_bits >> (bit & 31))) & 1u;
             const uint32_t v = unit[idx];
             const int tc = (int16_t) (v & 0xffffu), ts = (int32_t) v >> 16;
@@ -171,11 +138,8 @@ __global__ __launch_bounds__(kDsThreads) void despread_generic(
 }
 
 // ---------------------------------------------------------------------------
-// Row kernel.  Rows, windows and NCO words are those of the synthesis row kernels (gpsiq_kernels.hip):
-//   code word     [chips mod 256 : 8][fraction : 56], carrier word [5 don't-care][LUT index : 9][fraction : 50], stepped by one row
-//                 with a 64-bit add each; the per-lane start values are exact (they wrap mod 2^64 = mod 256 chips / mod 32 cycles);
-//   window        W[A mod 32] is the sign (chip xor data bit) of absolute chip A, one wave-uniform word per (channel, row), built
-//                 kDespreadChunkRows rows at a time into LDS by the wave itself: lane (c, g) walks sixteen rows of channel c.
+// Row kernel.  Rows, NCO words and sign windows are those of the synthesis row kernels (gpsiq_signal.h); the windows are built
+// kDespreadChunkRows rows at a time into LDS by the wave itself: lane (c, g) walks sixteen rows of channel c.
 // Per row a lane loads its sample ONCE, takes the stream statistics from it and packs it twice, (I, Q) and (Q, I).  Per channel:
 //   the sign enters as half a carrier cycle (the table is antisymmetric: entry k + 256 is minus entry k);
 //   entry k is (cos, sin), entry 511 - k is (cos, -sin) (the table is a half-sample-offset sine: sin[511 - k] = -sin[k] and
@@ -228,7 +192,7 @@ __global__ __launch_bounds__(kDsThreads, NCH <= 8 ? 4 : 2) void despread_rows(
     for (int i = tid; i < NCH * 12; i += kDsThreads)
         reinterpret_cast<uint32_t *>(qs)[i] = i < nq * 12 ? reinterpret_cast<const uint32_t *>(q_blk)[i] : 0u;
     __syncthreads();
-    stage_unit(tab, unit);
+    stage_unit<kDsThreads>(tab, unit);
     for (int e = tid; e < NCH * kPrnExtWords; e += kDsThreads) {
         const int c = e / kPrnExtWords, w = e % kPrnExtWords;
         ext[c][w] = qs[c].prn ? tab->prn_ext[qs[c].prn - 1][w] : 0u;
@@ -248,16 +212,8 @@ __global__ __launch_bounds__(kDsThreads, NCH <= 8 ? 4 : 2) void despread_rows(
     // ---- per-lane NCO state of every channel (steps in SGPRs via scalar loads, as in the synthesis) -----
     uint64_t P[NCH], Q[NCH], dP[NCH], dQ[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const bool have = c < nchan;
-        const uint64_t p0 = have ? q_blk[c].carr_phase : 0u, ps = have ? (uint64_t) q_blk[c].carr_step : 0u;
-        const uint64_t f0 = have ? q_blk[c].code_frac : 0u, cs = have ? q_blk[c].code_step : 0u;
-        const uint64_t c0 = have ? (uint64_t) q_blk[c].chip0 : 0u;
-        P[c] = p0 + ps * (uint64_t) n0;
-        Q[c] = (c0 << GPSIQ_CODE_FRAC_BITS) + f0 + cs * (uint64_t) n0;
-        dP[c] = ps * 64u;
-        dQ[c] = cs * 64u;
-    }
+    for (int c = 0; c < NCH; ++c)
+        nco_start(q_blk, c, c < nchan, n0, &P[c], &Q[c], &dP[c], &dQ[c]);
     int32_t acc_i[NCH], acc_q[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) acc_i[c] = acc_q[c] = 0;
@@ -273,40 +229,12 @@ __global__ __launch_bounds__(kDsThreads, NCH <= 8 ? 4 : 2) void despread_rows(
                 const gpsiq_qchan_t &q = qs[c];
                 const bool on = q.prn != 0;
                 const uint32_t n_row = (uint32_t) (row_first + row0 + g * kRun) * 64u;
-                const unsigned __int128 T = (unsigned __int128) q.code_frac + (unsigned __int128) q.code_step * (unsigned __int128) n_row;
-                const uint64_t A = (uint64_t) q.chip0 + (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-                uint64_t fr = (uint64_t) T & kDsCodeFracMask;
-                uint32_t k = (uint32_t) (A % GPSIQ_CA_SEQ_LEN);          // chip inside the period
-                const uint64_t ic = q.icode + A / GPSIQ_CA_SEQ_LEN;
-                uint32_t bit = (uint32_t) (ic / 20), icur = (uint32_t) (ic % 20);
-                uint32_t a5 = (uint32_t) A;                                // only A mod 32 is used
-                const uint64_t row_step = q.code_step * 64u;
-                const uint32_t d_int = (uint32_t) (row_step >> GPSIQ_CODE_FRAC_BITS);
-                const uint64_t d_fr = row_step & kDsCodeFracMask;
-                const uint32_t nav = q.nav_bits;
+#include "gpsiq_window_setup.inc"
 #pragma unroll 4
                 for (int r = 0; r < kRun; ++r) {
-                    // 32 chips starting at chip k of the (wrap-extended) code
-                    const uint32_t lo = ext[c][k >> 5], hi = ext[c][(k >> 5) + 1];
-                    uint32_t S = __builtin_amdgcn_alignbit(hi, lo, k & 31u);
-                    // chips at window positions >= 1023-k belong to the next code period
-                    const uint32_t to_wrap = GPSIQ_CA_SEQ_LEN - k;
-                    const uint32_t next_mask = to_wrap < 32u ? (0xffffffffu << to_wrap) : 0u;
-                    const uint32_t bit_next = icur == 19u ? bit + 1u : bit;
-                    const uint32_t d0 = 0u - ((nav >> (bit & 31u)) & 1u);
-                    const uint32_t d1 = 0u - ((nav >> (bit_next & 31u)) & 1u);
-                    S ^= (d0 & ~next_mask) ^ (d1 & next_mask);
-                    win[wave][g * kRun + r][c] = on ? __builtin_rotateleft32(S, a5 & 31u) : 0u;
-                    // advance one row (less than 32 chips: one period wrap at most)
-                    fr += d_fr;
-                    const uint32_t adv = d_int + (uint32_t) (fr >> GPSIQ_CODE_FRAC_BITS);
-                    fr &= kDsCodeFracMask;
-                    a5 += adv;
-                    k += adv;
-                    if (k >= GPSIQ_CA_SEQ_LEN) {
-                        k -= GPSIQ_CA_SEQ_LEN;
-                        if (++icur == 20u) { icur = 0u; ++bit; }
-                    }
+#include "gpsiq_window_row.inc"
+                    win[wave][g * kRun + r][c] = on ? window_word(S, a5) : 0u;
+#include "gpsiq_window_step.inc"
                 }
             }
         }
@@ -319,7 +247,7 @@ __global__ __launch_bounds__(kDsThreads, NCH <= 8 ? 4 : 2) void despread_rows(
             const uint32_t n = n0 + (uint32_t) (row0 + r) * 64u;
             const bool valid = n < (uint32_t) nsamp;
             int si, sq;
-            load_iq<FMT>(blk_src, n, valid, &si, &sq);
+            load_iq<FMT>(blk_src, n, &si, &sq, valid);
             st.add(si, sq, valid, clip);
             const uint32_t iq = ((uint32_t) si & 0xffffu) | ((uint32_t) sq << 16);        // (I, Q)
             const uint32_t qi = __builtin_amdgcn_alignbit(iq, iq, 16u);                      // (Q, I)

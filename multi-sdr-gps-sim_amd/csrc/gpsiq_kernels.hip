@@ -17,21 +17,13 @@
 #include "gpsiq_ctx.h"
 #include "gpsiq_geometry.h"
 #include "gpsiq_noise.h"
+#include "gpsiq_signal.h"
 
 namespace gpsiq {
 
 constexpr int kMaxChan = GPSIQ_MAX_CHAN;
-constexpr uint64_t kCodeFracMask = (UINT64_C(1) << GPSIQ_CODE_FRAC_BITS) - 1;
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int dev_sin512(const int16_t *qw, int k)
-{
-    k &= 511;
-    int h = k & 255;
-    int v = qw[h < 128 ? h : 255 - h];
-    return k < 256 ? v : -v;
-}
 
 // Workgroup prologue shared by both kernels: descriptors, gain LUTs and C/A codes to LDS.
 template <int NT>
@@ -129,14 +121,9 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
         for (int c = 0; c < nchan; ++c) {
             const gpsiq_qchan_t &q = qs[c];
             if (q.prn == 0) continue;
-            const uint64_t P = q.carr_phase + (uint64_t) q.carr_step * (uint64_t) n;
-            const uint32_t idx = (uint32_t) (P >> (GPSIQ_CARR_FRAC_BITS - 9)) & 511u;
-            const unsigned __int128 T = (unsigned __int128) q.code_frac +
-                                        (unsigned __int128) q.code_step * (unsigned __int128) n;
-            const uint64_t A = (uint64_t) q.chip0 + (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-            const uint32_t chip = (uint32_t) (A % GPSIQ_CA_SEQ_LEN);
-            const uint64_t period = A / GPSIQ_CA_SEQ_LEN;
-            const uint32_t bit = (uint32_t) ((q.icode + period) / 20);
+            const uint32_t idx = carrier_index(q, n);
+            const uint64_t A = chip_count(q, n);
+            const uint32_t chip = code_chip(A), bit = data_bit(q, A);
             const uint32_t neg = ((ext[c][chip >> 5] >> (chip & 31)) ^ (q.nav_bits >> (bit & 31))) & 1u;
             const uint32_t v = lut[c][idx];
             const int tc = (int16_t) (v & 0xffffu), ts = (int16_t) (v >> 16);
@@ -153,16 +140,12 @@ __global__ __launch_bounds__(kGenericThreads) void synth_generic(
 //   * IQ stores are one contiguous 128/256-byte run per wave instruction,
 //   * the carrier LUT indices of a wave are (nearly) consecutive -> conflict-free
 //     ds_read_b32 with broadcasts,
-//   * all lanes of a row sit inside one 32-chip window of the C/A code, which is a
-//     wave-uniform 32-bit word W (chip xor nav bit) prepared once per (channel,row):
-//     W[A mod 32] is the sign of absolute chip A, so a lane needs only the low 5
-//     bits of its own chip counter to find its sign — no mod-1023, no divisions.
+//   * all lanes of a row sit inside one 32-chip window of the C/A code, a wave-uniform
+//     word prepared once per (channel,row), in which a lane finds its sign with the low
+//     5 bits of its own chip counter — no mod-1023, no divisions.
 // Each wave owns kRowsPerWave consecutive rows.  Per channel it keeps two 64-bit
-// per-lane accumulators (carrier phase, code phase) and steps them by one row
-// (64 samples) with a 64-bit add each; the per-lane start values are exact
-// (64x32-bit products, wrapping mod 2^64 = mod 32 cycles / mod 256 chips).
-// Code phase word: [chips mod 256 : 8][fraction : 56]; carrier word: [5 don't-care]
-// [LUT index : 9][fraction : 50].
+// per-lane NCO words (carrier phase, code phase) and steps them by one row with a
+// 64-bit add each.  (The words and the window: gpsiq_signal.h.)
 // (kWaves, kRowsPerWave and what follows from them: gpsiq_geometry.h)
 constexpr int kWinRowsPerLane = kRowsPerWave * kMaxChan / 64;   // rows one lane prepares
 
@@ -189,41 +172,12 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rows(
         if (c < nchan && qs[c].prn != 0) {
             const gpsiq_qchan_t &q = qs[c];
             const uint32_t n_row = n_wave + (uint32_t) (g * kWinRowsPerLane) * 64u;
-            const unsigned __int128 T = (unsigned __int128) q.code_frac +
-                                        (unsigned __int128) q.code_step * (unsigned __int128) n_row;
-            uint64_t A = (uint64_t) q.chip0 + (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-            uint64_t fr = (uint64_t) T & kCodeFracMask;
-            uint32_t k = (uint32_t) (A % GPSIQ_CA_SEQ_LEN);          // chip inside the period
-            const uint64_t ic = q.icode + A / GPSIQ_CA_SEQ_LEN;
-            uint32_t bit = (uint32_t) (ic / 20), icur = (uint32_t) (ic % 20);
-            uint32_t a5 = (uint32_t) A;                                // only A mod 32 is used
-            const uint64_t row_step = q.code_step * 64u;
-            const uint32_t d_int = (uint32_t) (row_step >> GPSIQ_CODE_FRAC_BITS);
-            const uint64_t d_fr = row_step & kCodeFracMask;
-            const uint32_t nav = q.nav_bits;
+#include "gpsiq_window_setup.inc"
 #pragma unroll
             for (int r = 0; r < kWinRowsPerLane; ++r) {
-                // 32 chips starting at chip k of the (wrap-extended) code
-                const uint32_t lo = ext[c][k >> 5], hi = ext[c][(k >> 5) + 1];
-                uint32_t S = __builtin_amdgcn_alignbit(hi, lo, k & 31u);
-                // chips at window positions >= 1023-k belong to the next code period
-                const uint32_t to_wrap = GPSIQ_CA_SEQ_LEN - k;
-                const uint32_t next_mask = to_wrap < 32u ? (0xffffffffu << to_wrap) : 0u;
-                const uint32_t bit_next = icur == 19u ? bit + 1u : bit;
-                const uint32_t d0 = 0u - ((nav >> (bit & 31u)) & 1u);
-                const uint32_t d1 = 0u - ((nav >> (bit_next & 31u)) & 1u);
-                S ^= (d0 & ~next_mask) ^ (d1 & next_mask);
-                win[wave][c][g * kWinRowsPerLane + r] = __builtin_rotateleft32(S, a5 & 31u);
-                // advance one row
-                fr += d_fr;
-                const uint32_t adv = d_int + (uint32_t) (fr >> GPSIQ_CODE_FRAC_BITS);
-                fr &= kCodeFracMask;
-                a5 += adv;
-                k += adv;
-                if (k >= GPSIQ_CA_SEQ_LEN) {
-                    k -= GPSIQ_CA_SEQ_LEN;
-                    if (++icur == 20u) { icur = 0u; ++bit; }
-                }
+#include "gpsiq_window_row.inc"
+                win[wave][c][g * kWinRowsPerLane + r] = window_word(S, a5);
+#include "gpsiq_window_step.inc"
             }
         }
     }
@@ -325,38 +279,12 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rowsx(
             const gpsiq_qchan_t &q = qs[c];
             const bool on = q.prn != 0;
             const uint32_t n_row = n_wave + (uint32_t) (g * kRun) * 64u;
-            const unsigned __int128 T = (unsigned __int128) q.code_frac +
-                                        (unsigned __int128) q.code_step * (unsigned __int128) n_row;
-            uint64_t A = (uint64_t) q.chip0 + (uint64_t) (T >> GPSIQ_CODE_FRAC_BITS);
-            uint64_t fr = (uint64_t) T & kCodeFracMask;
-            uint32_t k = (uint32_t) (A % GPSIQ_CA_SEQ_LEN);
-            const uint64_t ic = q.icode + A / GPSIQ_CA_SEQ_LEN;
-            uint32_t bit = (uint32_t) (ic / 20), icur = (uint32_t) (ic % 20);
-            uint32_t a5 = (uint32_t) A;
-            const uint64_t row_step = q.code_step * 64u;
-            const uint32_t d_int = (uint32_t) (row_step >> GPSIQ_CODE_FRAC_BITS);
-            const uint64_t d_fr = row_step & kCodeFracMask;
-            const uint32_t nav = q.nav_bits;
+#include "gpsiq_window_setup.inc"
 #pragma unroll 4
             for (int r = 0; r < kRun; ++r) {
-                const uint32_t lo = ext[c][k >> 5], hi = ext[c][(k >> 5) + 1];
-                uint32_t S = __builtin_amdgcn_alignbit(hi, lo, k & 31u);
-                const uint32_t to_wrap = GPSIQ_CA_SEQ_LEN - k;
-                const uint32_t next_mask = to_wrap < 32u ? (0xffffffffu << to_wrap) : 0u;
-                const uint32_t bit_next = icur == 19u ? bit + 1u : bit;
-                const uint32_t d0 = 0u - ((nav >> (bit & 31u)) & 1u);
-                const uint32_t d1 = 0u - ((nav >> (bit_next & 31u)) & 1u);
-                S ^= (d0 & ~next_mask) ^ (d1 & next_mask);
-                win[wave][g * kRun + r][c] = on ? __builtin_rotateleft32(S, a5 & 31u) : 0u;
-                fr += d_fr;
-                const uint32_t adv = d_int + (uint32_t) (fr >> GPSIQ_CODE_FRAC_BITS);
-                fr &= kCodeFracMask;
-                a5 += adv;
-                k += adv;
-                if (k >= GPSIQ_CA_SEQ_LEN) {
-                    k -= GPSIQ_CA_SEQ_LEN;
-                    if (++icur == 20u) { icur = 0u; ++bit; }
-                }
+#include "gpsiq_window_row.inc"
+                win[wave][g * kRun + r][c] = on ? window_word(S, a5) : 0u;
+#include "gpsiq_window_step.inc"
             }
         }
     }
@@ -366,18 +294,8 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rowsx(
     const uint32_t n0 = n_wave + (uint32_t) lane;
     uint64_t P[NCH], Q[NCH], dP[NCH], dQ[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        // descriptor fields through scalar loads (uniform address, read-only global):
-        // the row steps must live in SGPRs, 4 per channel, or they cost 64 VGPRs
-        const bool have = c < nchan;
-        const uint64_t p0 = have ? q_blk[c].carr_phase : 0u, ps = have ? (uint64_t) q_blk[c].carr_step : 0u;
-        const uint64_t f0 = have ? q_blk[c].code_frac : 0u, cs = have ? q_blk[c].code_step : 0u;
-        const uint64_t c0 = have ? (uint64_t) q_blk[c].chip0 : 0u;
-        P[c] = p0 + ps * (uint64_t) n0;
-        Q[c] = (c0 << GPSIQ_CODE_FRAC_BITS) + f0 + cs * (uint64_t) n0;
-        dP[c] = ps * 64u;
-        dQ[c] = cs * 64u;
-    }
+    for (int c = 0; c < NCH; ++c)
+        nco_start(q_blk, c, c < nchan, n0, &P[c], &Q[c], &dP[c], &dQ[c]);      // (the steps: 4 SGPRs per channel)
 
     const unsigned char *lut_b = reinterpret_cast<const unsigned char *>(&lut[0][0]);
     for (int r = 0; r < kRowsPerWave; ++r) {
@@ -649,6 +567,7 @@ __global__ __launch_bounds__(64) void apply_patches(
         const gpsiq_qchan_t qc = desc[(size_t) p.block * nchan + c];
         if (qc.prn != 0) {
             const uint64_t n = p.sample;
+            // (the closed form of gpsiq_signal.h, written out: with its functions this kernel's instruction stream moves)
             const uint64_t P = qc.carr_phase + (uint64_t) qc.carr_step * n;
             uint32_t idx = (uint32_t) (P >> (GPSIQ_CARR_FRAC_BITS - 9)) & 511u;
             const unsigned __int128 T = (unsigned __int128) qc.code_frac + (unsigned __int128) qc.code_step * (unsigned __int128) n;

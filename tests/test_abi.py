@@ -152,7 +152,8 @@ def test_replayed_counters_are_bound_to_the_loaded_kernel(tmp_path, monkeypatch)
     assert "gpsiq_geometry.h" in devsrc and "gpsiq_launch.cpp" not in devsrc and "gpsiq_launch_plan.h" not in devsrc
     for f in sorted(os.listdir(csrc)):
         if f not in devsrc and os.path.isfile(os.path.join(csrc, f)):
-            assert "__global__" not in open(os.path.join(csrc, f), errors="replace").read(), f
+            text = open(os.path.join(csrc, f), errors="replace").read()
+            assert "__global__" not in text and "__device__" not in text, f
     blob = b"".join(open(os.path.join(csrc, f), "rb").read() for f in devsrc)
     assert gpsiq.kernels_id() == hashlib.sha256(blob).hexdigest()[:16], "libgpsiq.so is older than its device sources: rebuild"
     sys.path.insert(0, ROOT)
