@@ -1,6 +1,7 @@
 // gpsiq_ctx.h -- the device context of libgpsiq (include/gpsiq.h: gpsiq_ctx_t), shared by the translation units of the device half:
-// gpsiq_device.cpp (context, resident descriptors, launches, the drop-in calls) and gpsiq_evaldev.cpp (the batch calls whose
-// descriptors are quantised / evaluated on the device).
+// gpsiq_device.cpp (context, resident descriptors, launches, settings), gpsiq_batch.cpp (the drop-in calls of one context),
+// gpsiq_multi.cpp (gpsiq_generate_batch_multi) and gpsiq_evaldev.cpp (the batch calls whose descriptors are quantised / evaluated
+// on the device).
 #ifndef GPSIQ_CTX_H
 #define GPSIQ_CTX_H
 
@@ -13,6 +14,7 @@
 #include "gpsiq_evalctl.h"
 #include "gpsiq_noise.h"
 #include "gpsiq_own.h"
+#include "gpsiq_pieces.h"
 
 struct gpsiq_ctx {
     template <typename T> using DevBuf = gpsiq::DevBuf<T>;
@@ -93,10 +95,8 @@ struct gpsiq_ctx {
         bool           busy = false;
     } aslot[4];
     int anext = 0;
-    // carrier carry per slot (gpsiq_generate_block)
-    uint64_t carry[GPSIQ_MAX_CHAN] = {};
-    double   handed[GPSIQ_MAX_CHAN] = {};
-    int      carry_prn[GPSIQ_MAX_CHAN] = {};
+    // carrier carry per slot (gpsiq_generate_block): one value, so that a call can put it back and a change of model forgets it
+    struct Carry { uint64_t phase[GPSIQ_MAX_CHAN] = {}; double handed[GPSIQ_MAX_CHAN] = {}; int prn[GPSIQ_MAX_CHAN] = {}; } carry;
     // GPSIQ_NCO_REFERENCE batch calls: quantised descriptors and start states of the timeline being worked through, kept
     // between calls (a fresh 1.5 MB per call is four hundred page faults on the thread everything else waits for)
     std::vector<gpsiq_qchan_t> ref_q;
@@ -329,12 +329,27 @@ inline int gpsiq_ctx::Acquire::reserve(size_t cells, size_t npeaks, size_t corr_
     return GPSIQ_OK;
 }
 
-// helpers of gpsiq_device.cpp the other translation unit uses
+// ---- what the translation units of the device half use of each other ----------------------------------------------------------
+// gpsiq_device.cpp:
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
 gpsiq::noise::Launch gpsiq_noise_at(const gpsiq_ctx *c, uint64_t block);
-double gpsiq_wall_ms();
-int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b);
-int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s);
+double gpsiq_wall_ms();                                         // GPSIQ_TRACE: host-side phase times
+int gpsiq_wait_idle(gpsiq_ctx::DescBuf &b);                     // until no launch reads the set any more
+int gpsiq_mark_use(gpsiq_ctx::DescBuf &b, hipStream_t s);       // stream s has just launched work reading the set
+// gpsiq_set_descriptors with the set's patches in the same step; no_wait: the uploads are queued, launches wait for them on the device
+int gpsiq_stage_descriptors(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblocks, int nchan, const gpsiq_patch_t *patches, int npatch, bool no_wait);
+// gpsiq_launch with the absolute block index of the resident set's block 0 (receiver noise) given by the caller
+int gpsiq_launch_abs(gpsiq_ctx *c, int block0, int nblocks, int nsamp, int sample_size, void *dst, size_t stride, hipStream_t s, int variant, uint64_t nbase);
+// seed and sigma / the level of a context, checked by the caller (gpsiq_generate_batch_multi lends context 0's); the counter stays
+int gpsiq_apply_noise(gpsiq_ctx *c, uint64_t seed, double sigma);
+int gpsiq_apply_level(gpsiq_ctx *c, uint32_t mult, int32_t qmax);
+// the clamp has to fit the format, which only a rendering call knows
+inline int gpsiq_check_level(const gpsiq_ctx *c, int sample_size)
+{
+    if (c->level.mult && c->level.qmax > (sample_size == GPSIQ_SC08 ? 127 : 32767))
+        return gpsiq::fail(GPSIQ_E_ARG, "output level: qmax %d does not fit %d-byte samples", (int) c->level.qmax, sample_size);
+    return GPSIQ_OK;
+}
 // The stream of piece k of a batch worked through in pieces.  On ONE stream a piece's kernel starts when the last workgroup of
 // the piece before it has retired: every piece pays its own ramp-down (six pieces of a 2 000-block call: 1.75 ms of kernels
 // against 1.50 ms in one launch, profiles/r05_chain_ab.txt).  Pieces write disjoint blocks and read their own descriptor set
@@ -362,27 +377,41 @@ struct PieceOut {
     int finish(const char *label, int rc = GPSIQ_OK);            // rc != GPSIQ_OK: the call has failed, its error text stands
 };
 
+// gpsiq_batch.cpp: piece k of a GPSIQ_NCO_REFERENCE range, blocks [b0, b0 + nb) of it, queued without waiting
+int gpsiq_ref_piece(gpsiq_ctx *c, PieceOut &out, int k, const gpsiq_qchan_t *q, int b0, int nb, int nchan, int nsamp, int ss, uint64_t nbase,
+                    const std::vector<gpsiq_patch_t> &patches);
+
 // what a patch list of n entries (n > 0) asks its buffers for
 inline size_t gpsiq_patch_room(size_t n) { return n < 256 ? 256 : n; }
 
 // the fixed-point carrier: whether slot i continues what the context handed out (the caller gave back what it was given) ...
 inline bool gpsiq_continues(const gpsiq_ctx *c, int i, const gpsiq_chan_t &ch)
 {
-    return ch.prn > 0 && c->carry_prn[i] == ch.prn && c->handed[i] == ch.carr_phase;
+    return ch.prn > 0 && c->carry.prn[i] == ch.prn && c->carry.handed[i] == ch.carr_phase;
 }
 // ... and what a batch call leaves in slot i: satellite prn (0: none) with the accumulator at `phase`
 inline void gpsiq_hand_back(gpsiq_ctx *c, int i, int prn, uint64_t phase, double *carr_phase_out)
 {
-    c->carry_prn[i] = prn;
-    c->carry[i] = prn ? phase : 0;
-    c->handed[i] = prn ? gpsiq::carr_phase_to_double(phase) : 0.0;
-    if (carr_phase_out) carr_phase_out[i] = c->handed[i];
+    c->carry.prn[i] = prn;
+    c->carry.phase[i] = prn ? phase : 0;
+    c->carry.handed[i] = prn ? gpsiq::carr_phase_to_double(phase) : 0.0;
+    if (carr_phase_out) carr_phase_out[i] = c->carry.handed[i];
 }
-double gpsiq_rate_kernel();
+
+// gpsiq_batch.cpp:
+int gpsiq_check_gen_args(const gpsiq_ctx *c, const void *ch, const void *dst, int nblocks, int nchan, int nsamp, double fs, int sample_size);
+// quantised blocks q[0, nblocks) to dst: set resident, rendered, copied (nbase: absolute block index of q[0], for the receiver noise)
+int gpsiq_run_to_host_or_device(gpsiq_ctx *c, const gpsiq_qchan_t *q, int nblocks, int nchan, int nsamp, int sample_size, void *dst, int dst_is_device, uint64_t nbase);
+double gpsiq_rate_kernel();                                     // channel-samples per second of the synthesis kernel: measured, else MI355X's
 void gpsiq_note_kernel_rate(double channel_samples_per_s);      // a measured rate of the synthesis kernel (running mean)
 // GPSIQ_NCO_REFERENCE batch with chain link and evaluation on host threads (the path of rounds 4-5; fallback of the device path)
 int gpsiq_generate_reference_host(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs,
-                                  int sample_size, void *dst, int dst_is_device, double *carr_phase_out, const double *seeds);
+                                  int sample_size, void *dst, int dst_is_device, double *carr_phase_out, const double *seeds = nullptr);
+// level 1 of the carrier chain on the device: whether a batch takes it, the inputs of blocks [b0, b1) staged, the staged blocks' maps waited for
+bool gpsiq_chain_on_device(int nblocks, int nsamp, int nchan);
+void gpsiq_chain_stage_inputs(gpsiq_ctx *c, const gpsiq_chan_t *ch, int b0, int b1, int nchan);
+int gpsiq_chain_maps_staged(gpsiq_ctx *c, int nblocks, int nchan, double fs, int nsamp, const gpsiq_chain_est_t *start, int max_stretches,
+                            gpsiq_chain_est_t *end);
 // gpsiq_evaldev.cpp: the same call (either NCO model) with the descriptors quantised / evaluated on the device.  *handled = 0:
 // not taken (too short a batch, switched off), the caller goes on with the host path
 int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,

@@ -22,7 +22,7 @@ static int check_despread(const gpsiq_ctx *c, int block0, int nblocks, int nsamp
         return fail(GPSIQ_E_STATE, "blocks [%d,+%d) not resident (have %d)", block0, nblocks, c->nblocks);
     if (!src && nblocks && nsamp) return fail(GPSIQ_E_ARG, "null source");
     if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
-    if (stride < (size_t) 2 * (size_t) nsamp * (size_t) sample_size || (stride & 3))
+    if (stride < block_bytes(nsamp, sample_size) || (stride & 3))
         return fail(GPSIQ_E_ARG, "block stride %zu too small or not a multiple of 4", stride);
     if (nblocks && (!prn || (!sums && nsamp))) return fail(GPSIQ_E_ARG, "null output");
     return GPSIQ_OK;

@@ -235,7 +235,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     if (!reference) {
         for (int i = 0; i < nchan; ++i) {
             cont0[i] = gpsiq_continues(c, i, first[i]);
-            h_fix[i].phase = c->carry[i]; h_fix[i].prn = c->carry_prn[i]; h_fix[i].cont = cont0[i] ? 1 : 0;
+            h_fix[i].phase = c->carry.phase[i]; h_fix[i].prn = c->carry.prn[i]; h_fix[i].cont = cont0[i] ? 1 : 0;
         }
         HIP_TRY(hipMemcpyAsync(d_fix, h_fix, (size_t) nchan * sizeof(FixedCarry), hipMemcpyHostToDevice, S));
     }

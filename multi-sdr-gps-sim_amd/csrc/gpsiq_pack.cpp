@@ -53,7 +53,7 @@ static int queue_pack(gpsiq_ctx *c, const PackPlan &p, int nsamp, int sample_siz
 int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, const void *src, size_t src_stride, int bits, void *dst, size_t dst_stride,
                     void *hip_stream, uint64_t *clipped, float *kernel_ms)
 {
-    const size_t src_len = (size_t) 2 * (size_t) (nsamp > 0 ? nsamp : 0) * (size_t) sample_size, dst_len = packed_block_bytes(nsamp, bits);
+    const size_t src_len = block_bytes(nsamp > 0 ? nsamp : 0, sample_size), dst_len = packed_block_bytes(nsamp, bits);
     if (int rc = check_pack(c, nblocks, nsamp, sample_size, bits, src, src_stride, src_len, dst, dst_stride, dst_len)) return rc;
     if (clipped) *clipped = 0;
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -78,7 +78,7 @@ int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, con
 int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const void *src, size_t src_stride, int sample_size, void *dst, size_t dst_stride,
                       void *hip_stream, float *kernel_ms)
 {
-    const size_t dst_len = (size_t) 2 * (size_t) (nsamp > 0 ? nsamp : 0) * (size_t) sample_size, src_len = packed_block_bytes(nsamp, bits);
+    const size_t dst_len = block_bytes(nsamp > 0 ? nsamp : 0, sample_size), src_len = packed_block_bytes(nsamp, bits);
     if (int rc = check_pack(c, nblocks, nsamp, sample_size, bits, src, src_stride, src_len, dst, dst_stride, dst_len)) return rc;
     if (kernel_ms) *kernel_ms = 0.0f;
     const PackPlan p = plan_unpack(nblocks, nsamp, bits, sample_size);
@@ -123,7 +123,7 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
     if (bits != 4 && bits != 2) return fail(GPSIQ_E_ARG, "bad bits %d: 4 or 2", bits);
     if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
     if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
-    const size_t plen = packed_block_bytes(nsamp, bits), blk_bytes = (size_t) 2 * (size_t) nsamp;
+    const size_t plen = packed_block_bytes(nsamp, bits), blk_bytes = block_bytes(nsamp, GPSIQ_SC08);
     if (dst_block_stride < plen) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
     const int qmax = bits == 4 ? 7 : 1;
     if (!c->level.mult || c->level.qmax > qmax)

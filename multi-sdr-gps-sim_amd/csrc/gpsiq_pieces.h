@@ -20,6 +20,11 @@
 
 namespace gpsiq {
 
+// Block geometry: the bytes of one rendered block (nsamp complex elements of sample_size bytes per component), and between blocks
+// where the library lays them out itself (16-byte rows)
+inline size_t block_bytes(int nsamp, int sample_size) { return (size_t) 2 * (size_t) nsamp * (size_t) sample_size; }
+inline size_t block_stride(int nsamp, int sample_size) { return (block_bytes(nsamp, sample_size) + 15) & ~(size_t) 15; }
+
 inline std::optional<long> piece_blocks_env()
 {
     if (const char *e = std::getenv("GPSIQ_PIECE_BLOCKS")) return std::atol(e);

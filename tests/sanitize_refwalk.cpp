@@ -3,6 +3,7 @@
 // while the walkers run must add up to what one call over the whole timeline gives; two timelines walked at once on two host
 // threads; the chain and the evaluation called on their own (channel subsets, time ranges).  Run once with the default pool
 // and once under GPSIQ_THREADS=2 (fewer threads than channels: piece-major order).  TEST INFRASTRUCTURE.
+#include "gpsiq_calls.h"
 #include "gpsiq_internal.h"
 
 #include <cstdio>
@@ -182,6 +183,34 @@ int main()
         if (pthread_create(&ta, nullptr, body, &a) != 0 || pthread_create(&tb, nullptr, body, &b) != 0) return 1;
         pthread_join(ta, nullptr); pthread_join(tb, nullptr);
         if (!a.ok || !b.ok || a.sum != b.sum || a.sum <= 0) { std::fprintf(stderr, "pool: an index was visited %s\n", a.ok && b.ok ? "a wrong number of times in total" : "not exactly once"); return 1; }
+    }
+    // the outcome and the queue of a range of gpsiq_generate_batch_multi (gpsiq_calls.h): a worker takes items off its queue, fails
+    // at one of them (takes the error with its own thread's text) and drains the rest; the feeding thread polls the outcome between
+    // pushes, stops feeding when it sees the failure, closes the queue, and reads the text after the join
+    for (int rep = 0; rep < 50; ++rep) {
+        struct Worker { Status st; WorkQueue<int> items; int taken = 0, rendered = 0; } wk;
+        auto body = [](void *arg) -> void * {
+            Worker &k = *static_cast<Worker *>(arg);
+            int it = 0;
+            while (k.items.pop(&it)) {
+                ++k.taken;
+                if (!k.st.ok()) continue;
+                if (it == 20) k.st.take(fail(GPSIQ_E_RANGE, "item %d does not render", it));
+                else ++k.rendered;
+            }
+            return nullptr;
+        };
+        pthread_t th;
+        if (pthread_create(&th, nullptr, body, &wk) != 0) return 1;
+        int pushed = 0;
+        for (int it = 0; it < 100000 && wk.st.ok(); ++it) { wk.items.push(int(it)); ++pushed; }
+        wk.items.close();
+        pthread_join(th, nullptr);
+        if (wk.st.code() != GPSIQ_E_RANGE || std::strcmp(wk.st.text, "item 20 does not render") != 0 || wk.taken != pushed || wk.rendered != 20) {
+            std::fprintf(stderr, "status and queue: code %d, text '%s', %d of %d items taken, %d rendered\n", wk.st.code(), wk.st.text, wk.taken, pushed, wk.rendered);
+            return 1;
+        }
+        if (wk.st.fail() != GPSIQ_E_RANGE || std::strcmp(gpsiq_last_error(), wk.st.text) != 0) { std::fprintf(stderr, "status: fail() does not hand the text on\n"); return 1; }
     }
     if (p0.empty()) { std::fprintf(stderr, "the scenario should have patches\n"); return 1; }
     std::printf("ok\n");
