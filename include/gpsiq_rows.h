@@ -336,6 +336,116 @@ int gpsiq_acquire_steps(double fs, double f0_hz, double df_hz, uint64_t *code_st
  * argument, ndopp < 1, nshift < 1 or guard < 0. */
 int gpsiq_acquire_decide(const double *power, int ndopp, int nshift, int guard, int *dopp, int *shift, double *ratio);
 
+/* ---- Follow: closed-loop code and carrier tracking on the device ---------------------------------------------------------------------
+ * What a receiver does with what acquisition found: a delay-lock loop on the code, a frequency-then-phase lock loop on the carrier and
+ * the prompt correlator the navigation bits come out of.  ("track" is the host channel state above; this stage is "follow".)
+ * gpsiq_follow follows up to 32 satellites, independently of each other, through ONE contiguous span of a stream exactly as
+ * gpsiq_acquire takes it: interleaved I,Q, int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16, elements as stored, nsamp complex samples at
+ * src, the base 4-byte aligned; device memory, or page-locked host memory of gpsiq_host_alloc.  No resident descriptors, no NCO mode.
+ * Every quantity is an exact integer.  Below "/" on signed values is C's division of int64_t (it truncates toward zero), ">>" of a
+ * negative value the arithmetic shift (it floors), and "X * 2^16" never leaves 63 bits (bounds in DESIGN.md 8f).
+ *
+ * State of one satellite, gpsiq_follow_state_t (filled by the caller, handed back so that a later call continues from it):
+ *     prn         1..32
+ *     sample      index into the span of the next epoch's first sample
+ *     chip, code_frac   the prompt replica's code phase at `sample`: chip 0..1022 and a fraction in [0, 2^56), units of 2^-56 chip.
+ *                 Never one word: 1023 * 2^56 does not fit 64 bits
+ *     code_step0  the nominal code step (gpsiq_acquire_steps' value);  code_step  the current one; both in [2^52, 2^57)
+ *     carr_phase  [0, 2^59), units of 2^-59 cycle;  carr_step  per sample, |carr_step| < 2^58
+ *     carr_int    the loop's frequency integrator, units of carr_step, |carr_int| < 2^59
+ *     prev_ip, prev_qp, have_prev   the previous epoch's scaled prompt (|.| <= 2^22) for the frequency discriminator
+ *     epoch       epochs done so far: decides pull-in or phase lock
+ *     status      written by the call, not read: 0 running (the launch limit is never seen by the caller), 1 the next epoch would pass the
+ *                 end of the span, 2 the record array is full, 3 a step left its allowed range (also: code_step or carr_step outside
+ *                 the range on entry, no record);  reserved comes back 0
+ * A field outside the ranges above, other than code_step and carr_step, is GPSIQ_E_ARG.  From an acquisition peak at shift s of bin d:
+ * sample = s, chip = 0, code_frac = 0, code_step = code_step0, carr_phase = 0, carr_step = carr_int = carr_step0 + d * carr_step_inc,
+ * have_prev = 0, epoch = 0.  The decision-directed pull-in below has a false lock 500 Hz off; it pulls in from |error| < 250 Hz (a quarter
+ * of the epoch rate), so a search that feeds the follower uses bins of 250 Hz or finer.
+ *
+ * One epoch is one period of the replica's code.  m = sample, c = code_step, w = carr_step, T0 = chip * 2^56 + code_frac (67 bits).
+ *  1. N = ceil((1023 * 2^56 - T0) / c), the samples until the prompt replica enters the next period: 1 <= N <= 16368.  If m + N > nsamp
+ *     the satellite stops with status 1; else if nepochs == max_epochs it stops with status 2.  Nothing is written for this epoch.
+ *  2. For n in [0, N): idx = ((carr_phase + n*w) mod 2^59) >> 50, (rI, rQ) = (cosTable512[idx], sinTable512[idx]) (gpsiq_despread's unit
+ *     table), yi = I*rI + Q*rQ, yq = Q*rI - I*rQ at sample m + n (gpsiq_despread's formulas and signs).  Taps t = early, prompt, late at
+ *     off_t = +spacing, 0, -spacing (0 < spacing <= 2^56): A_t(n) = T0 + off_t + n*c, plus 1023 * 2^56 if T0 + off_t is negative;
+ *     chip_t = (A_t(n) >> 56) mod 1023; ca_t(n) = +1 where that chip of gpsiq_prn_code(prn) is 0, -1 where it is 1 (acquire's sign).
+ *     There is no data bit in the replica.
+ *  3. Ie, Qe, Ip, Qp, Il, Ql = sum over n of yi * ca_t(n), yq * ca_t(n): exact int64.
+ *  4. The record gpsiq_follow_epoch_t: sample, nsamp (= N), chip, code_frac, code_step, carr_phase, carr_step as they were at the start
+ *     of the epoch, and the six sums; reserved 0.
+ *  5. sh = max(0, bitlength(max |X| over the six sums) - 22), X' = X >> sh: every |X'| <= 2^22.
+ *  6. Code: num = (Ie'-Il')*Ip' + (Qe'-Ql')*Qp', den = Ip'^2 + Qp'^2, ed = den ? (num * 2^16) / den : 0, clamped to [-2^16, 2^16].
+ *     Positive: the replica is late, the code step rises.
+ *  7. Carrier while epoch < pull_epochs (pull-in): w' = carr_int after, if have_prev,
+ *         cross = prev_ip*Qp' - prev_qp*Ip', dot = prev_ip*Ip' + prev_qp*Qp'; if dot < 0, cross = -cross;
+ *         ef = (|cross| + |dot|) ? (cross * 2^16) / (|cross| + |dot|) : 0;  carr_int += (ef * kf) >> 16.
+ *  8. Carrier from epoch >= pull_epochs on (phase lock): numc = Ip' >= 0 ? Qp' : -Qp', denc = |Ip'| + |Qp'|,
+ *         ec = denc ? (numc * 2^16) / denc : 0;  carr_int += (ec * ki) >> 16;  w' = carr_int + ((ec * kp) >> 16).
+ *  9. carr_phase = (carr_phase + N*w) mod 2^59; total = code_frac + N*c, chip = chip + (total >> 56) - 1023, code_frac = total mod 2^56;
+ *     sample += N; prev_ip, prev_qp = Ip', Qp'; have_prev = 1; epoch += 1.
+ * 10. carr_step = w'; code_step = code_step0 + w' / 12320 + ((ed * kd) >> 16) (carrier aiding: 1540 cycles per chip, 2^59 / 2^56 = 8).
+ *     If carr_step or code_step (as a signed sum, stored in 64 bits as it is) has left its range the satellite stops with status 3.
+ *
+ * gpsiq_follow_cfg_t: spacing in (0, 2^56]; pull_epochs >= 0; the gains kf, kp, ki, kd in [0, 2^46); reserved 0: else GPSIQ_E_ARG.
+ * gpsiq_follow_gains fills it for sample rate fs (host arithmetic in double, then rint): with N0 = fs / 1000 and wn = pll_bn_hz / 0.53
+ *     kf = fll_gain * 2^59 / (2 pi N0)       ki = wn^2 * 1e-3 / (2 pi) * 2^59 / fs       kp = 1.414 * wn / (2 pi) * 2^59 / fs
+ *     kd = 4 * dll_bn_hz / (2 fs) * 2^56     spacing = 2^55     pull_epochs = 100
+ * GPSIQ_E_ARG for an fs, gain or bandwidth that is not positive and finite, GPSIQ_E_RANGE where a gain leaves [0, 2^46).  The values the
+ * tests and gpsiq_runahead use, (fs, 0.25, 18, 5), are tuned for strong signals.
+ *
+ * The call: state is host [nprn], in and out (1 <= nprn <= 32; a satellite may be listed twice); epochs is host [nprn][max_epochs]
+ * (max_epochs >= 1), nepochs host [nprn]; kernel_ms (may be NULL) the kernels' device time.  A satellite runs until the span ends,
+ * max_epochs records are written or a step leaves its range; state[p].status says which.  Records past nepochs[p] are not written.  It
+ * is synchronous, like gpsiq_acquire, and queued on hip_stream behind the caller's work there.  The same call twice from the same input
+ * state gives the same bytes; a call that stops on max_epochs and a second from the returned state give exactly the records and the
+ * final state of one call -- a stream can be followed in pieces; a caller moving to a later span rebases state.sample itself.  Samples
+ * at or past nsamp are never read.  (GPSIQ_FOLLOW_EPOCHS_PER_LAUNCH=n in the environment, read per call: the epochs one launch does per
+ * satellite before the host relaunches from the device-resident state, csrc/gpsiq_follow_plan.h; the records do not depend on it.) */
+typedef struct gpsiq_follow_state {
+    uint64_t sample;
+    uint64_t code_frac, code_step0, code_step;
+    uint64_t carr_phase;
+    int64_t  carr_step, carr_int;
+    int64_t  prev_ip, prev_qp;
+    uint32_t epoch;
+    uint16_t chip;
+    uint8_t  prn, have_prev;
+    uint8_t  status;
+    uint8_t  reserved[7];
+} gpsiq_follow_state_t;
+typedef struct gpsiq_follow_epoch {
+    uint64_t sample;
+    uint64_t code_frac, code_step;
+    uint64_t carr_phase;
+    int64_t  carr_step;
+    int64_t  ie, qe, ip, qp, il, ql;
+    uint32_t nsamp;
+    uint16_t chip, reserved;
+} gpsiq_follow_epoch_t;
+typedef struct gpsiq_follow_cfg {
+    uint64_t spacing;
+    int32_t  pull_epochs, reserved;
+    int64_t  kf, kp, ki, kd;
+} gpsiq_follow_cfg_t;
+#define GPSIQ_FOLLOW_RUNNING 0
+#define GPSIQ_FOLLOW_SPAN_END 1
+#define GPSIQ_FOLLOW_FULL 2
+#define GPSIQ_FOLLOW_RANGE 3
+int gpsiq_follow(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                 const gpsiq_follow_cfg_t *cfg,
+                 gpsiq_follow_state_t *state /* host [nprn], in and out */, int nprn,
+                 gpsiq_follow_epoch_t *epochs /* host [nprn][max_epochs] */, int max_epochs,
+                 int *nepochs /* host [nprn] */, float *kernel_ms /* may be NULL */);
+int gpsiq_follow_gains(double fs, double fll_gain, double pll_bn_hz, double dll_bn_hz, gpsiq_follow_cfg_t *cfg);
+/* The navigation bits of one satellite's records (host, integer arithmetic).  Over the epochs from `skip` on it chooses *offset in 0..19
+ * that maximises the sum over whole 20-epoch groups (group j: epochs skip + offset + 20 j .. + 19) of |sum of ip|, the lowest offset on a
+ * tie; bits[j] is the sign of group j's sum (+1 or -1; 0 for a zero sum); *nbits the number of groups, of which the first max_bits are
+ * written.  GPSIQ_E_RANGE with fewer than 40 epochs after skip; GPSIQ_E_ARG for a NULL argument, skip < 0 or max_bits < 0.  The polarity
+ * of a Costas loop is ambiguous: the whole sequence may come out negated. */
+int gpsiq_follow_bits(const gpsiq_follow_epoch_t *epochs, int nepochs, int skip,
+                      int *offset, int8_t *bits, int max_bits, int *nbits);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -182,6 +182,17 @@ struct gpsiq_ctx {
         // first use + room for one call (corr_cells 0: the correlations are not asked for; plane_bytes 0: the generic kernel)
         int reserve(size_t cells, size_t peaks, size_t corr_cells, size_t plane_bytes);
     } acq;
+    // gpsiq_follow (gpsiq_follow.cpp; include/gpsiq_rows.h, "Follow"): the satellites' states and record counts on the device and
+    // page-locked on their way there and back, the records on the device (they cross straight into the caller's array), and the events a
+    // launch is timed with
+    struct Follow {
+        DevBuf<gpsiq_follow_state_t>    d_state;  PinnedBuf<gpsiq_follow_state_t> h_state;      // [nprn]
+        DevBuf<int>                     d_count;  PinnedBuf<int>                  h_count;      // [nprn]
+        DevBuf<gpsiq_follow_epoch_t>    d_epochs;                                               // [nprn][max_epochs]
+        Event          t0, t1;
+        long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, epochs per launch, launches, bytes of records
+        int reserve(size_t records);                    // first use + room for one call
+    } fol;
 };
 
 #define HIP_TRY(expr)                                                                        \
@@ -329,6 +340,19 @@ inline int gpsiq_ctx::Acquire::reserve(size_t cells, size_t npeaks, size_t corr_
     return GPSIQ_OK;
 }
 
+// (states, counts and events on first use; the records grow)
+inline int gpsiq_ctx::Follow::reserve(size_t records)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(d_state.reserve(32));
+    HIP_TRY(h_state.reserve(32));
+    HIP_TRY(d_count.reserve(32));
+    HIP_TRY(h_count.reserve(32));
+    if (records > d_epochs.cap()) HIP_TRY(d_epochs.reserve(records + records / 4 + 64));
+    return GPSIQ_OK;
+}
+
 // ---- what the translation units of the device half use of each other ----------------------------------------------------------
 // gpsiq_device.cpp:
 // the noise and the output level of launches whose descriptor array starts at absolute block `block` (tab == nullptr while both are off)
@@ -432,6 +456,9 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
 int gpsiq_acquire_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, void *hip_stream, const uint8_t *prn, int nprn,
                        uint64_t code_step, int64_t carr_step0, int64_t carr_step_inc, int ndopp, int nshift, int ncoh, int nnoncoh, int hop,
                        gpsiq_acquire_peak_t *peaks, double *power, gpsiq_despread_sum_t *corr, float *kernel_ms);
+// gpsiq_follow.cpp: gpsiq_follow (include/gpsiq_rows.h) itself, behind the plumbing entry "follow"
+int gpsiq_follow_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, void *hip_stream, const gpsiq_follow_cfg_t *cfg,
+                      gpsiq_follow_state_t *state, int nprn, gpsiq_follow_epoch_t *epochs, int max_epochs, int *nepochs, float *kernel_ms);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
@@ -484,6 +511,11 @@ AcquireGenericFn acquire_generic_kernel(int fmt);
 AcquireWipeFn    acquire_wipe_kernel(int fmt);
 AcquireMfmaFn    acquire_mfma_kernel(int digits);
 AcquirePeaksFn   acquire_peaks_kernel();
+// the follow kernel (gpsiq_follow_kernels.hip): stream, its samples, tables, configuration, states, records, records per satellite,
+// record counts, epochs this launch does per satellite at most
+using FollowFn = void (*)(const uint8_t *, uint64_t, const DeviceTables *, gpsiq_follow_cfg_t, gpsiq_follow_state_t *, gpsiq_follow_epoch_t *, int,
+                          int *, int);
+FollowFn follow_kernel(int fmt);
 
 // gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
 // of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)

@@ -29,7 +29,8 @@ void *gpsiq_plumbing(const char *name);
  * libgpsiq_rows.so for the same reason, with gpsiq_despread's own signature.
  * "pack", "unpack" and "generate_batch_packed" are gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (ibid., "Packed streams";
  * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements.
- * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise. */
+ * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise, and "follow" is gpsiq_follow (ibid., "Follow";
+ * csrc/gpsiq_follow.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -196,6 +197,9 @@ int gpsiq_pack_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
  * that failed), out[1] the bytes of digit planes, out[2] the workgroups of the main kernel, out[3] the k-steps of the matrix kernel;
  * ms (may be NULL): the device time of stage one (0 for the generic kernel) and of the rest. */
 int gpsiq_acquire_last_plan(const gpsiq_ctx_t *ctx, long long out[4], float ms[2]);
+/* What the context's last gpsiq_follow took (csrc/gpsiq_follow_plan.h): out[0] the workgroups of a launch (-1: no call yet, or one that
+ * failed), out[1] the epochs a launch does per satellite at most, out[2] the launches, out[3] the bytes of records on the device. */
+int gpsiq_follow_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
 
 #ifdef __cplusplus
 }

@@ -739,4 +739,54 @@ int gpsiq_acquire_decide(const double *power, int ndopp, int nshift, int guard, 
     return GPSIQ_OK;
 }
 
+// include/gpsiq_rows.h, "Follow": the loop gains of a second-order phase lock behind a first-order frequency pull-in and a carrier-aided
+// first-order delay lock, in the integer units of the loop
+int gpsiq_follow_gains(double fs, double fll_gain, double pll_bn_hz, double dll_bn_hz, gpsiq_follow_cfg_t *cfg)
+{
+    if (!cfg) return fail(GPSIQ_E_ARG, "null argument");
+    for (double v : {fs, fll_gain, pll_bn_hz, dll_bn_hz})
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSIQ_E_ARG, "fs %g, gain %g, bandwidths %g, %g: each positive and finite", fs, fll_gain, pll_bn_hz, dll_bn_hz);
+    const double two_pi = 2.0 * 3.14159265358979323846, carr = std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS), code = std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS);
+    const double n0 = fs / 1000.0, wn = pll_bn_hz / 0.53;
+    const double g[4] = {std::rint(fll_gain * carr / (two_pi * n0)), std::rint(1.414 * wn / two_pi * carr / fs),
+                         std::rint(wn * wn * 1e-3 / two_pi * carr / fs), std::rint(4.0 * dll_bn_hz / (2.0 * fs) * code)};
+    for (double v : g)
+        if (!(v >= 0.0 && v < std::ldexp(1.0, 46))) return fail(GPSIQ_E_RANGE, "gain %g at fs %g outside [0, 2^46)", v, fs);
+    cfg->spacing = UINT64_C(1) << (GPSIQ_CODE_FRAC_BITS - 1);
+    cfg->pull_epochs = 100;
+    cfg->reserved = 0;
+    cfg->kf = (int64_t) g[0]; cfg->kp = (int64_t) g[1]; cfg->ki = (int64_t) g[2]; cfg->kd = (int64_t) g[3];
+    return GPSIQ_OK;
+}
+
+// ibid.: the bit edge is where 20-epoch sums of the in-phase prompt are largest; the bits are those sums' signs
+int gpsiq_follow_bits(const gpsiq_follow_epoch_t *epochs, int nepochs, int skip, int *offset, int8_t *bits, int max_bits, int *nbits)
+{
+    if (!epochs || !offset || !nbits || (!bits && max_bits > 0)) return fail(GPSIQ_E_ARG, "null argument");
+    if (skip < 0 || max_bits < 0) return fail(GPSIQ_E_ARG, "skip %d / max_bits %d", skip, max_bits);
+    const int64_t n = (int64_t) nepochs - (int64_t) skip;
+    if (n < 40) return fail(GPSIQ_E_RANGE, "bits need 40 epochs or more after skip (have %lld)", (long long) n);
+    const gpsiq_follow_epoch_t *e = epochs + skip;
+    int best = 0;
+    unsigned __int128 best_sum = 0;
+    for (int o = 0; o < 20; ++o) {
+        unsigned __int128 total = 0;
+        for (int64_t g = 0; o + 20 * (g + 1) <= n; ++g) {
+            int64_t sum = 0;                                       // |ip| < 2^39: twenty of them fit
+            for (int k = 0; k < 20; ++k) sum += e[o + 20 * g + k].ip;
+            total += (unsigned __int128) (sum < 0 ? -sum : sum);
+        }
+        if (total > best_sum) { best_sum = total; best = o; }      // ascending o: the first of equals stays
+    }
+    const int64_t groups = (n - best) / 20;
+    for (int64_t g = 0; g < groups && g < max_bits; ++g) {
+        int64_t sum = 0;
+        for (int k = 0; k < 20; ++k) sum += e[best + 20 * g + k].ip;
+        bits[g] = (int8_t) (sum > 0 ? 1 : sum < 0 ? -1 : 0);
+    }
+    *offset = best;
+    *nbits = (int) groups;
+    return GPSIQ_OK;
+}
+
 }  // extern "C"

@@ -115,3 +115,14 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_acquire(gpsiq_ctx_t 
     return f(ctx, nsamp, sample_size, src, hip_stream, prn, nprn, code_step, carr_step0, carr_step_inc, ndopp, nshift, ncoh, nnoncoh, hop, peaks, power, corr,
              kernel_ms);
 }
+
+// The follower runs on the context's device (csrc/gpsiq_follow.cpp) and is exported here like the search (include/gpsiq_rows.h, "Follow");
+// gpsiq_follow_gains and gpsiq_follow_bits, plain arithmetic, are in gpsiq_refresh.cpp beside gpsiq_acquire_decide.
+extern "C" __attribute__((visibility("default"))) int gpsiq_follow(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                                                                   const gpsiq_follow_cfg_t *cfg, gpsiq_follow_state_t *state, int nprn,
+                                                                   gpsiq_follow_epoch_t *epochs, int max_epochs, int *nepochs, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, const void *, void *, const gpsiq_follow_cfg_t *, gpsiq_follow_state_t *, int,
+                                              gpsiq_follow_epoch_t *, int, int *, float *)>("follow");
+    return f(ctx, nsamp, sample_size, src, hip_stream, cfg, state, nprn, epochs, max_epochs, nepochs, kernel_ms);
+}

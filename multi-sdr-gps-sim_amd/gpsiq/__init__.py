@@ -13,7 +13,8 @@ import numpy as np
 from .abi import (CHAN_DTYPE, QCHAN_DTYPE, SC08, SC16, SINK_HACKRF, SINK_IQFILE,  # noqa: F401
                   SINK_PLUTOSDR, HACKRF_CHUNK, MAX_CHAN, elem_dtype, EPHEM_DTYPE, IONO_DTYPE, TRACK_DTYPE,
                   NAV_EPH_DTYPE, NAV_UTC_DTYPE, NAV_ALM_DTYPE, NAV_STATE_DTYPE, RINEX_EPH_DTYPE, PATCH_DTYPE,
-                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE, ACQ_PEAK_DTYPE)
+                  NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE, ACQ_PEAK_DTYPE,
+                  FOLLOW_STATE_DTYPE, FOLLOW_EPOCH_DTYPE, FOLLOW_CFG_DTYPE)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPSIQ_LIB: another build of the library (tests/test_gpu_build.py loads the one it has just compiled on the GPU box)
@@ -163,6 +164,10 @@ _acquire = _sig("gpsiq_acquire", _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_uint64,
 _acquire_last_plan = _sig("gpsiq_acquire_last_plan", _i, _vp, _vp, _vp)
 _acquire_steps = _sig("gpsiq_acquire_steps", _i, _d, _d, _d, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 _acquire_decide = _sig("gpsiq_acquire_decide", _i, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d))
+_follow = _sig("gpsiq_follow", _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, C.POINTER(C.c_float))
+_follow_last_plan = _sig("gpsiq_follow_last_plan", _i, _vp, _vp)
+_follow_gains = _sig("gpsiq_follow_gains", _i, _d, _d, _d, _d, _vp)
+_follow_bits = _sig("gpsiq_follow_bits", _i, _vp, _i, _i, C.POINTER(_i), _vp, _i, C.POINTER(_i))
 
 
 class NoiseSettings(C.Structure):
@@ -660,6 +665,36 @@ def acquire_decide(power, guard):
     return d.value, s.value, r.value
 
 
+def follow_gains(fs, fll_gain=0.25, pll_bn_hz=18.0, dll_bn_hz=5.0):
+    """gpsiq_follow_gains: the follower's configuration (FOLLOW_CFG_DTYPE, one element) at sample rate fs.  The defaults are tuned for
+    strong signals."""
+    cfg = np.zeros(1, dtype=FOLLOW_CFG_DTYPE)
+    _check(_follow_gains(float(fs), float(fll_gain), float(pll_bn_hz), float(dll_bn_hz), _p(cfg)))
+    return cfg
+
+
+def follow_start(prn, shift, dopp, code_step, carr_step0, carr_step_inc):
+    """The follower's state (FOLLOW_STATE_DTYPE, one element per satellite) from acquisition peaks: satellite prn[k] found at sample
+    shift[k] of bin dopp[k] of a search with the steps of acquire_steps.  The pull-in reaches |frequency error| < 250 Hz (beyond it
+    lies a false lock 500 Hz off), so the search must use bins of 250 Hz or finer."""
+    prn, shift, dopp = (np.atleast_1d(np.asarray(a)) for a in (prn, shift, dopp))
+    st = np.zeros(len(prn), dtype=FOLLOW_STATE_DTYPE)
+    st["prn"], st["sample"] = prn, shift
+    st["code_step0"] = st["code_step"] = int(code_step)
+    st["carr_step"] = st["carr_int"] = [int(carr_step0) + int(d) * int(carr_step_inc) for d in dopp]
+    return st
+
+
+def follow_bits(epochs, skip=0):
+    """gpsiq_follow_bits on one satellite's records (FOLLOW_EPOCH_DTYPE [nepochs]): (offset of the bit edge in 0..19, int8 bits +1 / -1,
+    0 for a zero sum).  The whole sequence may be negated (the polarity of a Costas loop)."""
+    e = np.ascontiguousarray(epochs, dtype=FOLLOW_EPOCH_DTYPE).ravel()
+    bits = np.zeros(max(len(e) // 20, 1), dtype=np.int8)
+    off, nb = _i(0), _i(0)
+    _check(_follow_bits(_p(e), int(e.size), int(skip), C.byref(off), _p(bits), int(bits.size), C.byref(nb)))
+    return off.value, bits[:nb.value].copy()
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -907,6 +942,27 @@ class Context:
         ms = (C.c_float * 2)()
         _check(_acquire_last_plan(self._h, out, ms))
         return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3]), float(ms[0]), float(ms[1])
+
+    def follow(self, nsamp, sample_size, device_ptr, cfg, states, max_epochs, stream=None):
+        """gpsiq_follow: follow the satellites of `states` (FOLLOW_STATE_DTYPE, from follow_start or an earlier call) through the nsamp
+        complex samples at device_ptr with the configuration cfg (follow_gains) -> (records FOLLOW_EPOCH_DTYPE [nprn][max_epochs], of
+        which the first nepochs[p] are written, nepochs int32 [nprn], the states to continue from, kernel milliseconds)."""
+        cfg = np.ascontiguousarray(cfg, dtype=FOLLOW_CFG_DTYPE).ravel()
+        assert cfg.size == 1
+        st = np.array(states, dtype=FOLLOW_STATE_DTYPE, copy=True, ndmin=1).ravel()
+        ep = np.zeros((len(st), max(int(max_epochs), 0)), dtype=FOLLOW_EPOCH_DTYPE)
+        ne = np.zeros(len(st), dtype=np.int32)
+        ms = C.c_float(0.0)
+        _check(_follow(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(stream or 0), _p(cfg), _p(st) if len(st) else None, len(st),
+                       _p(ep) if ep.size else None, int(max_epochs), _p(ne) if len(st) else None, C.byref(ms)))
+        return ep, ne, st, float(ms.value)
+
+    def follow_last_plan(self):
+        """What the last follow() took: (workgroups of a launch or None, epochs a launch does per satellite at most, launches, bytes of
+        records on the device)."""
+        out = (C.c_longlong * 4)()
+        _check(_follow_last_plan(self._h, out))
+        return (None if out[0] < 0 else int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def pack_last_plan(self):
         """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""

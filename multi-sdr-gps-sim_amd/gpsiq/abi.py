@@ -95,3 +95,14 @@ assert DESPREAD_SUM_DTYPE.itemsize == 16 and BLOCK_STATS_DTYPE.itemsize == 40
 # gpsiq_acquire (include/gpsiq_rows.h, "Acquisition"): gpsiq_acquire_peak_t
 ACQ_PEAK_DTYPE = np.dtype([("power", "<f8"), ("shift", "<i4"), ("reserved", "<i4")], align=True)
 assert ACQ_PEAK_DTYPE.itemsize == 16
+# gpsiq_follow (include/gpsiq_rows.h, "Follow"): gpsiq_follow_state_t, gpsiq_follow_epoch_t, gpsiq_follow_cfg_t and the status values
+FOLLOW_STATE_DTYPE = np.dtype([("sample", "<u8"), ("code_frac", "<u8"), ("code_step0", "<u8"), ("code_step", "<u8"), ("carr_phase", "<u8"),
+                               ("carr_step", "<i8"), ("carr_int", "<i8"), ("prev_ip", "<i8"), ("prev_qp", "<i8"), ("epoch", "<u4"), ("chip", "<u2"),
+                               ("prn", "u1"), ("have_prev", "u1"), ("status", "u1"), ("reserved", "u1", (7,))], align=True)
+FOLLOW_EPOCH_DTYPE = np.dtype([("sample", "<u8"), ("code_frac", "<u8"), ("code_step", "<u8"), ("carr_phase", "<u8"), ("carr_step", "<i8"),
+                               ("ie", "<i8"), ("qe", "<i8"), ("ip", "<i8"), ("qp", "<i8"), ("il", "<i8"), ("ql", "<i8"),
+                               ("nsamp", "<u4"), ("chip", "<u2"), ("reserved", "<u2")], align=True)
+FOLLOW_CFG_DTYPE = np.dtype([("spacing", "<u8"), ("pull_epochs", "<i4"), ("reserved", "<i4"), ("kf", "<i8"), ("kp", "<i8"), ("ki", "<i8"),
+                             ("kd", "<i8")], align=True)
+assert FOLLOW_STATE_DTYPE.itemsize == 88 and FOLLOW_EPOCH_DTYPE.itemsize == 96 and FOLLOW_CFG_DTYPE.itemsize == 48
+FOLLOW_RUNNING, FOLLOW_SPAN_END, FOLLOW_FULL, FOLLOW_RANGE = 0, 1, 2, 3

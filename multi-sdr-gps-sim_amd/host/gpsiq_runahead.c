@@ -14,7 +14,7 @@
  *   allocate()                                   the 30 s refresh, gps.c:2870-2909
  *
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
- *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire]
+ *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -45,6 +45,13 @@
  * line per satellite -- the best bin in Hz, its shift, and gpsiq_acquire_decide's ratio at a guard of 3 samples (" rendered gain g" behind
  * the satellites the block holds, g the descriptor's gain: with --cn0 c such a satellite is at c + 20 log10 g dB-Hz).  The block is searched where it lies: the page-locked buffer of gpsiq_host_alloc is device-accessible.
  * Not with --pack (the search reads int8 / int16 elements); it needs 64 samples or more in a millisecond and five milliseconds in a block.
+ * Following (optional, with --acquire): --follow <seconds> then follows every satellite the search lists -- a ratio above FOLLOW_LISTED --
+ * through the first <seconds> of the stream (gpsiq_follow, include/gpsiq_rows.h, "Follow") with gpsiq_follow_gains(fs, 0.25, 18, 5), the
+ * gains for strong signals.  The follower's pull-in reaches 250 Hz (beyond it lies a false lock 500 Hz off), so with --follow the search
+ * is widened to 41 bins of 250 Hz.  One line per satellite followed: the final Doppler in Hz, the code phase in chips at the sample it
+ * stopped at, the mean prompt amplitude per sample from epoch 250 on, the bits gpsiq_follow_bits reads from there, the epochs and the
+ * status.  The span is followed where it lies, like the searched block; it must lie inside the run's first call to the library (the blocks
+ * up to the first 30 s boundary, 100 at the most).
  */
 #include <math.h>
 #include <stdint.h>
@@ -145,29 +152,77 @@ static int refresh_ephemeris(struct host_state *h, double t)
 
 /* --acquire: the blind search of one rendered block (page-locked, so the device reads it in place), one line per satellite */
 #define ACQ_BINS 21
-static int run_acquire(gpsiq_ctx_t *gq, const void *block, int nsamp, int ss, double fs, int ms, int ncoh, const gpsiq_chan_t *desc, int nchan)
+#define ACQ_BINS_FOLLOW 41      /* with --follow: bins of 250 Hz, the follower's pull-in range */
+#define FOLLOW_LISTED 2.2255    /* the ratio above which a satellite counts as found (measured: tests/test_acquire_ref.py, THRESHOLD) */
+#define FOLLOW_SKIP 250         /* epochs the loops are given to settle before amplitude and bits are read */
+struct found { int n; uint8_t prn[GPSIQ_MAX_SAT]; int bin[GPSIQ_MAX_SAT], shift[GPSIQ_MAX_SAT]; };
+static int run_acquire(gpsiq_ctx_t *gq, const void *block, int nsamp, int ss, double fs, int ms, int ncoh, const gpsiq_chan_t *desc, int nchan,
+                       int bins, double df, struct found *found)
 {
     uint8_t prn[GPSIQ_MAX_SAT];
-    static gpsiq_acquire_peak_t peaks[GPSIQ_MAX_SAT][ACQ_BINS];
+    static gpsiq_acquire_peak_t peaks[GPSIQ_MAX_SAT][ACQ_BINS_FOLLOW];
     uint64_t code_step;
     int64_t step0, step_inc;
     for (int p = 0; p < GPSIQ_MAX_SAT; ++p) prn[p] = (uint8_t) (p + 1);
-    if (gpsiq_acquire_steps(fs, -5000.0, 500.0, &code_step, &step0, &step_inc) != GPSIQ_OK) return -1;
-    double *power = malloc(sizeof(double) * GPSIQ_MAX_SAT * ACQ_BINS * (size_t) ms);
+    if (gpsiq_acquire_steps(fs, -5000.0, df, &code_step, &step0, &step_inc) != GPSIQ_OK) return -1;
+    double *power = malloc(sizeof(double) * GPSIQ_MAX_SAT * (size_t) bins * (size_t) ms);
     if (!power) return -1;
-    if (gpsiq_acquire(gq, nsamp, ss, block, NULL, prn, GPSIQ_MAX_SAT, code_step, step0, step_inc, ACQ_BINS, ms, ncoh, 4, ms, &peaks[0][0], power, NULL,
+    if (gpsiq_acquire(gq, nsamp, ss, block, NULL, prn, GPSIQ_MAX_SAT, code_step, step0, step_inc, bins, ms, ncoh, 4, ms, &peaks[0][0], power, NULL,
                       NULL) != GPSIQ_OK) { free(power); return -1; }
+    found->n = 0;
     for (int p = 0; p < GPSIQ_MAX_SAT; ++p) {
         int bin = 0, shift = 0, rendered = 0;
         double ratio = 0.0, gain = 0.0;
-        if (gpsiq_acquire_decide(power + (size_t) p * ACQ_BINS * (size_t) ms, ACQ_BINS, ms, 3, &bin, &shift, &ratio) != GPSIQ_OK) ratio = 0.0;
+        if (gpsiq_acquire_decide(power + (size_t) p * (size_t) bins * (size_t) ms, bins, ms, 3, &bin, &shift, &ratio) != GPSIQ_OK) ratio = 0.0;
         for (int i = 0; i < nchan; ++i)
             if (desc[i].prn == p + 1) { rendered = 1; gain = desc[i].gain; }
-        printf("acquire PRN %2d  %+6.0f Hz  shift %5d  ratio %.4f", p + 1, -5000.0 + 500.0 * bin, shift, ratio);
+        printf("acquire PRN %2d  %+6.0f Hz  shift %5d  ratio %.4f", p + 1, -5000.0 + df * bin, shift, ratio);
         if (rendered) printf("  rendered gain %.4f", gain);
         printf("\n");
+        if (ratio > FOLLOW_LISTED) { found->prn[found->n] = (uint8_t) (p + 1); found->bin[found->n] = bin; found->shift[found->n] = shift; found->n++; }
     }
     free(power);
+    return 0;
+}
+
+/* --follow: every satellite the search listed, from its peak through `span` samples at `stream` (page-locked: the device reads it in
+ * place), one line per satellite */
+static int run_follow(gpsiq_ctx_t *gq, const void *stream, int span, int ss, double fs, double df, const struct found *found)
+{
+    if (!found->n) return 0;
+    uint64_t code_step;
+    int64_t step0, step_inc;
+    gpsiq_follow_cfg_t cfg;
+    if (gpsiq_acquire_steps(fs, -5000.0, df, &code_step, &step0, &step_inc) != GPSIQ_OK) return -1;
+    if (gpsiq_follow_gains(fs, 0.25, 18.0, 5.0, &cfg) != GPSIQ_OK) return -1;
+    /* an epoch is a code period, about a millisecond: room for half as many again as the span has milliseconds */
+    const int max_epochs = (int) ((double) span / fs * 1500.0) + 16;
+    static gpsiq_follow_state_t st[GPSIQ_MAX_SAT];
+    int nep[GPSIQ_MAX_SAT];
+    gpsiq_follow_epoch_t *rec = malloc(sizeof *rec * (size_t) found->n * (size_t) max_epochs);
+    int8_t *bits = malloc((size_t) max_epochs / 20 + 1);
+    if (!rec || !bits) { free(rec); free(bits); return -1; }
+    memset(st, 0, sizeof st);
+    for (int k = 0; k < found->n; ++k) {                       /* include/gpsiq_rows.h, "Follow": from an acquisition peak */
+        st[k].prn = found->prn[k];
+        st[k].sample = (uint64_t) found->shift[k];
+        st[k].code_step0 = st[k].code_step = code_step;
+        st[k].carr_step = st[k].carr_int = step0 + (int64_t) found->bin[k] * step_inc;
+    }
+    if (gpsiq_follow(gq, span, ss, stream, NULL, &cfg, st, found->n, rec, max_epochs, nep, NULL) != GPSIQ_OK) { free(rec); free(bits); return -1; }
+    for (int k = 0; k < found->n; ++k) {
+        const gpsiq_follow_epoch_t *r = rec + (size_t) k * (size_t) max_epochs;
+        double amp = 0.0;
+        const int from = nep[k] > FOLLOW_SKIP ? FOLLOW_SKIP : 0;
+        for (int e = from; e < nep[k]; ++e) amp += hypot((double) r[e].ip, (double) r[e].qp) / (double) r[e].nsamp;
+        if (nep[k] > from) amp /= (double) (nep[k] - from);
+        int offset = 0, nbits = 0;
+        if (gpsiq_follow_bits(r, nep[k], FOLLOW_SKIP, &offset, bits, max_epochs / 20 + 1, &nbits) != GPSIQ_OK) nbits = 0;
+        printf("follow PRN %2d  %+9.2f Hz  code %9.4f chips  amplitude %.2f  bits %d  epochs %d  status %d\n", (int) st[k].prn,
+               (double) st[k].carr_step * fs / 576460752303423488.0, (double) st[k].chip + (double) st[k].code_frac / 72057594037927936.0, amp, nbits,
+               nep[k], (int) st[k].status);
+    }
+    free(rec); free(bits);
     return 0;
 }
 
@@ -179,13 +234,16 @@ int main(int argc, char **argv)
     int pack = 0, pack_given = 0;
     uint64_t noise_seed = 0;
     int acquire = 0;
+    double follow_s = NAN;
+    int follow = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
-                        strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0))) break;
+                        strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
+        else if (strcmp(argv[argc - 2], "--follow") == 0) { follow_s = atof(argv[argc - 1]); follow = 1; }
         else if (strcmp(argv[argc - 2], "--qmax") == 0) qmax = atoi(argv[argc - 1]);
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
@@ -197,10 +255,13 @@ int main(int argc, char **argv)
     const int pack_qmax = pack == GPSIQ_PK4 ? 7 : 1;
     const int pack_bad = pack_given && ((pack != GPSIQ_PK4 && pack != GPSIQ_PK2) || isnan(level_rms) || qmax < 0 || qmax > pack_qmax ||
                                         (argc >= 10 && atoi(argv[9]) != 1));
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire]\n"
+    /* --follow: with --acquire, a positive time of 10 s at the most (a call renders 100 blocks) */
+    const int follow_bad = follow && (!acquire || !(follow_s > 0.0) || !(follow_s <= 0.1 * BLOCKS_PER_CALL));
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
-                        "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n", argv[0]);
+                        "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
+                        "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -313,7 +374,19 @@ int main(int argc, char **argv)
                 if (gpsiq_generate_batch_packed(gq, desc, nb, nchan, nsamp, fs, pack, buf, blk_bytes, carr) != GPSIQ_OK) return die("generate packed");
             } else if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
-            if (acquire && done == 0 && b == 0 && run_acquire(gq, buf, nsamp, ss, fs, acq_ms, acq_ncoh, desc, nchan) != 0) return die("acquire");
+            if (acquire && done == 0 && b == 0) {
+                struct found found;
+                if (run_acquire(gq, buf, nsamp, ss, fs, acq_ms, acq_ncoh, desc, nchan, follow ? ACQ_BINS_FOLLOW : ACQ_BINS, follow ? 250.0 : 500.0, &found) != 0)
+                    return die("acquire");
+                if (follow) {
+                    const double span = floor(follow_s * fs + 0.5);
+                    if (span > (double) nb * (double) nsamp) {
+                        fprintf(stderr, "gpsiq_runahead: --follow %g s is more than the %d blocks of the run's first call\n", follow_s, nb);
+                        return 2;
+                    }
+                    if (run_follow(gq, buf, (int) span, ss, fs, 250.0, &found) != 0) return die("follow");
+                }
+            }
             if (fwrite(buf, blk_bytes, (size_t) nb, fo) != (size_t) nb) { fprintf(stderr, "short write\n"); return 1; }
         }
         done += n;
