@@ -130,7 +130,7 @@ typedef struct gpsiq_ctx gpsiq_ctx_t;
  * in time: a certified map per block, linked by a scan) and the search for those samples are kernels
  * (csrc/gpsiq_evaldev.cpp); descriptors that lie in page-locked (gpsiq_host_alloc) or device memory are read where they
  * are, pageable ones are first cut down to 64 bytes each on the host pool.  The block call and short batches walk the
- * carrier on host threads (~2 us per block and channel, csrc/gpsiq_exact.cpp); GPSIQ_EVAL=host takes every batch there. */
+ * carrier on host threads (~2 us per block and channel, csrc/gpsiq_exact.cpp and gpsiq_refwalk.cpp); GPSIQ_EVAL=host takes every batch there. */
 #define GPSIQ_NCO_FIXED      0
 #define GPSIQ_NCO_REFERENCE  1
 

@@ -130,7 +130,7 @@ int gpsiq_check_gen_args(const gpsiq_ctx *c, const void *ch, const void *dst, in
 
 // ---- GPSIQ_NCO_REFERENCE: walk and render in pieces ------------------------------------------
 // The carrier chain is serial in time on the host, the render is not: the timeline is cut into pieces (ref_chunk_blocks,
-// piece_ends), and while the device renders (and copies out) piece k the host threads (RefWalk, gpsiq_exact.cpp: a chain task and
+// piece_ends), and while the device renders (and copies out) piece k the host threads (RefWalk, gpsiq_refwalk.cpp: a chain task and
 // an evaluation task per channel and piece, taken piece-major from the shared pool) are in the pieces behind it.
 // gpsiq_generate_reference_host renders from the calling thread; gpsiq_generate_batch_multi (gpsiq_multi.cpp) gives every device a
 // thread, fed through a queue.  gpsiq_ref_piece queues piece k of a range without waiting: blocks [b0, b0 + nb) of the range, whose

@@ -46,7 +46,7 @@ int reference_timeline(const gpsiq_chan_t *ch, int nblocks, int nchan, double de
                        gpsiq_qchan_t *q, std::vector<gpsiq_patch_t> *patches, double *carr_end, int *last_prn,
                        const double *carr_in = nullptr, const int *prn_in = nullptr);
 
-// The same as a walker that can be consumed piece by piece while it runs (gpsiq_exact.cpp): the timeline is cut into pieces,
+// The same as a walker that can be consumed piece by piece while it runs (gpsiq_refwalk.cpp): the timeline is cut into pieces,
 // piece k = blocks [ends[k-1], ends[k]); per piece and channel one CHAIN task (serial down the channel: the start state of
 // every block) and one EVAL task (descriptors + patches from the start states, any thread); piece k is complete when every
 // channel's EVAL (chain_only: CHAIN) of it has finished.
@@ -62,6 +62,7 @@ struct RefWalk {
     // the patches of piece k (complete: wait_piece(k) first, or after run()), sorted by (block, sample, slot); relative: block
     // indices counted from the piece's first block
     void take_patches(size_t k, std::vector<gpsiq_patch_t> *out, bool relative);
+    void all_patches(std::vector<gpsiq_patch_t> *out);      // after run(): every piece's patches, absolute block indices, in that order
     size_t npieces() const { return ends.size(); }
     void abort() { abort_flag.store(true, std::memory_order_release); }     // the remaining tasks finish at once (pieces still complete)
 

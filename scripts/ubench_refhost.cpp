@@ -2,9 +2,13 @@
 // quantiser, the candidate search (two Euclid-style descents), the serial carrier chain (NcoWalk: wrap-to-wrap table) and the
 // whole evaluation of a block from its start state (quantiser + candidates + drift enclosure, walks only where it is
 // undecided), at 2.6 and 25 Msps, Doppler uniform in +-5 kHz (bench.py's synthetic channels).
-// Build:  g++ -O3 -std=c++17 -ffp-contract=off -I multi-sdr-gps-sim_amd/csrc scripts/ubench_refhost.cpp multi-sdr-gps-sim_amd/csrc/gpsiq_host.cpp -lpthread
-#include "gpsiq_exact.cpp"
+// Build:  cd multi-sdr-gps-sim_amd/csrc && g++ -O3 -std=c++17 -ffp-contract=off -I . ../../scripts/ubench_refhost.cpp
+//         gpsiq_host.cpp gpsiq_exact.cpp gpsiq_refwalk.cpp gpsiq_chain.cpp -lpthread      Run pinned to one core:  taskset -c 2 ./a.out
+#include "gpsiq_exact.h"
+#include "gpsiq_candidates.h"
+#include <algorithm>
 #include <chrono>
+#include <cstring>
 #include <random>
 using namespace gpsiq;
 static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -1,9 +1,11 @@
-// batch_walk.cpp -- NcoWalk::walk8_up / walk8_down (csrc/gpsiq_exact.cpp: eight carrier cycles walked at once with AVX-512)
+// batch_walk.cpp -- NcoWalk::walk8_up / walk8_down (csrc/gpsiq_ncowalk.h: eight carrier cycles walked at once with AVX-512)
 // against the scalar walk they vectorise (climb<true> / descend<true>), lane for lane: where a lane says ok, the cycle's end
 // state, its number of samples and the range of start states it holds for are the scalar walk's; a lane may only ever be
 // MORE cautious (not ok where the scalar walk is).  Random and adversarial addends (exact-tie binades), random and edge start
 // states.  TEST INFRASTRUCTURE.   prints  cases=.. lanes_ok=.. scalar_ok=.. bad=..   (skipped=1 without AVX-512)
-#include "gpsiq_exact.cpp"
+#include "gpsiq_ncowalk.h"
+#include <cstdio>
+#include <cstdlib>
 #include <random>
 using namespace gpsiq;
 

@@ -4,10 +4,19 @@
 // slots re-allocated and unused, a timeline continued from an earlier call, ranges summarised and folded as the ranks of a
 // time-sharded run do.  Every start state, end state and last_prn must be equal, bit for bit.  TEST INFRASTRUCTURE.
 //   usage: chain_parallel [seed] [cases]       prints  cases=.. blocks=.. linked=.. walked=.. bad=..
-#define GPSIQ_JOIN_CHECK 1
-#include "gpsiq_exact.cpp"          // (with its internals: the general walker Nco is what the top-tie walk is held against)
-#include "gpsiq_chain.cpp"
+//   links csrc/gpsiq_host.cpp, gpsiq_exact.cpp, gpsiq_refwalk.cpp and gpsiq_chain.cpp, all built with -DGPSIQ_JOIN_CHECK=1
+#ifndef GPSIQ_JOIN_CHECK
+#error "build with -DGPSIQ_JOIN_CHECK=1: gpsiq_chain.cpp then holds every join as a scan against the loop and counts them"
+#endif
+#include "gpsiq_internal.h"
+#include "gpsiq_lane.h"
+#include "gpsiq_nco.h"              // the general walker Nco is what the top-tie walk is held against
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <random>
+
+namespace gpsiq { extern std::atomic<long> g_join_mismatch, g_join_checked; }      // gpsiq_chain.cpp under GPSIQ_JOIN_CHECK
 
 using namespace gpsiq;
 

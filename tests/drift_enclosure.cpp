@@ -1,26 +1,15 @@
-// drift_enclosure.cpp -- Drift (csrc/gpsiq_exact.cpp): the enclosure of the reference's double accumulator at sample n, taken
-// from the block's start state alone, against the accumulator walked exactly (Nco::advance).  TEST INFRASTRUCTURE.
+// drift_enclosure.cpp -- Drift (csrc/gpsiq_drift.h): the enclosure of the reference's double accumulator at sample n, taken
+// from the block's start state alone, against the accumulator walked exactly (Nco::advance, csrc/gpsiq_nco.h).  Headers only.
+// TEST INFRASTRUCTURE.
 //   usage: drift_enclosure [seed]   prints  checked=.. bad=.. max_use=.. mean_width=.. worst_width=..
 // max_use: largest |truth - centre| / half-width seen; widths relative to the a-priori window 2 (n+1) 2^-54 (carrier) / 2^-44 (code).
-#include "gpsiq_exact.cpp"
+#include "gpsiq_drift.h"
+#include "gpsiq_nco.h"
+#include <cstdio>
+#include <cstdlib>
 #include <random>
 using namespace gpsiq;
 typedef __int128 i128;
-
-// the enclosure itself, as cell_at computes it (kept in step with Drift::cell_at)
-static bool enclose(const Drift &D, double x0, long n, i128 *lo, i128 *hi)
-{
-    if (!D.valid || !(x0 >= 0.0 && x0 < D.L)) return false;
-    const i128 R = D.neg ? D.units(x0) - (i128) n * D.mc : D.units(x0) + (i128) n * D.mc;
-    i128 q = R / D.Lint, r = R % D.Lint;
-    if (r < 0) { r += D.Lint; q -= 1; }
-    const double core = (double) q * D.GL + D.Gof((double) r * D.ulp_c) - D.Gof(x0);
-    const double I = ((double) (q < 0 ? -q : q) + 3.0) * D.Acyc;
-    const double eta = 4.0 * D.gmax * (std::fabs(core) + I) + 1e-12 * (std::fabs(core) + std::fabs((double) q * D.GL)) + 4.0 * D.gmax * D.L * 0x1p-52;
-    *lo = R + (i128) std::floor((core - I - eta) / D.ulp_c) - 2;
-    *hi = R + (i128) std::ceil((core + I + eta) / D.ulp_c) + 2;
-    return true;
-}
 
 int main(int argc, char **argv)
 {
@@ -51,7 +40,7 @@ int main(int argc, char **argv)
             a.advance(n);
             const i128 U = D.neg ? D.units(a.x) - (i128) a.wraps * D.Lint : D.units(a.x) + (i128) a.wraps * D.Lint;   // the unwrapped double phase, cut below one unit
             i128 lo, hi;
-            if (!enclose(D, x0, n, &lo, &hi)) continue;
+            if (!D.enclose(x0, n, &lo, &hi)) continue;
             ++tot;
             if (!(lo <= U && U + 1 <= hi)) { ++bad; if (bad < 10) std::fprintf(stderr, "OUTSIDE kind %d c %a x0 %a n %ld: lo-U %g hi-U %g\n", kind, c, x0, n, (double) (lo - U), (double) (hi - U)); }
             const double ctr = (double) (hi + lo - 2 * U) / 2.0, hw = (double) (hi - lo) / 2.0;
@@ -62,7 +51,7 @@ int main(int argc, char **argv)
             ++cells;
             if (D.cell_at(x0, n, &cell)) {
                 ++cells_ok;
-                const i128 truth = kind == 1 ? (i128) std::floor(a.x * 512.0) : (i128) (long) a.x + (i128) a.wraps * GPSIQ_CA_SEQ_LEN;
+                const i128 truth = kind == 1 ? (i128) std::floor(a.x * 512.0) : (i128) (long) a.x + (i128) a.wraps * kCaSeqLen;
                 const bool same = kind == 1 ? (long) (cell & 511) == (long) truth && a.x < 1.0 : cell == truth;
                 if (!same) { ++bad; if (bad < 10) std::fprintf(stderr, "WRONG CELL kind %d c %a x0 %a n %ld\n", kind, c, x0, n); }
             }

@@ -2,16 +2,21 @@
 // gpsiq_eval_kernels.hip run, compiled here for the host) against the host path it replaces, on random and adversarial
 // descriptors.  TEST INFRASTRUCTURE.
 //   A  pack_chan + quantize_dchan            == quantize_one (gpsiq_host.cpp): same descriptor bytes, same error class
-//   B  next_candidate, one at a time         == candidates() (gpsiq_exact.cpp), the recursive Euclid descent
+//   B  next_candidate, one at a time         == candidates() (gpsiq_candidates.h), the recursive Euclid descent
 //   C  eval_chan from the block's true start == eval_block: same descriptor, same patches; what it hands to the host walker
 //                                               (an undecided candidate) is counted and must stay rare
 //   D  the chain as a scan (Link)            == gpsiq_chain_link: every start state the scan calls known is the serial chain's,
 //                                               whatever the association of the scan and wherever the timeline is cut in pieces
 //   usage: eval_twin [seed] [cases]       prints  cases=.. chans=.. evals=.. host=.. evals_near=.. host_near=.. patches=.. known=.. unknown=.. bad=..
 //   (host: evaluations handed to the host walker; _near: those whose descriptor was seeded within 1e-9 cycle of the start state)
-#include "gpsiq_exact.cpp"
-#include "gpsiq_chain.cpp"
+//   links csrc/gpsiq_host.cpp, gpsiq_exact.cpp, gpsiq_refwalk.cpp and gpsiq_chain.cpp
+#include "gpsiq_exact.h"
+#include "gpsiq_candidates.h"
 #include "gpsiq_eval.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <random>
 
 using namespace gpsiq;
@@ -86,7 +91,7 @@ static long test_quantiser(int cases, long *chans)
         if (ev::qstatus_code(st) != rc || (rc == GPSIQ_OK && std::memcmp(&want, &got, sizeof want))) {
             if (bad++ < 5) std::printf("quantiser differs: rc %d, status %d (prn %d, f_carr %g, f_code %g, code_phase %.17g, pos %d/%d/%d, nsamp %d)\n", rc, st, c.prn, c.f_carr, c.f_code, c.code_phase, c.iword, c.ibit, c.icode, nsamp);
         }
-        // the window of data bits == nav_bit() of gpsiq_exact.cpp
+        // the window of data bits == nav_bit() of gpsiq_exact.h
         if (c.prn > 0 && !(d.pos & ev::kBadPos))
             for (long b = 0; b < 45; ++b)
                 if (ev::dchan_nav_bit(d, b) != nav_bit(c, b) && b < ev::kNavWindow) { if (bad++ < 5) std::printf("nav bit %ld differs (iword %d ibit %d)\n", b, c.iword, c.ibit); break; }

@@ -140,13 +140,18 @@ def test_ranges_composed_and_folded_equal_the_serial_chain(modes):
     assert rounds_total <= (12 * 3 if not modes else 12 * 8), rounds_total
 
 
+def soak_sources(csrc):
+    """What tests/chain_parallel.cpp links, and the define under which gpsiq_chain.cpp checks every join as a scan."""
+    return ["-DGPSIQ_JOIN_CHECK=1"] + [os.path.join(csrc, s) for s in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_refwalk.cpp", "gpsiq_chain.cpp")]
+
+
 def test_soak_program_random_and_adversarial_timelines(tmp_path):
     """tests/chain_parallel.cpp: exact-tie addends, Doppler through zero, re-seeded and unused slots, continued and
     range-sharded timelines, 1..16 stretches, all sample rates."""
     csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
     exe = str(tmp_path / "chain_parallel")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", exe,
-                    os.path.join(ROOT, "tests", "chain_parallel.cpp"), os.path.join(csrc, "gpsiq_host.cpp"), "-lpthread", "-lm"], check=True)
+                    os.path.join(ROOT, "tests", "chain_parallel.cpp"), *soak_sources(csrc), "-lpthread", "-lm"], check=True)
     for seed in (1, 2):
         r = subprocess.run([exe, str(seed), "45"], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0 and " bad=0" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
@@ -160,7 +165,7 @@ def test_lane_code_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "chain_parallel_san")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", exe,
-                    os.path.join(ROOT, "tests", "chain_parallel.cpp"), os.path.join(csrc, "gpsiq_host.cpp"), "-lpthread", "-lm"], check=True)
+                    os.path.join(ROOT, "tests", "chain_parallel.cpp"), *soak_sources(csrc), "-lpthread", "-lm"], check=True)
     r = subprocess.run([exe, "5", "24"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and " bad=0" in r.stdout and "runtime error" not in r.stderr, r.stdout[-2000:] + r.stderr[-2000:]
 

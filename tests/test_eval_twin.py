@@ -15,7 +15,8 @@ CSRC = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
 def build(tmp_path, name, flags):
     exe = str(tmp_path / name)
     subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", *flags, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", exe,
-                    os.path.join(ROOT, "tests", "eval_twin.cpp"), os.path.join(CSRC, "gpsiq_host.cpp"), "-lpthread", "-lm"], check=True)
+                    os.path.join(ROOT, "tests", "eval_twin.cpp"),
+                    *(os.path.join(CSRC, s) for s in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_refwalk.cpp", "gpsiq_chain.cpp")), "-lpthread", "-lm"], check=True)
     return exe
 
 

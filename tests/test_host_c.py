@@ -67,7 +67,7 @@ def test_host_half_under_sanitizers(tmp_path, san):
     if "undefined" in san:
         flags.append("-fno-sanitize-recover=undefined")
     objs = []
-    for src in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_chain.cpp", "gpsiq_refresh.cpp", "gpsiq_nav.cpp", "gpsiq_rinex.cpp"):
+    for src in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_refwalk.cpp", "gpsiq_chain.cpp", "gpsiq_refresh.cpp", "gpsiq_nav.cpp", "gpsiq_rinex.cpp"):
         o = str(tmp_path / (src + ".o"))
         b = subprocess.run(["g++", "-std=c++17", *flags, "-c", os.path.join(csrc, src), "-o", o], capture_output=True, text=True)
         if b.returncode != 0:
@@ -100,7 +100,8 @@ def test_reference_walker_consumed_in_pieces_under_sanitizers(tmp_path, san):
     if "undefined" in san:
         flags.append("-fno-sanitize-recover=undefined")
     b = subprocess.run(["g++", *flags, "-o", exe, os.path.join(root, "tests", "sanitize_refwalk.cpp"), os.path.join(csrc, "gpsiq_host.cpp"),
-                        os.path.join(csrc, "gpsiq_exact.cpp"), os.path.join(csrc, "gpsiq_chain.cpp"), "-lpthread", "-lm"], capture_output=True, text=True)
+                        os.path.join(csrc, "gpsiq_exact.cpp"), os.path.join(csrc, "gpsiq_refwalk.cpp"), os.path.join(csrc, "gpsiq_chain.cpp"), "-lpthread", "-lm"],
+                       capture_output=True, text=True)
     if b.returncode != 0:
         pytest.skip("no sanitizer toolchain / runtime here: " + b.stderr[-300:])
     for threads in (None, "2"):           # the default pool; fewer threads than channels (piece-major)
@@ -112,7 +113,7 @@ def test_reference_walker_consumed_in_pieces_under_sanitizers(tmp_path, san):
 
 
 def test_drift_enclosure_holds_the_walked_accumulator(tmp_path):
-    """The decision GPSIQ_NCO_REFERENCE takes WITHOUT walking an accumulator (Drift in csrc/gpsiq_exact.cpp: an enclosure of
+    """The decision GPSIQ_NCO_REFERENCE takes WITHOUT walking an accumulator (Drift in csrc/gpsiq_drift.h: an enclosure of
     the reference's double phase at sample n from the block's start state alone) against the accumulator walked exactly
     (Nco::advance, itself pinned to the plain loop of gps.c:2789-2792 / 2821-2826 by test_reference_nco_host.py): 400 000
     random and adversarial cases per seed -- carrier both signs and code, four sample rates, addends with trailing zero
@@ -122,7 +123,7 @@ def test_drift_enclosure_holds_the_walked_accumulator(tmp_path):
     csrc = os.path.join(root, "multi-sdr-gps-sim_amd", "csrc")
     exe = str(tmp_path / "drift_enclosure")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(root, "include"), "-I" + csrc, "-o", exe,
-                    os.path.join(root, "tests", "drift_enclosure.cpp"), os.path.join(csrc, "gpsiq_host.cpp"), os.path.join(csrc, "gpsiq_chain.cpp"), "-lpthread", "-lm"], check=True)
+                    os.path.join(root, "tests", "drift_enclosure.cpp"), "-lm"], check=True)      # the numerics are header-only
     for seed in ("1",):
         r = subprocess.run([exe, seed], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr
@@ -139,13 +140,35 @@ def test_eight_cycles_at_once_equal_the_scalar_walk(tmp_path):
     csrc = os.path.join(root, "multi-sdr-gps-sim_amd", "csrc")
     exe = str(tmp_path / "batch_walk")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(root, "include"), "-I" + csrc, "-o", exe,
-                    os.path.join(root, "tests", "batch_walk.cpp"), os.path.join(csrc, "gpsiq_host.cpp"), os.path.join(csrc, "gpsiq_chain.cpp"), "-lpthread", "-lm"], check=True)
+                    os.path.join(root, "tests", "batch_walk.cpp"), "-lm"], check=True)
     r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     f = dict(kv.split("=") for kv in r.stdout.split())
     if f.get("skipped"):
         pytest.skip("no AVX-512 on this host: the table is built by the scalar walk alone")
     assert int(f["bad"]) == 0 and int(f["lanes_ok"]) > 400000 and int(f["lanes_ok"]) <= int(f["scalar_ok"])
+
+
+@pytest.mark.parametrize("header", ["gpsiq_nco.h", "gpsiq_candidates.h", "gpsiq_ncowalk.h", "gpsiq_drift.h", "gpsiq_exact.h"])
+def test_exact_mode_header_compiles_on_its_own(header):
+    """Each header of the exact-mode host half is an interface of its own: a translation unit of nothing but its include compiles."""
+    csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-x", "c++", "-"],
+                       input='#include "%s"\n' % header, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+def test_no_program_includes_a_translation_unit():
+    """Tests and scripts reach the library's internals through its headers and link its sources: none includes a .cpp."""
+    import re
+    found = []
+    for sub in ("tests", "scripts"):
+        for dirpath, _, names in os.walk(os.path.join(ROOT, sub)):
+            for name in names:
+                path = os.path.join(dirpath, name)
+                with open(path, errors="replace") as f:
+                    found += ["%s:%d" % (os.path.relpath(path, ROOT), n) for n, l in enumerate(f, 1) if re.search(r'#include "[^"]*\.cpp"', l)]
+    assert not found, found
 
 
 def test_fifo_header_matches_reference_api():

@@ -163,7 +163,7 @@ def chain_case(oracle, fs, ns, f_carr, x0):
 
 
 def test_wrap_to_wrap_table_against_the_plain_loop(oracle):
-    """The carrier chain's table of whole cycles (csrc/gpsiq_exact.cpp, NcoWalk): blocks of hundreds of carrier
+    """The carrier chain's table of whole cycles (csrc/gpsiq_ncowalk.h, NcoWalk): blocks of hundreds of carrier
     cycles, where all but the first dozen or two cycles are look-ups -- Doppler-sized addends of both signs, addends
     that are short binary fractions (every rounding a tie or exact), start phases on and next to binade edges and on
     the post-wrap grid, whole-run lengths at all four sample rates."""
