@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "gpsiq_ctx.h"
+#include "gpsiq_acquire.h"
 #include "gpsiq_acquire_plan.h"
 
 using namespace gpsiq;
@@ -41,7 +42,7 @@ int gpsiq_acquire_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *s
     const char *force = std::getenv("GPSIQ_ACQUIRE_KERNEL");
     const AcquirePlan p = plan_acquire(nsamp, sample_size, nprn, ndopp, nshift, ncoh, nnoncoh, hop, force && !std::strcmp(force, "generic"),
                                        kAcqFastDefault, force && !std::strcmp(force, "mfma"));
-    gpsiq_ctx::Acquire &a = c->acq;
+    AcquireSet &a = c->acq;
     if (p.kind != kPlanLaunch) return fail(GPSIQ_E_ARG, "not a search");       // (the checks above and the planner's are the same list)
     const bool fast = p.kernel == kAcquireMfma;
     HIP_TRY(hipSetDevice(c->device));

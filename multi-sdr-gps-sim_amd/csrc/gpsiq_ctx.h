@@ -1,7 +1,22 @@
 // gpsiq_ctx.h -- the device context of libgpsiq (include/gpsiq.h: gpsiq_ctx_t), shared by the translation units of the device half:
 // gpsiq_device.cpp (context, resident descriptors, launches, settings), gpsiq_batch.cpp (the drop-in calls of one context),
 // gpsiq_multi.cpp (gpsiq_generate_batch_multi) and gpsiq_evaldev.cpp (the batch calls whose descriptors are quantised / evaluated
-// on the device).
+// on the device), and by the host side of every stream stage.  This header keeps the context itself, the first-use routines of the
+// chain and the device evaluation, what the translation units above use of each other, and the synthesis kernels by type.  What a
+// stream stage keeps in the context is in that stage's header, included below; HIP_TRY is in gpsiq_own.h.
+//
+// The files of a stream stage <s> (despread, pack, acquire, follow):
+//   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
+//   gpsiq_<s>.h                 the stage's member of gpsiq_ctx (resources, reserve()), its kernels by type and their look-ups,
+//                               and `decltype(gpsiq_<s>) gpsiq_<s>_impl;`
+//   gpsiq_<s>.cpp               checks, plan, look-up, launch, copy-back: the definition of gpsiq_<s>_impl
+//   gpsiq_<s>_plan.h            the plan, pure host arithmetic (pinned on the CPU by the tests)
+//   gpsiq_<s>_geometry.h        the constants plan and kernels share              } device sources: in the Makefile's DEVSRC,
+//   gpsiq_<s>_kernels.hip       the kernels and the table of those that exist     } behind gpsiq_kernels_id()
+//   gpsiq_device.cpp            one line of the gpsiq_plumbing() table: {"<s>", &gpsiq_<s>_impl}
+//   gpsiq_rows_link.cpp         the exported gpsiq_<s> of libgpsiq_rows.so: core<decltype(&gpsiq_<s>)>("<s>")
+//   gpsiq_stage_math.cpp        its helpers that are plain arithmetic (libgpsiq_rows.so)
+//   gpsiq/__init__.py           the Python binding
 #ifndef GPSIQ_CTX_H
 #define GPSIQ_CTX_H
 
@@ -15,6 +30,10 @@
 #include "gpsiq_noise.h"
 #include "gpsiq_own.h"
 #include "gpsiq_pieces.h"
+#include "gpsiq_despread.h"
+#include "gpsiq_pack.h"
+#include "gpsiq_acquire.h"
+#include "gpsiq_follow.h"
 
 struct gpsiq_ctx {
     template <typename T> using DevBuf = gpsiq::DevBuf<T>;
@@ -144,70 +163,15 @@ struct gpsiq_ctx {
         int reserve(size_t n, bool pinned_source, bool seeds);     // first use + room for n blocks x channels
         int reserve_repair(size_t rows);
     } evd;
-    // gpsiq_despread (gpsiq_despread.cpp; include/gpsiq_rows.h, "Despread"): the sums, satellites and stream statistics of one call
-    // on the device and page-locked on their way back, and the two events its kernel is timed with
-    struct Despread {
-        DevBuf<gpsiq_despread_sum_t>    d_sums;   PinnedBuf<gpsiq_despread_sum_t> h_sums;       // [nblocks][nchan][nseg]
-        DevBuf<uint8_t>                 d_prn;    PinnedBuf<uint8_t>              h_prn;        // [nblocks][nchan]
-        DevBuf<gpsiq_block_stats_t>     d_stats;  PinnedBuf<gpsiq_block_stats_t>  h_stats;      // [nblocks]
-        Event          t0, t1;
-        int            last[4] = {-1, 0, 0, 0};        // the last call's plan: kernel, slots, grid, wave_rows (gpsiq_despread_last_plan)
-        int reserve(size_t nsums, size_t nprn, size_t nblocks);     // first use + room for one call
-    } dsp;
-    // gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed (gpsiq_pack.cpp; include/gpsiq_rows.h, "Packed streams"): the counter of
-    // clamped elements on the device and page-locked on its way back, the two events a kernel is timed with, and what the batch call
-    // works through its pieces with -- two rendered and two packed staging buffers taken in turn, a stream for the packer, one for
-    // the copies, and per buffer pair the events "packed" and "copied"
-    struct Pack {
-        DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-        DevBuf<uint8_t>               d_render[2], d_packed[2];                               // bytes
-        Stream         pack_stream, copy_stream;
-        Event          t0, t1, packed[2], copied[2];
-        std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
-        long           last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, units per block, tiles per block, pieces (gpsiq_pack_last_plan)
-        int reserve(size_t render_bytes, size_t packed_bytes);      // first use + room for one call (0, 0: gpsiq_pack / gpsiq_unpack)
-    } pack;
-    // gpsiq_acquire (gpsiq_acquire.cpp; include/gpsiq_rows.h, "Acquisition"): the satellite list, the power grid, the peaks and (where
-    // the caller asks for them) the correlations of one call on the device, the digit planes of the matrix path, the page-locked
-    // staging of list and peaks (grid and correlations cross straight into the caller's arrays), and the events the kernels are timed with
-    struct Acquire {
-        DevBuf<uint8_t>                 d_prn;    PinnedBuf<uint8_t>              h_prn;        // [nprn]
-        DevBuf<double>                  d_power;                                                // [nprn][ndopp][nshift]
-        DevBuf<gpsiq_acquire_peak_t>    d_peaks;  PinnedBuf<gpsiq_acquire_peak_t> h_peaks;      // [nprn][ndopp]
-        DevBuf<gpsiq_despread_sum_t>    d_corr;                                                 // [nprn][ndopp][nnoncoh][nshift]
-        DevBuf<uint8_t>                 d_planes;                                               // bytes (gpsiq_acquire_plan.h: scratch_bytes)
-        Event          t0, t1, t2;                      // before stage one, between the stages, behind the peaks
-        long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, scratch bytes, grid of the main kernel, k-steps
-        float          last_ms[2] = {0.0f, 0.0f};       // the last call's device time: stage one (0 for the generic kernel), the rest
-        // first use + room for one call (corr_cells 0: the correlations are not asked for; plane_bytes 0: the generic kernel)
-        int reserve(size_t cells, size_t peaks, size_t corr_cells, size_t plane_bytes);
-    } acq;
-    // gpsiq_follow (gpsiq_follow.cpp; include/gpsiq_rows.h, "Follow"): the satellites' states and record counts on the device and
-    // page-locked on their way there and back, the records on the device (they cross straight into the caller's array), and the events a
-    // launch is timed with
-    struct Follow {
-        DevBuf<gpsiq_follow_state_t>    d_state;  PinnedBuf<gpsiq_follow_state_t> h_state;      // [nprn]
-        DevBuf<int>                     d_count;  PinnedBuf<int>                  h_count;      // [nprn]
-        DevBuf<gpsiq_follow_epoch_t>    d_epochs;                                               // [nprn][max_epochs]
-        Event          t0, t1;
-        long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, epochs per launch, launches, bytes of records
-        int reserve(size_t records);                    // first use + room for one call
-    } fol;
+    // the stream stages, each in the header of its name: gpsiq_despread; gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed;
+    // gpsiq_acquire; gpsiq_follow
+    gpsiq::DespreadSet dsp;
+    gpsiq::PackSet     pack;
+    gpsiq::AcquireSet  acq;
+    gpsiq::FollowSet   fol;
 };
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return gpsiq::fail(GPSIQ_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
-
-// ---- first use and growth of the chain's and the device evaluation's resources ------------------------------------------------
-// Every member is ensured / reserved by every call, each a compare once it exists: a call that fails part-way returns its error,
-// and the next call makes what is still missing instead of taking a half-made set for a whole one.  Members that share a
-// capacity are grown in one step that is entered while ANY of them lacks room for n (the smallest of their capacities): after a
-// step that failed part-way -- forget before free leaves the member it failed at empty, the ones behind it at their old size --
-// every later call enters it again, whatever its n.
+// ---- first use and growth of the chain's and the device evaluation's resources (the rule: reserve_together, gpsiq_own.h) ------
 inline int gpsiq_ctx::Chain::reserve(size_t n)
 {
     // (equal priorities: with the synthesis stream above the chain's, the second launch's maps came back late -- 0.98 ms
@@ -221,6 +185,8 @@ inline int gpsiq_ctx::Chain::reserve(size_t n)
     HIP_TRY(d_est.reserve((gpsiq::kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN));
     HIP_TRY(h_est.reserve((gpsiq::kEvalMaxPieces + 1) * GPSIQ_MAX_CHAN));
     HIP_TRY(d_c_before.reserve(gpsiq::kEvalMaxPieces * GPSIQ_MAX_CHAN));
+    // (reserve_together's rule in lines of its own: d_prep counts in bytes, kPrepBytes per entry, its neighbours in entries, and it
+    // keeps its place in the order the five are grown in)
     if (n <= std::min({d_in.cap(), h_in.cap(), d_prep.cap() / kPrepBytes, d_maps.cap(), h_maps.cap()})) return GPSIQ_OK;
     const size_t cap = n + n / 4 + 256;
     HIP_TRY(d_in.reserve(cap));
@@ -254,102 +220,15 @@ inline int gpsiq_ctx::EvalDev::reserve(size_t n, bool pinned_source, bool seeds)
     HIP_TRY(h_patches.reserve(kPatchCap));
     HIP_TRY(d_host.reserve(kHostCap));
     HIP_TRY(h_host.reserve(kHostCap));
-    if (n * kChanBytes > std::min(d_chan.cap(), h_chan.cap())) {
-        const size_t cap = n + n / 4 + 256;
-        HIP_TRY(d_chan.reserve(cap * kChanBytes));
-        HIP_TRY(h_chan.reserve(cap * kChanBytes));
-    }
-    if (pinned_source && n > d_raw.cap()) HIP_TRY(d_raw.reserve(n + n / 4 + 16));
-    if (seeds && n > d_seeds.cap()) HIP_TRY(d_seeds.reserve(n + n / 4 + 16));
+    HIP_TRY(gpsiq::reserve_together(n * kChanBytes, (n + n / 4 + 256) * kChanBytes, d_chan, h_chan));       // both in bytes
+    if (pinned_source) HIP_TRY(gpsiq::reserve_together(n, n + n / 4 + 16, d_raw));
+    if (seeds) HIP_TRY(gpsiq::reserve_together(n, n + n / 4 + 16, d_seeds));
     return GPSIQ_OK;
 }
 
 inline int gpsiq_ctx::EvalDev::reserve_repair(size_t rows)
 {
-    if (rows <= std::min({d_slot.cap(), h_slot.cap(), d_col.cap(), h_col.cap()})) return GPSIQ_OK;
-    const size_t cap = rows + 256;
-    HIP_TRY(d_slot.reserve(cap));
-    HIP_TRY(h_slot.reserve(cap));
-    HIP_TRY(d_col.reserve(cap));
-    HIP_TRY(h_col.reserve(cap));
-    return GPSIQ_OK;
-}
-
-// (every pair grows together, device side first: a step that failed part-way is entered again by the next call, whatever its size)
-inline int gpsiq_ctx::Despread::reserve(size_t nsums, size_t nprn, size_t nblocks)
-{
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
-    if (nsums > std::min(d_sums.cap(), h_sums.cap())) {
-        const size_t cap = nsums + nsums / 4 + 256;
-        HIP_TRY(d_sums.reserve(cap));
-        HIP_TRY(h_sums.reserve(cap));
-    }
-    if (nprn > std::min(d_prn.cap(), h_prn.cap())) {
-        const size_t cap = nprn + nprn / 4 + 256;
-        HIP_TRY(d_prn.reserve(cap));
-        HIP_TRY(h_prn.reserve(cap));
-    }
-    if (nblocks > std::min(d_stats.cap(), h_stats.cap())) {
-        const size_t cap = nblocks + nblocks / 4 + 16;
-        HIP_TRY(d_stats.reserve(cap));
-        HIP_TRY(h_stats.reserve(cap));
-    }
-    return GPSIQ_OK;
-}
-
-// (the counter, events and streams on first use; the staging pairs grow together, rendered side first)
-inline int gpsiq_ctx::Pack::reserve(size_t render_bytes, size_t packed_bytes)
-{
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
-    HIP_TRY(d_count.reserve(1));
-    HIP_TRY(h_count.reserve(1));
-    if (!render_bytes && !packed_bytes) return GPSIQ_OK;
-    HIP_TRY(pack_stream.ensure());
-    HIP_TRY(copy_stream.ensure());
-    for (auto &e : packed) HIP_TRY(e.ensure());
-    for (auto &e : copied) HIP_TRY(e.ensure());
-    if (render_bytes > std::min(d_render[0].cap(), d_render[1].cap())) {
-        const size_t cap = render_bytes + render_bytes / 4 + 256;
-        for (auto &b : d_render) HIP_TRY(b.reserve(cap));
-    }
-    if (packed_bytes > std::min(d_packed[0].cap(), d_packed[1].cap())) {
-        const size_t cap = packed_bytes + packed_bytes / 4 + 256;
-        for (auto &b : d_packed) HIP_TRY(b.reserve(cap));
-    }
-    return GPSIQ_OK;
-}
-
-// (the satellite list, events and peaks on first use; every pair grows together, device side first)
-inline int gpsiq_ctx::Acquire::reserve(size_t cells, size_t npeaks, size_t corr_cells, size_t plane_bytes)
-{
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
-    HIP_TRY(t2.ensure(hipEventDefault));
-    HIP_TRY(d_prn.reserve(32));
-    HIP_TRY(h_prn.reserve(32));
-    if (cells > d_power.cap()) HIP_TRY(d_power.reserve(cells + cells / 4 + 256));
-    if (npeaks > std::min(d_peaks.cap(), h_peaks.cap())) {
-        const size_t cap = npeaks + npeaks / 4 + 64;
-        HIP_TRY(d_peaks.reserve(cap));
-        HIP_TRY(h_peaks.reserve(cap));
-    }
-    if (corr_cells > d_corr.cap()) HIP_TRY(d_corr.reserve(corr_cells + corr_cells / 4 + 256));
-    if (plane_bytes > d_planes.cap()) HIP_TRY(d_planes.reserve(plane_bytes + plane_bytes / 4 + 256));
-    return GPSIQ_OK;
-}
-
-// (states, counts and events on first use; the records grow)
-inline int gpsiq_ctx::Follow::reserve(size_t records)
-{
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
-    HIP_TRY(d_state.reserve(32));
-    HIP_TRY(h_state.reserve(32));
-    HIP_TRY(d_count.reserve(32));
-    HIP_TRY(h_count.reserve(32));
-    if (records > d_epochs.cap()) HIP_TRY(d_epochs.reserve(records + records / 4 + 64));
+    HIP_TRY(gpsiq::reserve_together(rows, rows + 256, d_slot, h_slot, d_col, h_col));
     return GPSIQ_OK;
 }
 
@@ -440,25 +319,6 @@ int gpsiq_chain_maps_staged(gpsiq_ctx *c, int nblocks, int nchan, double fs, int
 // not taken (too short a batch, switched off), the caller goes on with the host path
 int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                           void *dst, int dst_is_device, double *carr_phase_out, const double *seeds, int *handled);
-// gpsiq_despread.cpp: gpsiq_despread (include/gpsiq_rows.h) itself, behind the plumbing entry "despread"
-int gpsiq_despread_impl(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int sample_size, const void *src, size_t block_stride_bytes,
-                        void *hip_stream, int seg_len, int clip, gpsiq_despread_sum_t *sums, uint8_t *prn, gpsiq_block_stats_t *stats,
-                        float *kernel_ms);
-// gpsiq_pack.cpp: gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (include/gpsiq_rows.h) themselves, behind the plumbing
-// entries "pack", "unpack" and "generate_batch_packed"
-int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, const void *src_dev, size_t src_stride, int bits,
-                    void *dst_dev, size_t dst_stride, void *hip_stream, uint64_t *clipped, float *kernel_ms);
-int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const void *src_dev, size_t src_stride, int sample_size,
-                      void *dst_dev, size_t dst_stride, void *hip_stream, float *kernel_ms);
-int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int bits,
-                                     void *dst_host, size_t dst_block_stride, double *carr_phase_out);
-// gpsiq_acquire.cpp: gpsiq_acquire (include/gpsiq_rows.h) itself, behind the plumbing entry "acquire"
-int gpsiq_acquire_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, void *hip_stream, const uint8_t *prn, int nprn,
-                       uint64_t code_step, int64_t carr_step0, int64_t carr_step_inc, int ndopp, int nshift, int ncoh, int nnoncoh, int hop,
-                       gpsiq_acquire_peak_t *peaks, double *power, gpsiq_despread_sum_t *corr, float *kernel_ms);
-// gpsiq_follow.cpp: gpsiq_follow (include/gpsiq_rows.h) itself, behind the plumbing entry "follow"
-int gpsiq_follow_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, void *hip_stream, const gpsiq_follow_cfg_t *cfg,
-                      gpsiq_follow_state_t *state, int nprn, gpsiq_follow_epoch_t *epochs, int max_epochs, int *nepochs, float *kernel_ms);
 
 namespace gpsiq {
 // The synthesis kernels by type (gpsiq_kernels.hip holds them and the table of the instantiations that exist; a lookup returns
@@ -485,37 +345,6 @@ RowsFn      rowsx_kernel(int fmt, int slots);
 RowsFn      rows_kernel(int fmt);
 GenericFn   generic_kernel(int fmt);
 PatchFn     patch_kernel(int fmt);
-// the correlator kernels (gpsiq_despread_kernels.hip): kernel and slots as gpsiq_despread_plan.h names them.  Arguments: descriptors,
-// nchan, nsamp, src, block stride, block0, tables, workgroups per block, rows per wave, rows per segment, segments per block, clip,
-// sums, satellites, stream statistics (may be null)
-using DespreadFn  = void (*)(const gpsiq_qchan_t *, int, int, const uint8_t *, size_t, int, const DeviceTables *, int, int, int, int, int,
-                             gpsiq_despread_sum_t *, uint8_t *, gpsiq_block_stats_t *);
-DespreadFn  despread_kernel(int fmt, int kernel, int slots);
-// the pack / unpack kernels (gpsiq_pack_kernels.hip).  Arguments: source and its block stride, destination and its block stride,
-// samples per block, units per block, tiles per block, tiles of the launch (gpsiq_pack_plan.h); pack: the counter of clamped elements
-using PackFn      = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, uint32_t, uint32_t, uint64_t, unsigned long long *);
-using UnpackFn    = void (*)(const uint8_t *, size_t, uint8_t *, size_t, int, uint32_t, uint32_t, uint64_t);
-PackFn      pack_kernel(int fmt, int bits);
-UnpackFn    unpack_kernel(int bits, int fmt);
-// the acquisition kernels (gpsiq_acquire_kernels.hip).  generic: stream, tables, satellites, nshift, ncoh, nnoncoh, hop, ndopp, code step,
-// carrier step of bin 0 and between bins (mod 2^64), power grid, correlations (may be null).  wipe: stream, tables, span, plane length,
-// ndopp, row tiles, the carrier steps, planes.  mfma: planes, tables, satellites, plane length, row tiles, nshift, ncoh, nnoncoh, hop,
-// ndopp, code step, k-steps, power grid, correlations (may be null).  peaks: power grid, its rows, nshift, peaks
-using AcquireGenericFn = void (*)(const uint8_t *, const DeviceTables *, const uint8_t *, int, int, int, int, int, uint64_t, uint64_t, uint64_t,
-                                  double *, gpsiq_despread_sum_t *);
-using AcquireWipeFn    = void (*)(const uint8_t *, const DeviceTables *, uint64_t, uint64_t, int, int, uint64_t, uint64_t, uint8_t *);
-using AcquireMfmaFn    = void (*)(const uint8_t *, const DeviceTables *, const uint8_t *, uint64_t, int, int, int, int, int, int, uint64_t, int,
-                                  double *, gpsiq_despread_sum_t *);
-using AcquirePeaksFn   = void (*)(const double *, uint64_t, int, gpsiq_acquire_peak_t *);
-AcquireGenericFn acquire_generic_kernel(int fmt);
-AcquireWipeFn    acquire_wipe_kernel(int fmt);
-AcquireMfmaFn    acquire_mfma_kernel(int digits);
-AcquirePeaksFn   acquire_peaks_kernel();
-// the follow kernel (gpsiq_follow_kernels.hip): stream, its samples, tables, configuration, states, records, records per satellite,
-// record counts, epochs this launch does per satellite at most
-using FollowFn = void (*)(const uint8_t *, uint64_t, const DeviceTables *, gpsiq_follow_cfg_t, gpsiq_follow_state_t *, gpsiq_follow_epoch_t *, int,
-                          int *, int);
-FollowFn follow_kernel(int fmt);
 
 // gpsiq_launch.cpp: the one door every rendered sample goes through.  cls: what the descriptors at desc contribute to the choice
 // of kernel (gpsiq_launch_plan.h); variant: not kAuto (auto_variant() resolves it)

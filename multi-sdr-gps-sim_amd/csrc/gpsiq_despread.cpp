@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "gpsiq_ctx.h"
+#include "gpsiq_despread.h"
 #include "gpsiq_despread_plan.h"
 
 using namespace gpsiq;
@@ -42,7 +43,7 @@ int gpsiq_despread_impl(gpsiq_ctx_t *c, int block0, int nblocks, int nsamp, int 
     if (p.kind != kPlanLaunch) return GPSIQ_OK;                       // no block: no output to write
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    gpsiq_ctx::Despread &d = c->dsp;
+    DespreadSet &d = c->dsp;
     const size_t nprn = (size_t) nblocks * (size_t) c->nchan, nsums = nprn * (size_t) p.nseg;
     if (int rc = d.reserve(nsums ? nsums : 1, nprn, (size_t) nblocks)) return rc;
     const DespreadFn kernel = despread_kernel(sample_size, p.kernel, p.slots);

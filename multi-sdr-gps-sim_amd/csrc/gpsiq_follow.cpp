@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "gpsiq_ctx.h"
+#include "gpsiq_follow.h"
 #include "gpsiq_follow_plan.h"
 
 using namespace gpsiq;
@@ -57,7 +58,7 @@ int gpsiq_follow_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *sr
     if (p.kind != kPlanLaunch) return fail(GPSIQ_E_ARG, "not a call");          // (the checks above and the planner's are the same list)
     const FollowFn kernel = follow_kernel(sample_size);
     if (!kernel) return fail(GPSIQ_E_DEVICE, "no follow kernel for %d-byte samples", sample_size);
-    gpsiq_ctx::Follow &f = c->fol;
+    FollowSet &f = c->fol;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     if (int rc = f.reserve((size_t) p.records)) return rc;

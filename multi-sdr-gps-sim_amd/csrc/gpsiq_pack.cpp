@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "gpsiq_ctx.h"
+#include "gpsiq_pack.h"
 #include "gpsiq_pack_plan.h"
 
 using namespace gpsiq;
@@ -62,7 +63,7 @@ int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, con
     if (!p.launch) return GPSIQ_OK;                                   // no byte: nothing to write
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    gpsiq_ctx::Pack &k = c->pack;
+    PackSet &k = c->pack;
     if (int rc = k.reserve(0, 0)) return rc;
     HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
     HIP_TRY(hipEventRecord(k.t0.get(), s));
@@ -86,7 +87,7 @@ int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const vo
     if (!p.launch) return GPSIQ_OK;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    gpsiq_ctx::Pack &k = c->pack;
+    PackSet &k = c->pack;
     if (int rc = k.reserve(0, 0)) return rc;
     const UnpackFn kernel = unpack_kernel(bits, sample_size);
     if (!kernel) return fail(GPSIQ_E_DEVICE, "no unpack kernel for %d bits, %d-byte samples", bits, sample_size);
@@ -138,7 +139,7 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
     // `raw` bytes into the same buffer, and a device copy on pack_stream moves them to rows of `sstride` bytes
     const size_t sstride = (blk_bytes + 3) & ~(size_t) 3, raw = sstride != blk_bytes ? sstride * (size_t) piece : 0;
     HIP_TRY(hipSetDevice(c->device));
-    gpsiq_ctx::Pack &k = c->pack;
+    PackSet &k = c->pack;
     if (int rc = k.reserve(raw + blk_bytes * (size_t) piece + 4, pstride * (size_t) piece + 4)) return rc;      // (+4: never a request of no bytes)
     const PackPlan whole = plan_pack(piece, nsamp, GPSIQ_SC08, bits);
     note_plan(c, whole, npieces);

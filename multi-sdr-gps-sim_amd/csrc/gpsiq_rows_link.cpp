@@ -1,5 +1,5 @@
 // gpsiq_rows_link.cpp -- libgpsiq_rows.so's end of its link to libgpsiq.so.  The rows either side of the hot path (gpsiq_refresh.cpp,
-// gpsiq_nav.cpp, gpsiq_rinex.cpp: include/gpsiq_rows.h, gpsiq_extras.h) are host code in a library of their own, so that the
+// gpsiq_stage_math.cpp, gpsiq_nav.cpp, gpsiq_rinex.cpp: include/gpsiq_rows.h, gpsiq_extras.h) are host code in a library of their own, so that the
 // library a maintainer binds for the sample loop exports the boundary and nothing else.  They run on four of that library's
 // internals -- the worker pool, the quantiser, the exact carrier prefix, the calling thread's error text -- which libgpsiq.so hands
 // out by name through its one plumbing entry (csrc/gpsiq_plumbing.h): one pool, one quantiser and one gpsiq_last_error() for both.
@@ -23,7 +23,7 @@ F core(const char *name)
 
 int fail(int code, const char *fmt, ...)
 {
-    static const auto f = core<int (*)(int, const char *)>("set_error");
+    static const auto f = core<decltype(&set_error)>("set_error");
     char text[512];
     va_list ap;
     va_start(ap, fmt);
@@ -56,7 +56,7 @@ void chain_carrier(gpsiq_qchan_t *q, int nblocks, int nchan, int nsamp, const bo
 // is at its export limit (include/gpsiq_rows.h, "Output level").
 extern "C" __attribute__((visibility("default"))) int gpsiq_set_level(gpsiq_ctx_t *ctx, const gpsiq_level_t *lv)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_level_t *)>("set_level");
+    static const auto f = gpsiq::core<decltype(&gpsiq_set_level)>("set_level");
     return f(ctx, lv);
 }
 
@@ -66,8 +66,7 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_despread(gpsiq_ctx_t
                                                                      const void *src, size_t block_stride_bytes, void *hip_stream, int seg_len, int clip,
                                                                      gpsiq_despread_sum_t *sums, uint8_t *prn, gpsiq_block_stats_t *stats, float *kernel_ms)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, int, const void *, size_t, void *, int, int, gpsiq_despread_sum_t *, uint8_t *,
-                                              gpsiq_block_stats_t *, float *)>("despread");
+    static const auto f = gpsiq::core<decltype(&gpsiq_despread)>("despread");
     return f(ctx, block0, nblocks, nsamp, sample_size, src, block_stride_bytes, hip_stream, seg_len, clip, sums, prn, stats, kernel_ms);
 }
 
@@ -83,7 +82,7 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_pack(gpsiq_ctx_t *ct
                                                                  size_t src_stride, int bits, void *dst_dev, size_t dst_stride, void *hip_stream,
                                                                  uint64_t *clipped, float *kernel_ms)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, const void *, size_t, int, void *, size_t, void *, uint64_t *, float *)>("pack");
+    static const auto f = gpsiq::core<decltype(&gpsiq_pack)>("pack");
     return f(ctx, nblocks, nsamp, sample_size, src_dev, src_stride, bits, dst_dev, dst_stride, hip_stream, clipped, kernel_ms);
 }
 
@@ -91,7 +90,7 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_unpack(gpsiq_ctx_t *
                                                                    size_t src_stride, int sample_size, void *dst_dev, size_t dst_stride,
                                                                    void *hip_stream, float *kernel_ms)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, int, const void *, size_t, int, void *, size_t, void *, float *)>("unpack");
+    static const auto f = gpsiq::core<decltype(&gpsiq_unpack)>("unpack");
     return f(ctx, nblocks, nsamp, bits, src_dev, src_stride, sample_size, dst_dev, dst_stride, hip_stream, kernel_ms);
 }
 
@@ -99,30 +98,28 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_packe
                                                                                   int nsamp, double fs, int bits, void *dst_host,
                                                                                   size_t dst_block_stride, double *carr_phase_out)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, const gpsiq_chan_t *, int, int, int, double, int, void *, size_t, double *)>("generate_batch_packed");
+    static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_packed)>("generate_batch_packed");
     return f(ctx, ch, nblocks, nchan, nsamp, fs, bits, dst_host, dst_block_stride, carr_phase_out);
 }
 
 // The acquisition search runs on the context's device (csrc/gpsiq_acquire.cpp) and is exported here like the correlator (include/gpsiq_rows.h,
-// "Acquisition"); its two helpers, plain arithmetic, are in gpsiq_refresh.cpp beside gpsiq_cn0_estimate.
+// "Acquisition"); its two helpers, plain arithmetic, are in gpsiq_stage_math.cpp beside gpsiq_cn0_estimate.
 extern "C" __attribute__((visibility("default"))) int gpsiq_acquire(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
                                                                     const uint8_t *prn, int nprn, uint64_t code_step, int64_t carr_step0,
                                                                     int64_t carr_step_inc, int ndopp, int nshift, int ncoh, int nnoncoh, int hop,
                                                                     gpsiq_acquire_peak_t *peaks, double *power, gpsiq_despread_sum_t *corr, float *kernel_ms)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, const void *, void *, const uint8_t *, int, uint64_t, int64_t, int64_t, int, int, int,
-                                              int, int, gpsiq_acquire_peak_t *, double *, gpsiq_despread_sum_t *, float *)>("acquire");
+    static const auto f = gpsiq::core<decltype(&gpsiq_acquire)>("acquire");
     return f(ctx, nsamp, sample_size, src, hip_stream, prn, nprn, code_step, carr_step0, carr_step_inc, ndopp, nshift, ncoh, nnoncoh, hop, peaks, power, corr,
              kernel_ms);
 }
 
 // The follower runs on the context's device (csrc/gpsiq_follow.cpp) and is exported here like the search (include/gpsiq_rows.h, "Follow");
-// gpsiq_follow_gains and gpsiq_follow_bits, plain arithmetic, are in gpsiq_refresh.cpp beside gpsiq_acquire_decide.
+// gpsiq_follow_gains and gpsiq_follow_bits, plain arithmetic, are in gpsiq_stage_math.cpp beside gpsiq_acquire_decide.
 extern "C" __attribute__((visibility("default"))) int gpsiq_follow(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
                                                                    const gpsiq_follow_cfg_t *cfg, gpsiq_follow_state_t *state, int nprn,
                                                                    gpsiq_follow_epoch_t *epochs, int max_epochs, int *nepochs, float *kernel_ms)
 {
-    static const auto f = gpsiq::core<int (*)(gpsiq_ctx_t *, int, int, const void *, void *, const gpsiq_follow_cfg_t *, gpsiq_follow_state_t *, int,
-                                              gpsiq_follow_epoch_t *, int, int *, float *)>("follow");
+    static const auto f = gpsiq::core<decltype(&gpsiq_follow)>("follow");
     return f(ctx, nsamp, sample_size, src, hip_stream, cfg, state, nprn, epochs, max_epochs, nepochs, kernel_ms);
 }

@@ -1,0 +1,153 @@
+// gpsiq_stage_math.cpp -- the plain arithmetic that goes with the noise, the output level and the stream stages (include/gpsiq_rows.h):
+// what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
+// C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow.  Host code of
+// libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves: gpsiq_rows_link.cpp).
+#include "gpsiq_internal.h"
+
+#include <cmath>
+
+using namespace gpsiq;
+
+extern "C" {
+
+// C = (250*gain)^2 (the carrier table's amplitude), N0 = 2*sigma^2/fs (I and Q each of variance sigma^2 over fs Hz)
+double gpsiq_noise_sigma_for_cn0(double cn0_dbhz, double gain, double fs)
+{
+    return 250.0 * std::fabs(gain) * std::sqrt(fs / (2.0 * std::pow(10.0, cn0_dbhz / 10.0)));
+}
+
+// per component: a channel of amplitude 250*gain has mean square (250*gain)^2 / 2 in I and in Q, the noise sigma^2
+double gpsiq_composite_rms(const double *gain, int nchan, double sigma)
+{
+    double p = sigma * sigma;
+    for (int c = 0; gain && c < nchan; ++c) p += (250.0 * gain[c]) * (250.0 * gain[c]) / 2.0;
+    return std::sqrt(p);
+}
+
+uint32_t gpsiq_level_mult(double rms_in, double rms_out)
+{
+    const double m = std::rint(65536.0 * rms_out / rms_in);
+    if (!(m >= 1.0)) return 1u;                            // also NaN (0/0) and a negative ratio
+    return m > 16777215.0 ? 16777215u : (uint32_t) m;
+}
+
+// include/gpsiq_rows.h, "Despread": the signal is the mean of the in-phase sums, the noise per component the mean of their sample
+// variance and the quadrature sums' mean square; m^2 / v = seg_len * a^2 / sigma^2 and C/N0 = a^2 * fs / (2 sigma^2)
+int gpsiq_cn0_estimate(const gpsiq_despread_sum_t *sums, int count, int seg_len, double fs, double *cn0_dbhz, double *one_sigma_db)
+{
+    if (!cn0_dbhz || !one_sigma_db) return fail(GPSIQ_E_ARG, "null argument");
+    if (seg_len < 1 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad seg_len %d / fs %g", seg_len, fs);
+    if (count < 2) return fail(GPSIQ_E_RANGE, "C/N0 estimate needs two segments or more (have %d)", count);
+    if (!sums) return fail(GPSIQ_E_ARG, "null argument");
+    double m = 0.0;
+    for (int k = 0; k < count; ++k) m += (double) sums[k].i;
+    m /= (double) count;
+    double si = 0.0, sq = 0.0;
+    for (int k = 0; k < count; ++k) {
+        const double d = (double) sums[k].i - m, q = (double) sums[k].q;
+        si += d * d;
+        sq += q * q;
+    }
+    const double v = (si / (double) (count - 1) + sq / (double) count) / 2.0;
+    if (!(m > 0.0) || !(v > 0.0)) return fail(GPSIQ_E_RANGE, "C/N0 estimate: mean %g, noise variance %g: no signal or no noise", m, v);
+    const double T = (double) seg_len / fs;
+    const double cn0 = 10.0 * std::log10(m * m / (2.0 * v * T));
+    *cn0_dbhz = cn0;
+    *one_sigma_db = (10.0 / std::log(10.0)) * std::sqrt(1.0 / (double) count + 1.0 / ((double) count * T * std::pow(10.0, cn0 / 10.0)));
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Acquisition": the steps of a search, in gpsiq_qchan_t's units and ranges
+int gpsiq_acquire_steps(double fs, double f0_hz, double df_hz, uint64_t *code_step, int64_t *carr_step0, int64_t *carr_step_inc)
+{
+    if (!code_step || !carr_step0 || !carr_step_inc) return fail(GPSIQ_E_ARG, "null argument");
+    if (!(fs > 0.0) || !std::isfinite(fs)) return fail(GPSIQ_E_ARG, "bad fs %g", fs);
+    const double cs = std::rint(1.023e6 / fs * std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS));
+    const double c0 = std::rint(f0_hz / fs * std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS)), ci = std::rint(df_hz / fs * std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS));
+    const double lim = std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS - 1);
+    if (!(cs >= 1.0 && cs < std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS + 1)))
+        return fail(GPSIQ_E_RANGE, "code step %g at fs %g outside (0, 2^57)", cs, fs);
+    if (!(std::fabs(c0) < lim) || !(std::fabs(ci) < lim))
+        return fail(GPSIQ_E_RANGE, "carrier steps %g, %g at fs %g: |f / fs| must stay below 0.5", c0, ci, fs);
+    *code_step = (uint64_t) cs;
+    *carr_step0 = (int64_t) c0;
+    *carr_step_inc = (int64_t) ci;
+    return GPSIQ_OK;
+}
+
+// ibid.: the best cell of one satellite's grid against the largest cell away from its shift
+int gpsiq_acquire_decide(const double *power, int ndopp, int nshift, int guard, int *dopp, int *shift, double *ratio)
+{
+    if (!power || !dopp || !shift || !ratio) return fail(GPSIQ_E_ARG, "null argument");
+    if (ndopp < 1 || nshift < 1 || guard < 0) return fail(GPSIQ_E_ARG, "bad grid %d x %d / guard %d", ndopp, nshift, guard);
+    int bd = 0, bs = 0;
+    double best = power[0];
+    for (int d = 0; d < ndopp; ++d)
+        for (int s = 0; s < nshift; ++s)
+            if (power[(size_t) d * (size_t) nshift + (size_t) s] > best) { best = power[(size_t) d * (size_t) nshift + (size_t) s]; bd = d; bs = s; }
+    *dopp = bd; *shift = bs;
+    bool have = false;
+    double floor_max = 0.0;
+    for (int d = 0; d < ndopp; ++d)
+        for (int s = 0; s < nshift; ++s) {
+            if ((int64_t) s - bs <= guard && (int64_t) bs - s <= guard) continue;
+            const double v = power[(size_t) d * (size_t) nshift + (size_t) s];
+            if (!have || v > floor_max) { floor_max = v; have = true; }
+        }
+    if (!have) return fail(GPSIQ_E_RANGE, "no cell more than %d samples from shift %d", guard, bs);
+    if (!(floor_max > 0.0)) return fail(GPSIQ_E_RANGE, "the largest cell away from the peak is %g", floor_max);
+    *ratio = best / floor_max;
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Follow": the loop gains of a second-order phase lock behind a first-order frequency pull-in and a carrier-aided
+// first-order delay lock, in the integer units of the loop
+int gpsiq_follow_gains(double fs, double fll_gain, double pll_bn_hz, double dll_bn_hz, gpsiq_follow_cfg_t *cfg)
+{
+    if (!cfg) return fail(GPSIQ_E_ARG, "null argument");
+    for (double v : {fs, fll_gain, pll_bn_hz, dll_bn_hz})
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSIQ_E_ARG, "fs %g, gain %g, bandwidths %g, %g: each positive and finite", fs, fll_gain, pll_bn_hz, dll_bn_hz);
+    const double two_pi = 2.0 * 3.14159265358979323846, carr = std::ldexp(1.0, GPSIQ_CARR_FRAC_BITS), code = std::ldexp(1.0, GPSIQ_CODE_FRAC_BITS);
+    const double n0 = fs / 1000.0, wn = pll_bn_hz / 0.53;
+    const double g[4] = {std::rint(fll_gain * carr / (two_pi * n0)), std::rint(1.414 * wn / two_pi * carr / fs),
+                         std::rint(wn * wn * 1e-3 / two_pi * carr / fs), std::rint(4.0 * dll_bn_hz / (2.0 * fs) * code)};
+    for (double v : g)
+        if (!(v >= 0.0 && v < std::ldexp(1.0, 46))) return fail(GPSIQ_E_RANGE, "gain %g at fs %g outside [0, 2^46)", v, fs);
+    cfg->spacing = UINT64_C(1) << (GPSIQ_CODE_FRAC_BITS - 1);
+    cfg->pull_epochs = 100;
+    cfg->reserved = 0;
+    cfg->kf = (int64_t) g[0]; cfg->kp = (int64_t) g[1]; cfg->ki = (int64_t) g[2]; cfg->kd = (int64_t) g[3];
+    return GPSIQ_OK;
+}
+
+// ibid.: the bit edge is where 20-epoch sums of the in-phase prompt are largest; the bits are those sums' signs
+int gpsiq_follow_bits(const gpsiq_follow_epoch_t *epochs, int nepochs, int skip, int *offset, int8_t *bits, int max_bits, int *nbits)
+{
+    if (!epochs || !offset || !nbits || (!bits && max_bits > 0)) return fail(GPSIQ_E_ARG, "null argument");
+    if (skip < 0 || max_bits < 0) return fail(GPSIQ_E_ARG, "skip %d / max_bits %d", skip, max_bits);
+    const int64_t n = (int64_t) nepochs - (int64_t) skip;
+    if (n < 40) return fail(GPSIQ_E_RANGE, "bits need 40 epochs or more after skip (have %lld)", (long long) n);
+    const gpsiq_follow_epoch_t *e = epochs + skip;
+    int best = 0;
+    unsigned __int128 best_sum = 0;
+    for (int o = 0; o < 20; ++o) {
+        unsigned __int128 total = 0;
+        for (int64_t g = 0; o + 20 * (g + 1) <= n; ++g) {
+            int64_t sum = 0;                                       // |ip| < 2^39: twenty of them fit
+            for (int k = 0; k < 20; ++k) sum += e[o + 20 * g + k].ip;
+            total += (unsigned __int128) (sum < 0 ? -sum : sum);
+        }
+        if (total > best_sum) { best_sum = total; best = o; }      // ascending o: the first of equals stays
+    }
+    const int64_t groups = (n - best) / 20;
+    for (int64_t g = 0; g < groups && g < max_bits; ++g) {
+        int64_t sum = 0;
+        for (int k = 0; k < 20; ++k) sum += e[best + 20 * g + k].ip;
+        bits[g] = (int8_t) (sum > 0 ? 1 : sum < 0 ? -1 : 0);
+    }
+    *offset = best;
+    *nbits = (int) groups;
+    return GPSIQ_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
-// own_types.cpp -- the owning types the device context is made of (csrc/gpsiq_own.h) and the first-use routines built from them
-// (gpsiq_ctx::Chain::reserve, gpsiq_ctx::EvalDev::reserve / reserve_repair, csrc/gpsiq_ctx.h), on the CPU.
+// own_types.cpp -- the owning types the device context is made of and the one rule its groups of buffers grow by (csrc/gpsiq_own.h),
+// and the first-use routines built from them: gpsiq_ctx::Chain::reserve, gpsiq_ctx::EvalDev::reserve / reserve_repair
+// (csrc/gpsiq_ctx.h) and the reserve() of the four stream stages' sets (csrc/gpsiq_despread.h, gpsiq_pack.h, gpsiq_acquire.h,
+// gpsiq_follow.h), on the CPU.
 // TEST INFRASTRUCTURE: tests/test_own_types.py builds this file with the address and undefined-behaviour sanitizers and runs it.
 // No HIP runtime is linked: the handful of entry points the two headers call are defined below as counting fakes over malloc /
 // free.  Each fake counts its calls and the objects it has handed out that are still alive, aborts on a pointer it does not know
@@ -103,6 +105,10 @@ using gpsiq::DevBuf;
 using gpsiq::PinnedBuf;
 using gpsiq::Event;
 using gpsiq::Stream;
+using gpsiq::DespreadSet;
+using gpsiq::PackSet;
+using gpsiq::AcquireSet;
+using gpsiq::FollowSet;
 
 // (a), (b): a buffer of either kind grows only, by one free and one allocation of exactly the count asked for
 template <typename B>
@@ -229,12 +235,13 @@ static bool room(const B &b, size_t n) { return b.get() != nullptr && b.cap() >=
 // k.  Forget before free leaves that member empty and the ones behind it at their old size.  The next call may ask for LESS than
 // the failed one (small again): it must not take the set for whole because some member still has room -- every member has a
 // pointer and room for what was asked when a call returns GPSIQ_OK, here and when the set then grows to `big` after all.
+// `members`: how many resources the step makes, every member `whole` names (a lone buffer that grows with slack is a group of one).
 template <typename Set, typename Grow, typename Whole>
-static void grow_step_recovers(const char *what, Grow grow, Whole whole)
+static void grow_step_recovers(const char *what, long members, Grow grow, Whole whole)
 {
     const size_t small = 1000, big = 5000;
     long first = 0, step = 0;
-    { Set s; CHECK(grow(s, small) == GPSIQ_OK); first = g_created; CHECK(grow(s, big) == GPSIQ_OK && whole(s, big)); step = g_created - first; CHECK(step > 1); }
+    { Set s; CHECK(grow(s, small) == GPSIQ_OK); first = g_created; CHECK(grow(s, big) == GPSIQ_OK && whole(s, big)); step = g_created - first; CHECK(step == members); }
     reset();
     for (long k = 1; k <= step; ++k) {
         {
@@ -252,6 +259,43 @@ static void grow_step_recovers(const char *what, Grow grow, Whole whole)
     std::printf("%s: a grow step of %ld resources, failed at each, recovered by a smaller request\n", what, step);
 }
 
+// reserve_together itself, on a group of three of both kinds: at or below the SMALLEST capacity no call at all; above it every
+// member gets `cap`, in the order given; with the k-th allocation of the step failing, a later and smaller request completes the group
+static void group_grows_together()
+{
+    using gpsiq::reserve_together;
+    {
+        DevBuf<double> a; PinnedBuf<int> b; DevBuf<uint8_t> c;
+        CHECK(reserve_together(0, 64, a, b, c) == hipSuccess && calls_total() == 0);             // nothing asked for, nothing done
+        CHECK(reserve_together(100, 130, a, b, c) == hipSuccess);
+        CHECK(a.cap() == 130 && b.cap() == 130 && c.cap() == 130 && f_malloc.calls == 2 && f_hmalloc.calls == 1 && g_last_bytes == 130);   // c last
+        long before = calls_total();
+        for (size_t n : {(size_t) 130, (size_t) 100, (size_t) 1, (size_t) 0}) CHECK(reserve_together(n, n + 1000, a, b, c) == hipSuccess);
+        CHECK(calls_total() == before);
+        CHECK(b.reserve(500) == hipSuccess);                                                     // one member ahead of the others ...
+        before = calls_total();
+        CHECK(reserve_together(130, 999, a, b, c) == hipSuccess && calls_total() == before);     // ... the smallest capacity still decides
+        CHECK(reserve_together(131, 200, a, b, c) == hipSuccess && a.cap() == 200 && b.cap() == 500 && c.cap() == 200);
+        DevBuf<double> lone;
+        CHECK(reserve_together(10, 26, lone) == hipSuccess && lone.cap() == 26 && reserve_together(26, 99, lone) == hipSuccess && lone.cap() == 26);
+    }
+    reset();
+    for (long k = 1; k <= 3; ++k) {
+        {
+            DevBuf<double> a; PinnedBuf<int> b; DevBuf<uint8_t> c;
+            CHECK(reserve_together(1000, 1100, a, b, c) == hipSuccess);
+            g_fail_created_at = 3 + k;
+            CHECK(reserve_together(5000, 5100, a, b, c) == hipErrorOutOfMemory);                 // the first error is the one returned
+            CHECK((k == 1 ? a.cap() : k == 2 ? b.cap() : c.cap()) == 0 && g_created == 3 + k);   // ... and nothing behind it was touched
+            CHECK(reserve_together(1000, 1100, a, b, c) == hipSuccess && room(a, 1000) && room(b, 1000) && room(c, 1000));
+            const long before = calls_total();
+            CHECK(reserve_together(1000, 1100, a, b, c) == hipSuccess && calls_total() == before);
+        }
+        reset();
+    }
+    std::printf("group: a grow step of 3 members, failed at each, recovered by a smaller request\n");
+}
+
 int main()
 {
     grows_only<DevBuf<double>>(f_malloc, f_free);
@@ -263,15 +307,44 @@ int main()
     { PinnedBuf<int> b; CHECK(b.reserve(1) == hipSuccess && g_last_flags == hipHostMallocDefault); }
     reset();
     ensure_is_idempotent();
+    group_grows_together();
     first_use_recovers<gpsiq_ctx::Chain>("chain", [](gpsiq_ctx::Chain &k) { return k.reserve(1000); });
     first_use_recovers<gpsiq_ctx::EvalDev>("device evaluation", [](gpsiq_ctx::EvalDev &e) { return e.reserve(1000, true, true); });
     first_use_recovers<gpsiq_ctx::EvalDev>("repair", [](gpsiq_ctx::EvalDev &e) { return e.reserve_repair(300); });
-    grow_step_recovers<gpsiq_ctx::Chain>("chain", [](gpsiq_ctx::Chain &k, size_t n) { return k.reserve(n); }, [](const gpsiq_ctx::Chain &k, size_t n) {
+    first_use_recovers<DespreadSet>("despread", [](DespreadSet &d) { return d.reserve(1000, 1000, 1000); });
+    first_use_recovers<PackSet>("pack", [](PackSet &p) { return p.reserve(1000, 1000); });
+    first_use_recovers<AcquireSet>("acquire", [](AcquireSet &a) { return a.reserve(1000, 1000, 1000, 1000); });
+    first_use_recovers<FollowSet>("follow", [](FollowSet &f) { return f.reserve(1000); });
+    grow_step_recovers<gpsiq_ctx::Chain>("chain", 5, [](gpsiq_ctx::Chain &k, size_t n) { return k.reserve(n); }, [](const gpsiq_ctx::Chain &k, size_t n) {
         return room(k.d_in, n) && room(k.h_in, n) && room(k.d_prep, n * k.kPrepBytes) && room(k.d_maps, n) && room(k.h_maps, n); });
-    grow_step_recovers<gpsiq_ctx::EvalDev>("device evaluation", [](gpsiq_ctx::EvalDev &e, size_t n) { return e.reserve(n, true, true); },
+    grow_step_recovers<gpsiq_ctx::EvalDev>("device evaluation", 4, [](gpsiq_ctx::EvalDev &e, size_t n) { return e.reserve(n, true, true); },
         [](const gpsiq_ctx::EvalDev &e, size_t n) { return room(e.d_chan, n * e.kChanBytes) && room(e.h_chan, n * e.kChanBytes) && room(e.d_raw, n) && room(e.d_seeds, n); });
-    grow_step_recovers<gpsiq_ctx::EvalDev>("repair", [](gpsiq_ctx::EvalDev &e, size_t n) { return e.reserve_repair(n); }, [](const gpsiq_ctx::EvalDev &e, size_t n) {
+    grow_step_recovers<gpsiq_ctx::EvalDev>("repair", 4, [](gpsiq_ctx::EvalDev &e, size_t n) { return e.reserve_repair(n); }, [](const gpsiq_ctx::EvalDev &e, size_t n) {
         return room(e.d_slot, n) && room(e.h_slot, n) && room(e.d_col, n) && room(e.h_col, n); });
+    grow_step_recovers<DespreadSet>("despread", 6, [](DespreadSet &d, size_t n) { return d.reserve(n, n, n); }, [](const DespreadSet &d, size_t n) {
+        return room(d.d_sums, n) && room(d.h_sums, n) && room(d.d_prn, n) && room(d.h_prn, n) && room(d.d_stats, n) && room(d.h_stats, n); });
+    grow_step_recovers<PackSet>("pack", 4, [](PackSet &p, size_t n) { return p.reserve(n, n); }, [](const PackSet &p, size_t n) {
+        return room(p.d_count, 1) && room(p.h_count, 1) && room(p.d_render[0], n) && room(p.d_render[1], n) && room(p.d_packed[0], n) && room(p.d_packed[1], n); });
+    grow_step_recovers<AcquireSet>("acquire", 5, [](AcquireSet &a, size_t n) { return a.reserve(n, n, n, n); }, [](const AcquireSet &a, size_t n) {
+        return room(a.d_prn, 32) && room(a.h_prn, 32) && room(a.d_power, n) && room(a.d_peaks, n) && room(a.h_peaks, n) && room(a.d_corr, n) && room(a.d_planes, n); });
+    grow_step_recovers<FollowSet>("follow", 1, [](FollowSet &f, size_t n) { return f.reserve(n); }, [](const FollowSet &f, size_t n) {
+        return room(f.d_state, 32) && room(f.h_state, 32) && room(f.d_count, 32) && room(f.h_count, 32) && room(f.d_epochs, n); });
+    // the sizes a grown stage set ends with are each site's own: n + n/4 + 256, but + 16 for the stream statistics and + 64 for peaks and records
+    {
+        DespreadSet d; AcquireSet a; FollowSet f; PackSet p;
+        CHECK(d.reserve(5000, 5000, 5000) == GPSIQ_OK && a.reserve(5000, 5000, 5000, 5000) == GPSIQ_OK && f.reserve(5000) == GPSIQ_OK && p.reserve(5000, 5000) == GPSIQ_OK);
+        const size_t base = 5000 + 5000 / 4;
+        CHECK(d.d_sums.cap() == base + 256 && d.h_sums.cap() == base + 256 && d.d_prn.cap() == base + 256 && d.h_prn.cap() == base + 256);
+        CHECK(d.d_stats.cap() == base + 16 && d.h_stats.cap() == base + 16);
+        CHECK(a.d_power.cap() == base + 256 && a.d_peaks.cap() == base + 64 && a.h_peaks.cap() == base + 64 && a.d_corr.cap() == base + 256 && a.d_planes.cap() == base + 256);
+        CHECK(f.d_epochs.cap() == base + 64);
+        CHECK(p.d_render[0].cap() == base + 256 && p.d_render[1].cap() == base + 256 && p.d_packed[0].cap() == base + 256 && p.d_packed[1].cap() == base + 256);
+        PackSet q;                                                                   // gpsiq_pack / gpsiq_unpack: the counter alone, no stream
+        CHECK(q.reserve(0, 0) == GPSIQ_OK && room(q.d_count, 1) && room(q.h_count, 1) && !q.pack_stream.get() && !q.d_render[0].get());
+        AcquireSet g;                                                                // the generic kernel without correlations: neither buffer made
+        CHECK(g.reserve(100, 10, 0, 0) == GPSIQ_OK && !g.d_corr.get() && !g.d_planes.get() && room(g.d_power, 100));
+    }
+    reset();
     // the sizes a grown chain ends with are the policy's, and at or below them nothing is called
     {
         gpsiq_ctx::Chain k;
@@ -289,6 +362,7 @@ int main()
         CHECK(c.d_tab.reserve(1) == hipSuccess && c.buf[2].h_patch.reserve(256) == hipSuccess && c.aslot[3].out.reserve(16) == hipSuccess);
         CHECK(c.buf[0].use[3].ev.ensure() == hipSuccess && c.d_noise_tab.reserve(4) == hipSuccess && c.d_zero_tab.reserve(4) == hipSuccess);
         CHECK(c.chain.reserve(10) == GPSIQ_OK && c.evd.reserve(10, false, false) == GPSIQ_OK);
+        CHECK(c.dsp.reserve(10, 10, 1) == GPSIQ_OK && c.pack.reserve(10, 10) == GPSIQ_OK && c.acq.reserve(10, 10, 10, 10) == GPSIQ_OK && c.fol.reserve(10) == GPSIQ_OK);
     }
     reset();
     std::printf("own types ok\n");

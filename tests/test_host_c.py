@@ -67,7 +67,8 @@ def test_host_half_under_sanitizers(tmp_path, san):
     if "undefined" in san:
         flags.append("-fno-sanitize-recover=undefined")
     objs = []
-    for src in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_refwalk.cpp", "gpsiq_chain.cpp", "gpsiq_refresh.cpp", "gpsiq_nav.cpp", "gpsiq_rinex.cpp"):
+    for src in ("gpsiq_host.cpp", "gpsiq_exact.cpp", "gpsiq_refwalk.cpp", "gpsiq_chain.cpp", "gpsiq_refresh.cpp", "gpsiq_stage_math.cpp", "gpsiq_nav.cpp",
+                "gpsiq_rinex.cpp"):
         o = str(tmp_path / (src + ".o"))
         b = subprocess.run(["g++", "-std=c++17", *flags, "-c", os.path.join(csrc, src), "-o", o], capture_output=True, text=True)
         if b.returncode != 0:
@@ -154,6 +155,17 @@ def test_exact_mode_header_compiles_on_its_own(header):
     """Each header of the exact-mode host half is an interface of its own: a translation unit of nothing but its include compiles."""
     csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-x", "c++", "-"],
+                       input='#include "%s"\n' % header, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("header", ["gpsiq_own.h", "gpsiq_despread.h", "gpsiq_pack.h", "gpsiq_acquire.h", "gpsiq_follow.h"])
+def test_stage_header_compiles_on_its_own(header):
+    """The owning types and each stream stage's header are interfaces of their own (the context includes them, not the other way
+    round): a translation unit of nothing but the include compiles, against the HIP runtime's host declarations alone."""
+    csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-x", "c++", "-"],
                        input='#include "%s"\n' % header, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
 
