@@ -262,7 +262,12 @@ int gpsiq_wait(gpsiq_ctx_t *ctx);
  * a long batch (48 blocks or more in GPSIQ_NCO_REFERENCE; in the fixed-point model ~300 descriptors per host thread) is quantised -- and in
  * GPSIQ_NCO_REFERENCE chained and evaluated -- on the device, which reads page-locked and device-resident descriptors where
  * they lie (pageable ones are first cut down to 64 bytes each by the host pool); shorter batches, and every batch under
- * GPSIQ_EVAL=host, take the host quantiser / walker.  Either way a long batch is worked through in pieces, piece k+1 staged
+ * GPSIQ_EVAL=host or GPSIQ_CHAIN, take the host quantiser / walker, which reads ch on the host: device-resident descriptors are
+ * then copied down first, all nblocks*nchan of them in one copy into page-locked staging the context keeps (the batch the device
+ * takes copies only its first and last block).  Where ch lies is looked up once per call, before anything is queued: memory the HIP
+ * runtime does not know is taken for pageable host memory (it is not probed), and memory neither the host nor the context's device
+ * can read -- another device's -- is GPSIQ_E_ARG, the text saying which, the carried phases and the noise block counter untouched.
+ * Either way a long batch is worked through in pieces, piece k+1 staged
  * under the kernel of piece k, and the call returns when everything has landed.  Descriptors are range-checked on the way: when a
  * descriptor is refused the call returns the error (the first refused block, in the host quantiser's words) after other
  * pieces have been rendered -- dst and the resident descriptor set are then undefined; the carried phases are untouched. */
@@ -277,7 +282,8 @@ int gpsiq_generate_batch(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, 
  * one host thread per context; nothing passes between the devices.  Results land in timeline order:
  *   host_dst != NULL: one host buffer of nblocks*2*nsamp elements (page-locked: gpsiq_host_alloc);
  *   else dev_dst[i]:  device buffer on ctx[i]'s device for range i (its blocks packed, no padding).
- * Carrier continuation between calls follows gpsiq_generate_batch, with ctx[0] keeping the state. */
+ * Carrier continuation between calls follows gpsiq_generate_batch, with ctx[0] keeping the state.
+ * ch is host memory, pageable or page-locked (the host side of the timeline runs once, on the host); device memory is GPSIQ_E_ARG. */
 int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_chan_t *ch, int nblocks, int nchan,
                                int nsamp, double fs, int sample_size, void *host_dst, void *const *dev_dst,
                                double *carr_phase_out);

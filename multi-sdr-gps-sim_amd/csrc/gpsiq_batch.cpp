@@ -525,15 +525,49 @@ int gpsiq_generate_quantized(gpsiq_ctx_t *c, const gpsiq_qchan_t *q, int nblocks
     return rc;
 }
 
-static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
+// ---- where the descriptors lie (gpsiq_ctx.h: SrcKind) -------------------------------------------------------------------------
+int gpsiq_rows_kind(const gpsiq_ctx *c, const void *ch, const char *host_call, SrcKind *kind)
+{
+    SrcKind unused;
+    if (!kind) kind = &unused;                            // (a call that only wants the refusal)
+    *kind = kSrcPageable;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, ch) != hipSuccess) { (void) hipGetLastError(); return GPSIQ_OK; }     // not the runtime's: the host's
+    if (a.type == hipMemoryTypeHost) { *kind = kSrcPinned; return GPSIQ_OK; }
+    if (a.type == hipMemoryTypeArray) return fail(GPSIQ_E_ARG, "descriptors in a HIP array: ch is linear memory");
+    if (a.type != hipMemoryTypeDevice) return GPSIQ_OK;                  // unregistered, managed: read through the host
+    if (host_call)
+        return fail(GPSIQ_E_ARG, "%s: descriptors in device memory (device %d); this call reads ch on the host, pageable or page-locked", host_call, a.device);
+    if (a.device != c->device)
+        return fail(GPSIQ_E_ARG, "descriptors in device memory of device %d, the context is on device %d: ch is host memory or the context's device's",
+                    a.device, c->device);
+    *kind = kSrcDevice;
+    return GPSIQ_OK;
+}
+
+// Descriptors in the context's device memory and the host path about to read them (the device path declined the batch, or its
+// lists overflowed): the rows come down once, into page-locked staging the context keeps, and the call goes on with that pointer.
+// (The path the device takes copies nothing but its two edge blocks.)
+static int rows_to_host(gpsiq_ctx *c, const gpsiq_chan_t **ch, size_t n)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(reserve_together(n, n + n / 4 + 16, c->h_rows));
+    HIP_TRY(hipMemcpy(c->h_rows.get(), *ch, n * sizeof(gpsiq_chan_t), hipMemcpyDeviceToHost));
+    *ch = c->h_rows.get();
+    return GPSIQ_OK;
+}
+
+static int generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, SrcKind kind, int nblocks, int nchan, int nsamp,
                           double fs, int sample_size, void *dst, int dst_is_device, double *carr_phase_out)
 {
     int rc = GPSIQ_OK;
     {   // descriptors quantised / evaluated on the device (gpsiq_evaldev.cpp) where that path takes the call
         int handled = 0;
-        rc = gpsiq_generate_device(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out, nullptr, &handled);
+        rc = gpsiq_generate_device(c, ch, kind, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out, nullptr, &handled);
         if (handled) return rc;
     }
+    // from here on the host reads ch
+    if (kind == kSrcDevice && (rc = rows_to_host(c, &ch, (size_t) nblocks * (size_t) nchan)) != GPSIQ_OK) return rc;
     if (c->nco_mode == GPSIQ_NCO_REFERENCE)
         return gpsiq_generate_reference_host(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out);
     const char *trace_env = std::getenv("GPSIQ_TRACE");
@@ -614,8 +648,11 @@ int gpsiq_generate_batch(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, in
     int rc = gpsiq_check_gen_args(c, ch, dst, nblocks, nchan, nsamp, fs, sample_size);
     if (rc) return rc;
     if (nblocks == 0) return GPSIQ_OK;                    // an empty batch leaves the carried phases alone
+    SrcKind kind;
+    rc = gpsiq_rows_kind(c, ch, nullptr, &kind);          // once per call; a pointer nobody here can read: refused with nothing queued
+    if (rc) return rc;
     c->call_block = c->noise.next_block;
-    rc = generate_batch(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out);
+    rc = generate_batch(c, ch, kind, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out);
     if (rc == GPSIQ_OK) c->noise.next_block += (uint64_t) nblocks;
     return rc;
 }
@@ -627,11 +664,14 @@ int gpsiq_generate_seeded(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, i
     if (rc) return rc;
     if (!carr_start && nblocks) return fail(GPSIQ_E_ARG, "null start states");
     if (nblocks == 0) return GPSIQ_OK;
+    SrcKind kind;                                         // ch is host memory, pageable or page-locked: the start states are checked against it here
+    rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_seeded", &kind);
+    if (rc) return rc;
     for (size_t k = 0; k < (size_t) nblocks * (size_t) nchan; ++k)
         if (ch[k].prn > 0 && !(carr_start[k] >= 0.0 && carr_start[k] <= 1.0)) return fail(GPSIQ_E_RANGE, "start phase %zu outside [0, 1]", k);
     c->call_block = c->noise.next_block;
     int handled = 0;
-    rc = gpsiq_generate_device(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start, &handled);
+    rc = gpsiq_generate_device(c, ch, kind, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start, &handled);
     if (!handled) rc = gpsiq_generate_reference_host(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, nullptr, carr_start);
     if (rc == GPSIQ_OK) c->noise.next_block += (uint64_t) nblocks;
     return rc;

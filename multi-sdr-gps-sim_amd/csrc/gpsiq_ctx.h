@@ -120,6 +120,9 @@ struct gpsiq_ctx {
     // between calls (a fresh 1.5 MB per call is four hundred page faults on the thread everything else waits for)
     std::vector<gpsiq_qchan_t> ref_q;
     std::vector<double>        ref_start;
+    // gpsiq_generate_batch with descriptors in the context's device memory and the host path about to read them: the rows, copied
+    // down once per call, page-locked (gpsiq_batch.cpp: rows_to_host)
+    PinnedBuf<gpsiq_chan_t>    h_rows;
     // the carrier chain of GPSIQ_NCO_REFERENCE on the device (gpsiq_chain_maps_device): inputs, estimates and maps of the
     // timeline being worked through, device side and page-locked staging, kept between calls
     struct Chain {
@@ -315,9 +318,17 @@ bool gpsiq_chain_on_device(int nblocks, int nsamp, int nchan);
 void gpsiq_chain_stage_inputs(gpsiq_ctx *c, const gpsiq_chan_t *ch, int b0, int b1, int nchan);
 int gpsiq_chain_maps_staged(gpsiq_ctx *c, int nblocks, int nchan, double fs, int nsamp, const gpsiq_chain_est_t *start, int max_stretches,
                             gpsiq_chain_est_t *end);
+// Where a call's descriptors lie.  gpsiq_rows_kind is the one place that asks the runtime, once per call, at the call's entry and
+// before anything is queued: host memory the runtime does not know is pageable (it is not probed), device memory of the context's
+// device is kSrcDevice, and what neither the host nor that device can read (another device's memory, a HIP array) is GPSIQ_E_ARG
+// with the kind of pointer in the text.  host_call: the name of a call that reads ch on the host by contract
+// (gpsiq_generate_seeded, gpsiq_generate_batch_multi, gpsiq_generate_batch_packed) -- device memory is GPSIQ_E_ARG there too.
+namespace gpsiq { enum SrcKind { kSrcPageable = 0, kSrcPinned = 1, kSrcDevice = 2 }; }
+int gpsiq_rows_kind(const gpsiq_ctx *c, const void *ch, const char *host_call, gpsiq::SrcKind *kind);
 // gpsiq_evaldev.cpp: the same call (either NCO model) with the descriptors quantised / evaluated on the device.  *handled = 0:
-// not taken (too short a batch, switched off), the caller goes on with the host path
-int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+// not taken (too short a batch, switched off, or its lists overflowed), the caller goes on with the host path -- which reads ch
+// on the host: rows of kSrcDevice are the caller's to copy down first
+int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, gpsiq::SrcKind kind, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                           void *dst, int dst_is_device, double *carr_phase_out, const double *seeds, int *handled);
 
 namespace gpsiq {

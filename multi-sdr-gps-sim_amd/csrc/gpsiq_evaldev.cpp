@@ -35,18 +35,6 @@ int eval_block_host(const gpsiq_chan_t &ch, double start, const uint64_t *seed, 
 
 namespace {
 
-enum SrcKind { kSrcPageable = 0, kSrcPinned = 1, kSrcDevice = 2 };
-
-SrcKind classify(const void *p, int device, const void **dev_ptr)
-{
-    *dev_ptr = nullptr;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void) hipGetLastError(); return kSrcPageable; }
-    if (a.type == hipMemoryTypeDevice && a.device == device) { *dev_ptr = p; return kSrcDevice; }
-    if (a.type == hipMemoryTypeHost) return kSrcPinned;
-    return kSrcPageable;               // unregistered, managed, another device's: through the host
-}
-
 static_assert(sizeof(ev::DChan) == gpsiq_ctx::EvalDev::kChanBytes, "the rows d_chan / h_chan are sized for");
 constexpr unsigned kPatchCap = gpsiq_ctx::EvalDev::kPatchCap, kHostCap = gpsiq_ctx::EvalDev::kHostCap;
 
@@ -156,7 +144,8 @@ static bool device_path_wanted(const gpsiq_ctx *c, int nblocks, int nchan)
     return (long) nblocks * nchan >= 300L * (host_threads() > 0 ? host_threads() : 1);
 }
 
-int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+// (kind: where ch lies, as the call's entry classified it -- gpsiq_rows_kind, gpsiq_batch.cpp)
+int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, SrcKind kind, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                           void *dst, int dst_is_device, double *carr_phase_out, const double *seeds, int *handled)
 {
     *handled = 0;
@@ -169,8 +158,7 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
     gpsiq_ctx::EvalDev &e = c->evd;
     const size_t n = (size_t) nblocks * (size_t) nchan;
     const double delt = 1.0 / fs;
-    const void *dev_src = nullptr;
-    const SrcKind kind = classify(ch, c->device, &dev_src);
+    const void *dev_src = kind == kSrcDevice ? ch : nullptr;
     int rc = c->chain.reserve(n);
     if (rc == GPSIQ_OK) rc = e.reserve(n, kind == kSrcPinned, seeds != nullptr);
     if (rc) return rc;
@@ -552,9 +540,11 @@ int gpsiq_generate_device(gpsiq_ctx *c, const gpsiq_chan_t *ch, int nblocks, int
             gpsiq_note_kernel_rate((double) timed_blocks * (double) nsamp * (double) nchan / (ms * 1e-3));
     }
     if (fall_back) {
-        // the lists overflowed: the host path does the whole call again (dst is rewritten)
+        // the lists overflowed: not handled after all -- the caller's host path does the whole call again (dst is rewritten), from
+        // descriptors the host can read
         __atomic_fetch_add(&g_evd_stats[5], 1, __ATOMIC_RELAXED);
-        return gpsiq_generate_reference_host(c, ch, nblocks, nchan, nsamp, fs, sample_size, dst, dst_is_device, carr_phase_out, seeds);
+        *handled = 0;
+        return GPSIQ_OK;
     }
 
     // ---- the resident set and the carried state ------------------------------------------------------------------------------

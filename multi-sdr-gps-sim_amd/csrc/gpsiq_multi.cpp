@@ -204,6 +204,8 @@ int gpsiq_generate_batch_multi(gpsiq_ctx_t *const *ctx, int ndev, const gpsiq_ch
     int rc = gpsiq_check_gen_args(ctx[0], ch, host_dst ? host_dst : (void *) dev_dst, nblocks, nchan, nsamp, fs, sample_size);
     if (rc) return rc;
     if (nblocks == 0) return GPSIQ_OK;
+    rc = gpsiq_rows_kind(ctx[0], ch, "gpsiq_generate_batch_multi", nullptr);     // the host side of the timeline runs once, here: ch is host memory
+    if (rc) return rc;
     // the ranges, once: everything after reads this table
     std::vector<gpsiq_qchan_t> q((size_t) nblocks * (size_t) nchan);
     const Call call = {q.data(), nchan, nsamp, sample_size};

@@ -130,6 +130,8 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
     if (!c->level.mult || c->level.qmax > qmax)
         return fail(GPSIQ_E_STATE, "packed output at %d bits needs the output level on with qmax <= %d (gpsiq_set_level)", bits, qmax);
     if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
+    // the pieces' first rows are rewritten on the host: ch is host memory
+    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_packed", nullptr)) return rc;
     const char *env = std::getenv("GPSIQ_PACK_PIECE_BLOCKS");
     const int piece = pack_piece_blocks(nblocks, blk_bytes, env ? std::atol(env) : 0);
     const int npieces = (nblocks + piece - 1) / piece;

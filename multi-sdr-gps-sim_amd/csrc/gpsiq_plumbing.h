@@ -40,7 +40,8 @@ void gpsiq_carrier_table(int16_t cos512[512], int16_t sin512[512]);
 /* One shard of a time-sharded run in GPSIQ_NCO_REFERENCE, whatever the context's mode: render nblocks blocks whose start
  * states are known (carr_start[nblocks][nchan], this range's rows of gpsiq_reference_chain; ch[b][i].carr_phase is not
  * read) into dst, host or device as gpsiq_generate_batch -- evaluated and rendered in pieces like it, with no reference
- * to the blocks before the range.  Synchronous.  Does not touch the carrier continuation state. */
+ * to the blocks before the range.  Synchronous.  Does not touch the carrier continuation state.  ch is host memory, pageable
+ * or page-locked (the start states are checked against it on the host); device memory is GPSIQ_E_ARG. */
 int gpsiq_generate_seeded(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs,
                           int sample_size, const double *carr_start, void *dst, int dst_is_device);
 

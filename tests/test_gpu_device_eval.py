@@ -39,22 +39,30 @@ def rough_timeline(nb, nc, seed):
     return d
 
 
-def render(ctx, d, ns, fs, ss, mode, how, monkeypatch, kind="pageable"):
+def render(ctx, d, ns, fs, ss, mode, how, monkeypatch, kind="pageable", to="device", offset=0):
+    """One gpsiq_generate_batch call -> (bytes, carr_out).  how: GPSIQ_EVAL for the call (None: unset, the library decides); kind:
+    where the descriptors lie; to: device or host destination; offset: the rows start that many bytes into their allocation."""
     import torch
-    monkeypatch.setenv("GPSIQ_EVAL", how)
+    if how is None:
+        monkeypatch.delenv("GPSIQ_EVAL", raising=False)
+    else:
+        monkeypatch.setenv("GPSIQ_EVAL", how)
     ctx.set_nco_mode(mode)
     nb, nc = d.shape
     carr = np.zeros(nc)
-    out = torch.zeros(nb * 2 * ns * ss, dtype=torch.uint8, device="cuda")
     keep = None
     if kind == "pageable":
         src = d
-    elif kind == "pinned":
-        keep = torch.from_numpy(d.view(np.uint8).reshape(-1).copy()).pin_memory()
-        src = (keep.data_ptr(), nb, nc)
     else:
-        keep = torch.from_numpy(d.view(np.uint8).reshape(-1).copy()).cuda()
-        src = (keep.data_ptr(), nb, nc)
+        keep = torch.from_numpy(np.concatenate([np.zeros(offset, np.uint8), d.view(np.uint8).reshape(-1)]))
+        keep = keep.pin_memory() if kind == "pinned" else keep.cuda()
+        src = (keep.data_ptr() + offset, nb, nc)
+    if to == "host":
+        out = ctx.generate_batch(src, ns, fs, ss, carr_out=carr)
+        del keep
+        return out.view(np.uint8).reshape(-1), carr
+    out = torch.zeros(nb * 2 * ns * ss, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()        # the fill runs on torch's stream, the library renders on non-blocking streams of its own: dst is the caller's to have ready
     ctx.generate_batch(src, ns, fs, ss, device_ptr=out.data_ptr(), carr_out=carr)
     torch.cuda.synchronize()
     del keep

@@ -82,6 +82,22 @@ assert np.array_equal(got, want) and carr_f.tobytes() == carr_h.tobytes()
 del os.environ["GPSIQ_TEST_LIST_CAP"]
 got = ctx.generate_batch(d2, ns2, fs2, SC08)                                # and the context is as good as before
 assert np.array_equal(got, want) and gpsiq.device_eval_stats()[5] == s2[5]
+# the same with the descriptors in page-locked and in device memory: the host path that does the call again reads rows the host can
+# read (device-resident ones are copied down for it)
+import torch
+os.environ["GPSIQ_TEST_LIST_CAP"] = "3"
+for place in ("pinned", "device"):
+    rows = torch.from_numpy(d2.view(np.uint8).reshape(-1).copy())
+    rows = rows.pin_memory() if place == "pinned" else rows.cuda()
+    s3 = gpsiq.device_eval_stats()
+    carr_m = np.zeros(nc)
+    got = ctx.generate_batch((rows.data_ptr(), nb2, nc), ns2, fs2, SC08, carr_out=carr_m)
+    s4 = gpsiq.device_eval_stats()
+    assert s4[5] == s3[5] + 1, (place, s3, s4)
+    assert np.array_equal(got, want), place
+    assert carr_m.tobytes() == carr_h.tobytes(), place
+    del rows
+del os.environ["GPSIQ_TEST_LIST_CAP"]
 print("fall-back ok")
 ctx.close()
 print("all ok")
