@@ -74,6 +74,41 @@ def acquire(orc, stream, prns, code_step, carr_step0, carr_step_inc, ndopp, nshi
     return peaks, power, corr
 
 
+def carrier_index_from(step, first, count):
+    """int64 [count]: ((m * step) mod 2^59) >> 50 for the ABSOLUTE samples m = first .. first + count - 1 (64-bit wrapping product)"""
+    m = np.arange(count, dtype=np.uint64) + np.uint64(first)
+    return (((m * np.uint64(int(step) % (1 << 64))) & np.uint64(MASK59)) >> np.uint64(50)).astype(np.int64)
+
+
+def acquire_windows(orc, windows, first, prns, code_step, carr_step0, carr_step_inc, ndopp, nshift, ncoh):
+    """The search of a span too long to hold densely, from its dwell windows alone: windows[k] the elements (interleaved I, Q) of samples
+    [first[k], first[k] + nshift - 1 + ncoh) of the span, first[k] = k * hop the window's ABSOLUTE first sample -- the carrier index of a
+    sample is taken at its absolute m, everything else is local to the window.  No sample outside the windows is an input of the
+    contract's sums.  -> acquire()'s (peaks, power, corr)."""
+    s, c = orc.tables()
+    s, c = s.astype(np.int64), c.astype(np.int64)
+    ca = np.stack([sampled_code(orc, p, code_step, ncoh) for p in prns]).astype(np.float64)
+    width = nshift - 1 + ncoh
+    corr = np.zeros((len(prns), ndopp, len(windows), nshift), dtype=DESPREAD_SUM_DTYPE)
+    for k, (w, m0) in enumerate(zip(windows, first)):
+        x = np.asarray(w).astype(np.int64).reshape(-1, 2)
+        assert len(x) == width
+        for d in range(ndopp):
+            idx = carrier_index_from(int(carr_step0) + d * int(carr_step_inc), int(m0), width)
+            yi, yq = x[:, 0] * c[idx] + x[:, 1] * s[idx], x[:, 1] * c[idx] - x[:, 0] * s[idx]
+            for y, f in ((yi, "i"), (yq, "q")):
+                corr[f][:, d, k, :] = (np.lib.stride_tricks.sliding_window_view(y.astype(np.float64), ncoh) @ ca.T).T.astype(np.int64)
+    power = np.zeros((len(prns), ndopp, nshift), dtype=np.float64)
+    for k in range(len(windows)):
+        xi, xq = corr["i"][:, :, k, :].astype(np.float64), corr["q"][:, :, k, :].astype(np.float64)
+        power = power + (xi * xi + xq * xq)
+    peaks = np.zeros((len(prns), ndopp), dtype=ACQ_PEAK_DTYPE)
+    at = power.argmax(axis=2)
+    peaks["shift"] = at
+    peaks["power"] = np.take_along_axis(power, at[:, :, None], axis=2)[:, :, 0]
+    return peaks, power, corr
+
+
 def acquire_direct(orc, stream, prn, code_step, step, s, k, hop, ncoh):
     """one (Xi, Xq) in Python integers, sample by sample: what the matrix product above is held against"""
     sn, cs = orc.tables()
@@ -84,6 +119,20 @@ def acquire_direct(orc, stream, prn, code_step, step, s, k, hop, ncoh):
         m = s + k * hop + n
         idx = ((m * int(step)) % (1 << 59)) >> 50
         i, q, rc, rs = int(x[m, 0]), int(x[m, 1]), int(cs[idx]), int(sn[idx])
+        xi += (i * rc + q * rs) * int(ca[n])
+        xq += (q * rc - i * rs) * int(ca[n])
+    return xi, xq
+
+
+def acquire_direct_window(orc, window, first, prn, code_step, step, s, ncoh):
+    """acquire_direct for one dwell given as its window (acquire_windows' layout): the carrier at the absolute sample first + s + n"""
+    sn, cs = orc.tables()
+    x = np.asarray(window).astype(np.int64).reshape(-1, 2)
+    ca = sampled_code(orc, prn, code_step, ncoh)
+    xi = xq = 0
+    for n in range(ncoh):
+        idx = (((int(first) + s + n) * int(step)) % (1 << 59)) >> 50
+        i, q, rc, rs = int(x[s + n, 0]), int(x[s + n, 1]), int(cs[idx]), int(sn[idx])
         xi += (i * rc + q * rs) * int(ca[n])
         xq += (q * rc - i * rs) * int(ca[n])
     return xi, xq

@@ -148,6 +148,20 @@ def follow(orc, stream, cfg, states, max_epochs):
     return rec, count, out
 
 
+def follow_rebased(orc, tail, base, cfg, states, max_epochs):
+    """follow() on a span too long to hold, from its tail: `tail` the elements of samples [base, nsamp) of the span, every state's
+    `sample` at or past base.  Nothing in an epoch depends on the absolute sample but where it reads (the carrier runs from carr_phase),
+    so the run is follow() on the tail with `sample` rebased in the states going in, and in the records and states coming out."""
+    states = np.array(np.atleast_1d(states), dtype=FOLLOW_STATE_DTYPE, copy=True)
+    assert all(int(s) >= base for s in states["sample"])
+    states["sample"] -= np.uint64(base)
+    rec, count, out = follow(orc, tail, cfg, states, max_epochs)
+    for p in range(len(states)):
+        rec["sample"][p, :count[p]] += np.uint64(base)
+    out["sample"] += np.uint64(base)
+    return rec, count, out
+
+
 def follow_scalar(orc, stream, cfg, state, max_epochs):
     """one satellite, the contract sample by sample in Python integers -> (list of record tuples in FOLLOW_EPOCH_DTYPE's field order
     without `reserved`, final state as a dict)"""

@@ -137,6 +137,34 @@ def test_extreme_streams(ctx, orc, ss, top, kernel):
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("name", ["p100-int16", "p64-int8", "p16-int16"])
+def test_the_lowest_shift_on_a_tie(ctx, name, kernel):
+    """a periodic stream searched with carr_step0 = 0: in bin 0 the peak of either satellite is reached at 7, 5 and 16 shifts with
+    exactly equal power, a period apart, the first of them past shift 0 (tests/test_stage_contract_cases.py holds that structure on
+    the restatement); the peak reported is the lowest.  A reduction that keeps a later lane, tile or iteration fails here."""
+    import _contract_cases as cc
+    t, stream, ref = cc.tie_reference(name)
+    buf, ptr = to_device(stream, 4, 16)
+    got = search(ctx, kernel, ptr, len(stream) // 2, t.ss, t.prns, cc.TIE_STEPS, t.ndopp, t.nshift, t.ncoh, t.nnoncoh, t.hop)
+    assert [int(s) for s in got[0]["shift"][:, 0]] == [int(s) for s in ref[0]["shift"][:, 0]]
+    same(got, ref)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("ss", [SC08, SC16])
+def test_an_all_zero_stream(ctx, orc, ss, kernel):
+    """every power is 0.0 and every peak is at shift 0"""
+    nshift, ncoh, nn, hop, ndopp, prns = 300, 128, 2, 150, 2, (4, 21)
+    nsamp = ap.span_of(nshift, ncoh, nn, hop)
+    stream = np.zeros(2 * nsamp, dtype=elem_dtype(ss))
+    steps = ar.steps(2.6e6, 0.0, 500.0)
+    buf, ptr = to_device(stream, 8, 16)
+    got = search(ctx, kernel, ptr, nsamp, ss, prns, steps, ndopp, nshift, ncoh, nn, hop)
+    assert not got[0]["shift"].any() and got[0]["power"].tobytes() == bytes(8 * len(prns) * ndopp) and got[1].tobytes() == bytes(got[1].nbytes)
+    same(got, ar.acquire(orc, stream, prns, *steps, ndopp, nshift, ncoh, nn, hop))
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("ss,ncoh", [(SC16, 320), (SC08, 3072)])
 def test_a_coherent_stream_at_full_scale(ctx, orc, ss, ncoh, kernel):
     """code times carrier with every element at the extreme of the format that has the replica's sign: at shift 0 of the right
