@@ -446,6 +446,62 @@ int gpsiq_follow_gains(double fs, double fll_gain, double pll_bn_hz, double dll_
 int gpsiq_follow_bits(const gpsiq_follow_epoch_t *epochs, int nepochs, int skip,
                       int *offset, int8_t *bits, int max_bits, int *nbits);
 
+/* ---- Filter: a device FIR stage that band-limits and decimates -------------------------------------------------------------------
+ * The synthesiser samples rectangular chips at the output rate with unlimited bandwidth; a receiver behind a band-limited front end
+ * sees the stream low-passed and, usually, at a lower rate.  gpsiq_filter is that front end as integers: a causal FIR with int16 taps
+ * over ONE contiguous span, a decimator, a rounding shift and a symmetric clamp.  Integers only, like every other stage: a restatement
+ * in numpy agrees with the device byte for byte.
+ *
+ * Input span.  src is ONE contiguous span of nsamp complex samples, interleaved I,Q, int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16,
+ * elements as stored, base 4-byte aligned -- the span gpsiq_acquire and gpsiq_follow take.  x(m) is sample m of src for 0 <= m < nsamp.
+ * For -(ntaps-1) <= m < 0, x(m) is sample ntaps-1+m of head: ntaps-1 samples in the same format, 4-byte aligned; head == NULL means
+ * those samples are zeros.
+ * Output count.  Output j, 0 <= j < nout, sits at input index m_j = phase + j*decim.  nout = 0 if phase >= nsamp, otherwise
+ * nout = (nsamp - phase + decim - 1) / decim; next_phase = phase + nout*decim - nsamp (gpsiq_filter_span: host arithmetic, either
+ * result pointer may be NULL).
+ * Arithmetic.  For I and Q alike: acc = sum over k < ntaps of taps[k] * x(m_j - k), exact and causal.  y = acc at shift == 0,
+ * otherwise y = floor((acc + 2^(shift-1)) / 2^shift).  out = min(max(y, -qmax), qmax) with qmax 127 for an int8 dst and 32767 for an
+ * int16 dst: the clamp is symmetric, like the output level's.  *clipped is the number of elements the clamp changed.
+ * Ranges.  1 <= ntaps <= 512, 1 <= decim <= 16, 0 <= phase < decim, 0 <= shift <= 24, nsamp >= 0, both sample sizes GPSIQ_SC08 or
+ * GPSIQ_SC16 in any of the four combinations: anything else is GPSIQ_E_ARG.  sum |taps[k]| <= 65535, else GPSIQ_E_RANGE: with it
+ * |acc| < 2^31 for both input formats, so there is one accumulator width and no saturation rule inside the sum.
+ * Memory.  dst is device memory, 4-byte aligned, and receives exactly nout complex samples back to back; bytes past them are never
+ * written, bytes past 2*nsamp*sample_size of src never read.  dst must not overlap src or head (GPSIQ_E_ARG).  src, head and dst may
+ * also be page-locked memory of gpsiq_host_alloc, as for gpsiq_acquire.  taps is host memory.
+ * Stream order and return.  The taps cross to the device on hip_stream (a hipStream_t, NULL = the null stream) and the kernel is
+ * queued there: it runs behind the caller's gpsiq_launch on that stream.  The call then waits, fetches the count and returns:
+ * synchronous, like gpsiq_pack; taps may be overwritten once it has returned.  nsamp == 0 or nout == 0 launches nothing and returns
+ * GPSIQ_OK with a count of 0.  *nout (may be NULL) is the output count; kernel_ms (may be NULL) the kernel's device time.  The same
+ * call twice gives the same bytes.
+ * Continuation is part of the contract: filtering a span in pieces gives exactly the bytes and the clip count of one call over the
+ * whole span, when each piece is called with head set to the last ntaps-1 samples of the piece before (of the pieces before, where
+ * one is shorter than that) and phase set to that piece's next_phase.
+ *
+ * gpsiq_filter_design is a Hamming-windowed sinc low-pass: h[k] = 2fc/fs * sinc(2fc/fs * (k - (ntaps-1)/2)) * (0.54 - 0.46 cos(2 pi
+ * k/(ntaps-1))), normalised to sum 1, scaled by 2^shift and rounded with rint; the remainder that makes sum taps == 2^shift exactly is
+ * added to the centre tap.  ntaps odd, 3 <= ntaps <= 511, 0 < cutoff_hz < fs/2, 8 <= shift <= 14 (GPSIQ_E_ARG).  The result is symmetric
+ * with a DC gain of exactly 1 after the shift.  Double arithmetic: its properties are contract, its bits are not.
+ *
+ * gpsiq_generate_batch_filtered is gpsiq_generate_batch_packed's piece loop with the filter in the packer's place: a piece is rendered
+ * into device staging at sample_size, filtered on a side stream and its rows cross to HOST memory (pageable or page-locked) while
+ * the next piece renders.  It needs nsamp % decim == 0 (GPSIQ_E_ARG); output block b is nsamp/decim samples of out_sample_size at
+ * dst_host + b*dst_block_stride.  The first block's history is zeros, phase is 0 throughout, and the ntaps-1 samples of history
+ * cross from piece to piece inside the staging: the caller never sees them.  The result is byte for byte gpsiq_filter (head NULL,
+ * phase 0) of what ONE gpsiq_generate_batch over the whole timeline writes, in both NCO models, with noise and level; carrier
+ * continuation, the noise block counter and carr_phase_out are that call's.  ch is host memory only, as for the packed call.
+ * GPSIQ_FILTER_PIECE_BLOCKS=n in the environment, read per call, sets the blocks per piece (default: about 32 MiB of rendered
+ * stream); GPSIQ_FILTER_KERNEL=generic|mfma, read per call by both calls, forces a kernel where it can serve.  *clipped (may be NULL)
+ * is the sum over the pieces. */
+int gpsiq_filter(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head /* may be NULL */,
+                 const int16_t *taps /* host [ntaps] */, int ntaps, int shift, int decim, int phase,
+                 int out_sample_size, void *dst, void *hip_stream,
+                 int *nout /* may be NULL */, uint64_t *clipped /* may be NULL */, float *kernel_ms /* may be NULL */);
+int gpsiq_filter_span(int nsamp, int decim, int phase, int *nout, int *next_phase);          /* host arithmetic */
+int gpsiq_filter_design(double fs, double cutoff_hz, int ntaps, int shift, int16_t *taps);   /* host arithmetic */
+int gpsiq_generate_batch_filtered(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs,
+                                  int sample_size, const int16_t *taps, int ntaps, int shift, int decim, int out_sample_size,
+                                  void *dst_host, size_t dst_block_stride, uint64_t *clipped, double *carr_phase_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

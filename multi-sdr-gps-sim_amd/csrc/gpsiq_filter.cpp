@@ -1,0 +1,249 @@
+// gpsiq_filter.cpp -- host side of gpsiq_filter and gpsiq_generate_batch_filtered (include/gpsiq_rows.h, "Filter"): checks, plan
+// (gpsiq_filter_plan.h, pure and pinned on the CPU), the taps and the matrix kernel's digit planes on their way to the device, kernel
+// look-up (gpsiq_filter_kernels.hip holds the kernels and the table of those that exist), launch, count, and the batch call's pieces.
+// libgpsiq_rows.so exports the typed calls and reaches these through the plumbing entries "filter" and "generate_batch_filtered".
+// Host code: nothing here decides device code, so the file is not one of the device sources behind gpsiq_kernels_id().
+#include <cstdlib>
+#include <cstring>
+
+#include "gpsiq_ctx.h"
+#include "gpsiq_filter.h"
+#include "gpsiq_filter_plan.h"
+
+using namespace gpsiq;
+
+namespace {
+
+struct TapStats { long mag = 0; int max_tap = 0; };
+
+// what both calls ask of the filter itself
+int check_taps(const int16_t *taps, int ntaps, int shift, int decim, int sample_size, int out_sample_size, TapStats *st)
+{
+    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
+    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (ntaps < 1 || ntaps > kFiltMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kFiltMaxTaps);
+    if (decim < 1 || decim > kFiltMaxDecim) return fail(GPSIQ_E_ARG, "decim %d outside 1..%d", decim, kFiltMaxDecim);
+    if (shift < 0 || shift > kFiltMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kFiltMaxShift);
+    if (!taps) return fail(GPSIQ_E_ARG, "null taps");
+    st->max_tap = -32768;
+    for (int k = 0; k < ntaps; ++k) {
+        st->mag += taps[k] < 0 ? -(long) taps[k] : (long) taps[k];
+        if (taps[k] > st->max_tap) st->max_tap = taps[k];
+    }
+    if (st->mag > kFiltTapSum) return fail(GPSIQ_E_RANGE, "sum |taps| %ld above %ld: the accumulator would not hold the sum", st->mag, kFiltTapSum);
+    return GPSIQ_OK;
+}
+
+int forced_kernel()
+{
+    const char *env = std::getenv("GPSIQ_FILTER_KERNEL");
+    if (!env) return kFiltAuto;
+    return !std::strcmp(env, "generic") ? kFiltForceGeneric : !std::strcmp(env, "mfma") ? kFiltForceMfma : kFiltAuto;
+}
+
+void note_plan(gpsiq_ctx *c, const FilterPlan &p, long pieces)
+{
+    c->filt.last[0] = p.launch ? (long) p.kernel : -1; c->filt.last[1] = (long) p.grid; c->filt.last[2] = (long) p.run; c->filt.last[3] = pieces;
+}
+
+// The coefficients of a call, page-locked, then queued for the device on s: the taps as dwords, and behind them the two digit planes
+// of the matrix kernel in fragment order (gpsiq_filter_geometry.h) -- lane l = (row i = l & 15, group g = l >> 4) of k-step t holds
+// bytes j = 0..15, k = 64 t + 16 g + j, of A(i, k) = T[2 jj decim + c + 2 (ntaps - 1) - k], i = 2 jj + c, T the taps zero-stuffed.
+// The caller has made sure nothing queued earlier still reads h_coef (every call ends synchronised).
+int stage_coefficients(gpsiq_ctx *c, const int16_t *taps, int ntaps, int decim, const FilterPlan &p, hipStream_t s)
+{
+    FilterSet &k = c->filt;
+    int32_t *t32 = reinterpret_cast<int32_t *>(k.h_coef.get());
+    for (int i = 0; i < ntaps; ++i) t32[i] = taps[i];
+    size_t bytes = FilterSet::kTapBytes;
+    if (p.kernel == kFiltMfma) {
+        int8_t *pl = reinterpret_cast<int8_t *>(k.h_coef.get() + FilterSet::kTapBytes);
+        const size_t plane = (size_t) p.steps * kFiltK * 16;
+        std::memset(pl, 0, 2 * plane);
+        for (int i = 0; i < 16; ++i) {
+            const int jj = i >> 1, comp = i & 1;
+            for (int tap = 0; tap < ntaps; ++tap) {
+                const int kk = 2 * jj * decim + comp + 2 * (ntaps - 1) - 2 * tap;      // the k at which this row meets taps[tap]
+                const int t = kk / kFiltK, g = (kk % kFiltK) / 16, j = kk % 16;
+                const size_t at = ((size_t) t * 64 + (size_t) (16 * g + i)) * 16 + (size_t) j;
+                const int d0 = ((taps[tap] + 128) & 255) - 128, d1 = (taps[tap] - d0) / 256;
+                pl[at] = (int8_t) d0;
+                pl[plane + at] = (int8_t) d1;
+            }
+        }
+        bytes += 2 * plane;
+    }
+    HIP_TRY(hipMemcpyAsync(k.d_coef.get(), k.h_coef.get(), bytes, hipMemcpyHostToDevice, s));
+    return GPSIQ_OK;
+}
+
+// the filter queued on s behind its coefficients: the counter is NOT zeroed here (the batch call adds its pieces up)
+int queue_filter(gpsiq_ctx *c, const FilterPlan &p, int nsamp, int sample_size, const uint8_t *src, const uint8_t *head, int ntaps, int shift, int decim,
+                 int phase, int out_sample_size, uint8_t *dst, hipStream_t s)
+{
+    FilterSet &k = c->filt;
+    if (p.kernel == kFiltMfma) {
+        const FilterMfmaFn kernel = filter_mfma_kernel(out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no matrix filter kernel for %d-byte outputs", out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const uint8_t *) (k.d_coef.get() + FilterSet::kTapBytes), ntaps,
+                           shift, decim, phase, dst, p.nout, p.run, p.runs, p.steps, k.d_count.get());
+    } else {
+        const FilterGenericFn kernel = filter_generic_kernel(sample_size, out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no filter kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, reinterpret_cast<const int32_t *>(k.d_coef.get()), ntaps, shift,
+                           decim, phase, dst, p.nout, p.run, p.runs, k.d_count.get());
+    }
+    HIP_TRY(hipGetLastError());
+    return GPSIQ_OK;
+}
+
+bool overlap(const void *a, size_t alen, const void *b, size_t blen)
+{
+    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
+}
+
+}  // namespace
+
+int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, const void *head, const int16_t *taps, int ntaps, int shift, int decim,
+                      int phase, int out_sample_size, void *dst, void *hip_stream, int *nout, uint64_t *clipped, float *kernel_ms)
+{
+    if (!c) return fail(GPSIQ_E_ARG, "null context");
+    TapStats st;
+    if (int rc = check_taps(taps, ntaps, shift, decim, sample_size, out_sample_size, &st)) return rc;
+    if (phase < 0 || phase >= decim) return fail(GPSIQ_E_ARG, "phase %d outside [0, decim %d)", phase, decim);
+    if (nsamp < 0) return fail(GPSIQ_E_ARG, "negative size");
+    const FilterPlan p = plan_filter(nsamp, sample_size, ntaps, decim, phase, st.max_tap, forced_kernel());
+    if (!src && nsamp) return fail(GPSIQ_E_ARG, "null source");
+    if (!dst && p.nout) return fail(GPSIQ_E_ARG, "null destination");
+    if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
+    if ((uintptr_t) head & 3) return fail(GPSIQ_E_ARG, "head %p not 4-byte aligned", head);
+    if ((uintptr_t) dst & 3) return fail(GPSIQ_E_ARG, "destination %p not 4-byte aligned", dst);
+    const size_t src_len = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, head_len = head ? (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size : 0;
+    const size_t dst_len = (size_t) 2 * (size_t) p.nout * (size_t) out_sample_size;
+    if (overlap(dst, dst_len, src, src_len)) return fail(GPSIQ_E_ARG, "source [%p, +%zu) and destination [%p, +%zu) overlap", src, src_len, dst, dst_len);
+    if (overlap(dst, dst_len, head, head_len)) return fail(GPSIQ_E_ARG, "head [%p, +%zu) and destination [%p, +%zu) overlap", head, head_len, dst, dst_len);
+    if (nout) *nout = p.nout;
+    if (clipped) *clipped = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    note_plan(c, p, 0);
+    if (!p.launch) return GPSIQ_OK;                                   // no output: nothing to write
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t) hip_stream;
+    FilterSet &k = c->filt;
+    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = stage_coefficients(c, taps, ntaps, decim, p, s)) return rc;
+    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
+    HIP_TRY(hipEventRecord(k.t0.get(), s));
+    if (int rc = queue_filter(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), ntaps, shift, decim, phase,
+                              out_sample_size, static_cast<uint8_t *>(dst), s)) return rc;
+    HIP_TRY(hipEventRecord(k.t1.get(), s));
+    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (clipped) *clipped = (uint64_t) k.h_count[0];
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
+    return GPSIQ_OK;
+}
+
+// nothing of the call may still read the staging or write dst when it returns, on any path
+static int drain_filter(gpsiq_ctx *c, int rc)
+{
+    hipError_t e = hipStreamSynchronize(c->filt.filt_stream.get());
+    const hipError_t d = hipStreamSynchronize(c->filt.copy_stream.get());
+    if (e == hipSuccess) e = d;
+    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
+    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "filtered batch: %s", hipGetErrorString(e));
+}
+
+// Piece k: gpsiq_generate_batch renders its blocks back to back into d_render[k & 1] BEHIND a head region of `hb` bytes (synchronous),
+// the filter turns head region and piece into d_out[k & 1] on filt_stream, the rows cross to the host on copy_stream behind it --
+// while the calling thread is already in the render of piece k + 1, which uses the other pair.  The history crosses inside the
+// staging: behind the filter of piece k, on filt_stream, the last ntaps - 1 samples of [head region | piece k] are copied to the end
+// of the other pair's head region -- right for a piece shorter than the history too, whose own head region then supplies the rest;
+// the first piece's head region is zeros.  Piece k + 2 takes pair k & 1 again once `copied` of piece k has been reached, which lies
+// behind `filtered` of piece k and with it behind that copy.  Every piece is a whole number of blocks and nsamp a multiple of
+// decim: the phase is 0 at every piece, and a piece's outputs are its blocks' rows back to back.
+// The pieces are chained as gpsiq_generate_batch_packed chains them (gpsiq_pack.cpp).
+int gpsiq_generate_batch_filtered_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+                                       const int16_t *taps, int ntaps, int shift, int decim, int out_sample_size, void *dst, size_t dst_block_stride,
+                                       uint64_t *clipped, double *carr_phase_out)
+{
+    if (!c || (!ch && nblocks) || (!dst && nblocks && nsamp)) return fail(GPSIQ_E_ARG, "null argument");
+    TapStats st;
+    if (int rc = check_taps(taps, ntaps, shift, decim, sample_size, out_sample_size, &st)) return rc;
+    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
+    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (nsamp % decim) return fail(GPSIQ_E_ARG, "nsamp %d is not a multiple of decim %d", nsamp, decim);
+    const int nrow = nsamp / decim;                                   // outputs of a block
+    const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, row_bytes = (size_t) 2 * (size_t) nrow * (size_t) out_sample_size;
+    if (dst_block_stride < row_bytes) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
+    if (clipped) *clipped = 0;
+    if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
+    // the pieces' first rows are rewritten on the host: ch is host memory
+    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_filtered", nullptr)) return rc;
+    const char *env = std::getenv("GPSIQ_FILTER_PIECE_BLOCKS");
+    const int piece = filter_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
+    const int npieces = (nblocks + piece - 1) / piece;
+    const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
+    const int force = forced_kernel();
+    HIP_TRY(hipSetDevice(c->device));
+    FilterSet &k = c->filt;
+    if (int rc = k.reserve(hb + blk_bytes * (size_t) piece + 4, row_bytes * (size_t) piece + 4)) return rc;     // (+4: never a request of no bytes)
+    const FilterPlan whole = plan_filter(piece * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
+    note_plan(c, whole, npieces);
+    hipStream_t fs_ = k.filt_stream.get();
+    if (nsamp) {
+        // one kernel for every piece (the choice does not look at the length), so one set of coefficients, queued once
+        if (int rc = stage_coefficients(c, taps, ntaps, decim, whole, fs_)) return drain_filter(c, rc);
+        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), fs_));
+        if (hb) HIP_TRY(hipMemsetAsync(k.d_render[0].get(), 0, hb, fs_));            // the first block's history
+    }
+    double carr[GPSIQ_MAX_CHAN] = {};
+    int rc = GPSIQ_OK;
+    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
+        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, pair = p & 1;
+        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
+        if (p > 0) {
+            k.row.assign(rows, rows + (size_t) nb * nchan);
+            for (int i = 0; i < nchan; ++i)
+                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
+            rows = k.row.data();
+        }
+        if (p >= 2) {                                                 // the pair's last user: piece p - 2
+            const hipError_t e = hipEventSynchronize(k.copied[pair].get());
+            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "filtered batch: %s", hipGetErrorString(e)); break; }
+        }
+        uint8_t *span = k.d_render[pair].get() + hb;
+        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, sample_size, span, 1, carr);
+        if (rc != GPSIQ_OK) break;
+        if (nsamp == 0) continue;
+        const FilterPlan pl = plan_filter(nb * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
+        rc = queue_filter(c, pl, nb * nsamp, sample_size, span, hist ? span - hist : nullptr, ntaps, shift, decim, 0, out_sample_size, k.d_out[pair].get(), fs_);
+        if (rc != GPSIQ_OK) break;
+        hipError_t e = hipSuccess;
+        if (hist && p + 1 < npieces)                                  // the next piece's history
+            e = hipMemcpyAsync(k.d_render[pair ^ 1].get() + hb - hist, span + blk_bytes * (size_t) nb - hist, hist, hipMemcpyDeviceToDevice, fs_);
+        if (e == hipSuccess) e = hipEventRecord(k.filtered[pair].get(), fs_);
+        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.filtered[pair].get(), 0);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * dst_block_stride, dst_block_stride, k.d_out[pair].get(),
+                                                  row_bytes, row_bytes, (size_t) nb, hipMemcpyDeviceToHost, k.copy_stream.get());
+        if (e == hipSuccess) e = hipEventRecord(k.copied[pair].get(), k.copy_stream.get());
+        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "filtered batch piece: %s", hipGetErrorString(e));
+    }
+    if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last filter
+        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, fs_);
+        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "filtered batch count: %s", hipGetErrorString(e));
+    }
+    rc = drain_filter(c, rc);
+    if (rc != GPSIQ_OK) return rc;
+    if (clipped && nsamp) *clipped = (uint64_t) k.h_count[0];
+    if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
+    return GPSIQ_OK;
+}
+
+extern "C" int gpsiq_filter_last_plan(const gpsiq_ctx_t *c, long out[4])
+{
+    if (!c || !out) return fail(GPSIQ_E_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = c->filt.last[i];
+    return GPSIQ_OK;
+}

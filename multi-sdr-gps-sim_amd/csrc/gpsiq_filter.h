@@ -1,0 +1,67 @@
+// gpsiq_filter.h -- what the device context holds for gpsiq_filter / gpsiq_generate_batch_filtered (include/gpsiq_rows.h, "Filter") and
+// what their host side (gpsiq_filter.cpp) and their kernels (gpsiq_filter_kernels.hip, with gpsiq_filter_geometry.h) use of each
+// other.  The plan is in gpsiq_filter_plan.h.  Host code; gpsiq_ctx.h includes this header for the context's member `filt`.
+#ifndef GPSIQ_FILTER_H
+#define GPSIQ_FILTER_H
+
+#include <vector>
+
+#include "gpsiq_internal.h"
+#include "gpsiq_own.h"
+#include "gpsiq_filter_geometry.h"
+
+namespace gpsiq {
+
+// the coefficients of a call on the device and page-locked on their way there (the taps as dwords, then the matrix kernel's digit
+// planes: one size, the largest a call can ask for), the counter of clamped elements and its page-locked twin, the two events a kernel
+// is timed with, and what the batch call works through its pieces with -- two rendered and two filtered staging buffers taken in
+// turn, a stream for the filter, one for the copies, and per buffer pair the events "filtered" and "copied"
+struct FilterSet {
+    static constexpr size_t kTapBytes = 4 * (size_t) kFiltMaxTaps;
+    static constexpr size_t kCoefBytes = kTapBytes + (size_t) filter_mfma_plane_bytes(kFiltMaxSteps);
+    DevBuf<uint8_t>               d_coef;    PinnedBuf<uint8_t>            h_coef;        // [kCoefBytes]
+    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
+    DevBuf<uint8_t>               d_render[2], d_out[2];                                  // bytes
+    Stream         filt_stream, copy_stream;
+    Event          t0, t1, filtered[2], copied[2];
+    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    long           last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, outputs per run, pieces (gpsiq_filter_last_plan)
+    int reserve(size_t render_bytes, size_t out_bytes);         // first use + room for one call (0, 0: gpsiq_filter)
+};
+
+// (coefficients, counter, events and streams on first use; the staging pairs grow together, rendered side first)
+inline int FilterSet::reserve(size_t render_bytes, size_t out_bytes)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(reserve_together(kCoefBytes, kCoefBytes, d_coef, h_coef));
+    HIP_TRY(d_count.reserve(1));
+    HIP_TRY(h_count.reserve(1));
+    if (!render_bytes && !out_bytes) return GPSIQ_OK;
+    HIP_TRY(filt_stream.ensure());
+    HIP_TRY(copy_stream.ensure());
+    for (auto &e : filtered) HIP_TRY(e.ensure());
+    for (auto &e : copied) HIP_TRY(e.ensure());
+    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
+    HIP_TRY(reserve_together(out_bytes, out_bytes + out_bytes / 4 + 256, d_out[0], d_out[1]));
+    return GPSIQ_OK;
+}
+
+// the filter kernels (gpsiq_filter_kernels.hip).  Arguments: span and its samples, head, the taps as dwords (generic) or the digit
+// planes (matrix), ntaps, shift, decim, phase, destination, outputs of the span, outputs of a run, runs of the launch
+// (gpsiq_filter_plan.h); matrix kernel: the k-steps of a tile; the counter of clamped elements
+using FilterGenericFn = void (*)(const uint8_t *, int, const uint8_t *, const int32_t *, int, int, int, int, uint8_t *, int, int, uint64_t,
+                                 unsigned long long *);
+using FilterMfmaFn    = void (*)(const uint8_t *, int, const uint8_t *, const uint8_t *, int, int, int, int, uint8_t *, int, int, uint64_t, int,
+                                 unsigned long long *);
+FilterGenericFn filter_generic_kernel(int in_fmt, int out_fmt);
+FilterMfmaFn    filter_mfma_kernel(int out_fmt);
+
+}  // namespace gpsiq
+
+// gpsiq_filter.cpp: gpsiq_filter and gpsiq_generate_batch_filtered themselves, behind the plumbing entries "filter" and
+// "generate_batch_filtered".  Declared from the public prototypes, and hidden: a definition that has drifted from
+// include/gpsiq_rows.h is another function, and the library no longer links
+__attribute__((visibility("hidden"))) decltype(gpsiq_filter) gpsiq_filter_impl;
+__attribute__((visibility("hidden"))) decltype(gpsiq_generate_batch_filtered) gpsiq_generate_batch_filtered_impl;
+#endif

@@ -30,7 +30,8 @@ void *gpsiq_plumbing(const char *name);
  * "pack", "unpack" and "generate_batch_packed" are gpsiq_pack, gpsiq_unpack and gpsiq_generate_batch_packed (ibid., "Packed streams";
  * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements.
  * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise, and "follow" is gpsiq_follow (ibid., "Follow";
- * csrc/gpsiq_follow.cpp). */
+ * csrc/gpsiq_follow.cpp).  "filter" and "generate_batch_filtered" are gpsiq_filter and gpsiq_generate_batch_filtered (ibid., "Filter";
+ * csrc/gpsiq_filter.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -201,6 +202,10 @@ int gpsiq_acquire_last_plan(const gpsiq_ctx_t *ctx, long long out[4], float ms[2
 /* What the context's last gpsiq_follow took (csrc/gpsiq_follow_plan.h): out[0] the workgroups of a launch (-1: no call yet, or one that
  * failed), out[1] the epochs a launch does per satellite at most, out[2] the launches, out[3] the bytes of records on the device. */
 int gpsiq_follow_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
+/* What the context's last gpsiq_filter / gpsiq_generate_batch_filtered took (csrc/gpsiq_filter_plan.h): out[0] the kernel (0 generic, 1 mfma;
+ * -1: nothing was launched, or no call yet), out[1] the grid, out[2] the outputs of a workgroup's run, out[3] the pieces of a batch call
+ * (0: not one; a batch call reports the plan of a full piece). */
+int gpsiq_filter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
 
 #ifdef __cplusplus
 }

@@ -123,3 +123,22 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_follow(gpsiq_ctx_t *
     static const auto f = gpsiq::core<decltype(&gpsiq_follow)>("follow");
     return f(ctx, nsamp, sample_size, src, hip_stream, cfg, state, nprn, epochs, max_epochs, nepochs, kernel_ms);
 }
+
+// The filter runs on the context's device (csrc/gpsiq_filter.cpp) and is exported here like the packer (include/gpsiq_rows.h, "Filter");
+// gpsiq_filter_span and gpsiq_filter_design, plain arithmetic, are in gpsiq_stage_math.cpp beside gpsiq_follow_gains.
+extern "C" __attribute__((visibility("default"))) int gpsiq_filter(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head,
+                                                                   const int16_t *taps, int ntaps, int shift, int decim, int phase, int out_sample_size,
+                                                                   void *dst, void *hip_stream, int *nout, uint64_t *clipped, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_filter)>("filter");
+    return f(ctx, nsamp, sample_size, src, head, taps, ntaps, shift, decim, phase, out_sample_size, dst, hip_stream, nout, clipped, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_filtered(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan,
+                                                                                    int nsamp, double fs, int sample_size, const int16_t *taps, int ntaps,
+                                                                                    int shift, int decim, int out_sample_size, void *dst_host,
+                                                                                    size_t dst_block_stride, uint64_t *clipped, double *carr_phase_out)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_filtered)>("generate_batch_filtered");
+    return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, taps, ntaps, shift, decim, out_sample_size, dst_host, dst_block_stride, clipped, carr_phase_out);
+}

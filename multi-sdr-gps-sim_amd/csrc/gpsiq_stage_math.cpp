@@ -1,8 +1,10 @@
 // gpsiq_stage_math.cpp -- the plain arithmetic that goes with the noise, the output level and the stream stages (include/gpsiq_rows.h):
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
-// C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow.  Host code of
-// libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves: gpsiq_rows_link.cpp).
+// C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
+// and the taps of a filter.  Host code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves:
+// gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
+#include "gpsiq_filter_plan.h"
 
 #include <cmath>
 
@@ -147,6 +149,47 @@ int gpsiq_follow_bits(const gpsiq_follow_epoch_t *epochs, int nepochs, int skip,
     }
     *offset = best;
     *nbits = (int) groups;
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Filter": the outputs of a span and the phase its continuation starts at (filter_span, gpsiq_filter_plan.h)
+int gpsiq_filter_span(int nsamp, int decim, int phase, int *nout, int *next_phase)
+{
+    if (nsamp < 0 || decim < 1 || decim > kFiltMaxDecim || phase < 0 || phase >= decim)
+        return fail(GPSIQ_E_ARG, "nsamp %d >= 0, decim %d in 1..%d, phase %d in [0, decim)", nsamp, decim, kFiltMaxDecim, phase);
+    int n = 0, next = 0;
+    filter_span(nsamp, decim, phase, &n, &next);
+    if (nout) *nout = n;
+    if (next_phase) *next_phase = next;
+    return GPSIQ_OK;
+}
+
+// ibid.: a Hamming-windowed sinc low-pass as integers with a DC gain of exactly 2^shift.  Window and sinc are even about the centre
+// and are evaluated at k and at ntaps - 1 - k from the same distance, so the taps are symmetric to the bit
+int gpsiq_filter_design(double fs, double cutoff_hz, int ntaps, int shift, int16_t *taps)
+{
+    if (!taps) return fail(GPSIQ_E_ARG, "null argument");
+    if (ntaps < 3 || ntaps > kFiltMaxTaps - 1 || !(ntaps & 1)) return fail(GPSIQ_E_ARG, "ntaps %d: odd, 3..%d", ntaps, kFiltMaxTaps - 1);
+    if (shift < 8 || shift > 14) return fail(GPSIQ_E_ARG, "shift %d: 8..14", shift);
+    if (!(fs > 0.0) || !std::isfinite(fs) || !(cutoff_hz > 0.0) || !(cutoff_hz < fs / 2.0))
+        return fail(GPSIQ_E_ARG, "cutoff %g Hz outside (0, fs / 2) at fs %g", cutoff_hz, fs);
+    const double pi = 3.14159265358979323846, w = 2.0 * cutoff_hz / fs;
+    const int mid = (ntaps - 1) / 2;
+    double h[kFiltMaxTaps], sum = 0.0;
+    for (int d = 0; d <= mid; ++d) {                                   // distance from the centre
+        const double x = w * (double) d, sinc = d ? std::sin(pi * x) / (pi * x) : 1.0;
+        const double win = 0.54 - 0.46 * std::cos(2.0 * pi * (double) (mid - d) / (double) (ntaps - 1));
+        h[mid - d] = h[mid + d] = w * sinc * win;
+        sum += d ? 2.0 * h[mid + d] : h[mid];
+    }
+    const double scale = std::ldexp(1.0, shift) / sum;
+    long total = 0, mag = 0;
+    long q[kFiltMaxTaps];
+    for (int k = 0; k < ntaps; ++k) { q[k] = std::lrint(h[k] * scale); total += q[k]; }
+    q[mid] += (1L << shift) - total;                                   // the remainder of the rounding, to the centre tap
+    for (int k = 0; k < ntaps; ++k) mag += q[k] < 0 ? -q[k] : q[k];
+    if (mag > kFiltTapSum || q[mid] > 32767 || q[mid] < -32768) return fail(GPSIQ_E_RANGE, "taps outside the filter's range (sum |taps| %ld)", mag);
+    for (int k = 0; k < ntaps; ++k) taps[k] = (int16_t) q[k];
     return GPSIQ_OK;
 }
 

@@ -168,6 +168,11 @@ _follow = _sig("gpsiq_follow", _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i,
 _follow_last_plan = _sig("gpsiq_follow_last_plan", _i, _vp, _vp)
 _follow_gains = _sig("gpsiq_follow_gains", _i, _d, _d, _d, _d, _vp)
 _follow_bits = _sig("gpsiq_follow_bits", _i, _vp, _i, _i, C.POINTER(_i), _vp, _i, C.POINTER(_i))
+_filter = _sig("gpsiq_filter", _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_filter_span = _sig("gpsiq_filter_span", _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i))
+_filter_design = _sig("gpsiq_filter_design", _i, _d, _d, _i, _i, _vp)
+_generate_batch_filtered = _sig("gpsiq_generate_batch_filtered", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(C.c_uint64), _vp)
+_filter_last_plan = _sig("gpsiq_filter_last_plan", _i, _vp, _vp)
 
 
 class NoiseSettings(C.Structure):
@@ -695,6 +700,22 @@ def follow_bits(epochs, skip=0):
     return off.value, bits[:nb.value].copy()
 
 
+def filter_span(nsamp, decim, phase=0):
+    """gpsiq_filter_span: (outputs of a span of nsamp samples decimated by decim from input index phase, the phase its continuation
+    starts at)."""
+    nout, nxt = _i(0), _i(0)
+    _check(_filter_span(int(nsamp), int(decim), int(phase), C.byref(nout), C.byref(nxt)))
+    return nout.value, nxt.value
+
+
+def filter_design(fs, cutoff_hz, ntaps, shift=14):
+    """gpsiq_filter_design: int16 taps [ntaps] of a Hamming-windowed sinc low-pass with its -6 dB point at cutoff_hz, symmetric, their
+    sum exactly 2**shift."""
+    taps = np.zeros(max(int(ntaps), 1), dtype=np.int16)
+    _check(_filter_design(float(fs), float(cutoff_hz), int(ntaps), int(shift), _p(taps)))
+    return taps
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -963,6 +984,43 @@ class Context:
         out = (C.c_longlong * 4)()
         _check(_follow_last_plan(self._h, out))
         return (None if out[0] < 0 else int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def filter(self, nsamp, sample_size, device_ptr, taps, shift, decim, phase, out_sample_size, dst_device_ptr, head_ptr=None, stream=None):
+        """gpsiq_filter: the nsamp complex samples at device_ptr through the FIR `taps` (int16, host), rounded by `shift`, decimated by
+        `decim` from input index `phase`, clamped into out_sample_size at dst_device_ptr; head_ptr: the ntaps - 1 samples before the span
+        (None: zeros) -> (outputs written, elements the clamp changed, kernel milliseconds)."""
+        taps = np.ascontiguousarray(taps, dtype=np.int16).ravel()
+        nout, clipped, ms = _i(0), C.c_uint64(0), C.c_float(0.0)
+        _check(_filter(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(head_ptr or 0), _p(taps) if len(taps) else None, len(taps), int(shift),
+                       int(decim), int(phase), int(out_sample_size), _vp(dst_device_ptr), _vp(stream or 0), C.byref(nout), C.byref(clipped), C.byref(ms)))
+        return nout.value, int(clipped.value), float(ms.value)
+
+    def generate_batch_filtered(self, desc, nsamp, fs, sample_size, taps, shift, decim, out_sample_size, host_ptr=None, block_stride=None,
+                                carr_out=None):
+        """gpsiq_generate_batch_filtered: the run-ahead call rendered at sample_size, filtered and decimated on the device, with blocks
+        of nsamp / decim samples of out_sample_size in host memory.  Returns (int8 / int16 [nblocks][2 * nsamp / decim], elements the
+        clamp changed), the array None when host_ptr names the caller's buffer (pageable or page-locked; block_stride bytes between
+        blocks, default: back to back)."""
+        desc = np.ascontiguousarray(desc, dtype=CHAN_DTYPE)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).ravel()
+        nb, nc = desc.shape
+        rlen = 2 * (int(nsamp) // max(int(decim), 1)) * int(out_sample_size)
+        stride = rlen if block_stride is None else int(block_stride)
+        co = None if carr_out is None else _p(carr_out)
+        clipped = C.c_uint64(0)
+        out = None if host_ptr is not None else np.zeros((nb, stride), dtype=np.uint8)
+        _check(_generate_batch_filtered(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(sample_size), _p(taps) if len(taps) else None, len(taps),
+                                        int(shift), int(decim), int(out_sample_size), _vp(host_ptr) if out is None else _p(out), stride,
+                                        C.byref(clipped), co))
+        if out is None:
+            return None, int(clipped.value)
+        return np.ascontiguousarray(out[:, :rlen]).view(np.int8 if int(out_sample_size) == 1 else np.int16), int(clipped.value)
+
+    def filter_last_plan(self):
+        """What the last filter() / generate_batch_filtered() took: (kernel name or None, grid, outputs of a workgroup's run, pieces)."""
+        out = (C.c_long * 4)()
+        _check(_filter_last_plan(self._h, out))
+        return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def pack_last_plan(self):
         """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""

@@ -15,6 +15,7 @@
  *
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
  *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
+ *                  [--filter cutoff_hz [--taps n] [--decim d]]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -52,6 +53,11 @@
  * stopped at, the mean prompt amplitude per sample from epoch 250 on, the bits gpsiq_follow_bits reads from there, the epochs and the
  * status.  The span is followed where it lies, like the searched block; it must lie inside the run's first call to the library (the blocks
  * up to the first 30 s boundary, 100 at the most).
+ * Filter (optional, same place): --filter <cutoff Hz> renders at <fs> and writes the stream low-passed and decimated, at <fs>/d in the
+ * run's own sample size, through gpsiq_generate_batch_filtered (include/gpsiq_rows.h, "Filter") with the taps of
+ * gpsiq_filter_design(fs, cutoff, n, 14): --taps <n> (odd, 3..511, default 65), --decim <d> (1..16, default 1; the block length must be
+ * a multiple of it).  The cutoff lies in (0, fs/2).  Every call to the library starts from a history of zeros.  The elements the
+ * filter's clamp changed are counted and printed.  Not with --pack, --acquire or --follow.
  */
 #include <math.h>
 #include <stdint.h>
@@ -236,15 +242,21 @@ int main(int argc, char **argv)
     int acquire = 0;
     double follow_s = NAN;
     int follow = 0;
+    double filter_hz = NAN;
+    int filter = 0, ftaps = 65, fdecim = 1, fopts = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
-                        strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0))) break;
+                        strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0 ||
+                        strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--follow") == 0) { follow_s = atof(argv[argc - 1]); follow = 1; }
         else if (strcmp(argv[argc - 2], "--qmax") == 0) qmax = atoi(argv[argc - 1]);
+        else if (strcmp(argv[argc - 2], "--filter") == 0) { filter_hz = atof(argv[argc - 1]); filter = 1; }
+        else if (strcmp(argv[argc - 2], "--taps") == 0) { ftaps = atoi(argv[argc - 1]); fopts = 1; }
+        else if (strcmp(argv[argc - 2], "--decim") == 0) { fdecim = atoi(argv[argc - 1]); fopts = 1; }
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
@@ -257,11 +269,18 @@ int main(int argc, char **argv)
                                         (argc >= 10 && atoi(argv[9]) != 1));
     /* --follow: with --acquire, a positive time of 10 s at the most (a call renders 100 blocks) */
     const int follow_bad = follow && (!acquire || !(follow_s > 0.0) || !(follow_s <= 0.1 * BLOCKS_PER_CALL));
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]\n"
+    /* --filter: a cutoff inside (0, fs/2), odd taps 3..511, a decimation 1..16 that divides the block length; on its own */
+    const double fs_arg = argc >= 9 ? atof(argv[8]) : 0.0;
+    const int filter_bad = (fopts && !filter) ||
+                           (filter && (pack_given || acquire || follow || !(filter_hz > 0.0) || !(filter_hz < fs_arg / 2.0) || ftaps < 3 || ftaps > 511 ||
+                                       !(ftaps & 1) || fdecim < 1 || fdecim > 16 || (int) floor(fs_arg / 10.0 + 0.5) % fdecim != 0));
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]]\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
                         "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
-                        "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n", argv[0]);
+                        "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n"
+                        "       --filter needs a cutoff in (0, fs/2), odd --taps 3..511 (default 65), --decim 1..16 (default 1) dividing the block length;\n"
+                        "                not with --pack, --acquire or --follow\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -336,7 +355,10 @@ int main(int argc, char **argv)
     if (!isnan(level_rms) && !(level_rms > 0.0)) { fprintf(stderr, "bad --level\n"); return 2; }
     if (qmax && isnan(level_rms)) { fprintf(stderr, "--qmax needs --level\n"); return 2; }
     int level_set = isnan(level_rms);                                          /* nothing to set without --level */
-    const size_t blk_bytes = pack ? gpsiq_packed_block_bytes(nsamp, pack) : (size_t) 2 * (size_t) nsamp * (size_t) ss;      /* as written */
+    const size_t blk_bytes = pack ? gpsiq_packed_block_bytes(nsamp, pack) : (size_t) 2 * (size_t) (nsamp / fdecim) * (size_t) ss;      /* as written */
+    static int16_t taps[511];
+    uint64_t filter_clipped = 0;
+    if (filter && gpsiq_filter_design(fs, filter_hz, ftaps, 14, taps) != GPSIQ_OK) return die("filter design");
     void *buf = gpsiq_host_alloc(blk_bytes * BLOCKS_PER_CALL);
     gpsiq_chan_t *desc = malloc(sizeof *desc * BLOCKS_PER_CALL * (size_t) nchan);
     FILE *fo = fopen(argv[10], "wb");
@@ -372,6 +394,11 @@ int main(int argc, char **argv)
             }
             if (pack) {
                 if (gpsiq_generate_batch_packed(gq, desc, nb, nchan, nsamp, fs, pack, buf, blk_bytes, carr) != GPSIQ_OK) return die("generate packed");
+            } else if (filter) {
+                uint64_t clipped = 0;
+                if (gpsiq_generate_batch_filtered(gq, desc, nb, nchan, nsamp, fs, ss, taps, ftaps, 14, fdecim, ss, buf, blk_bytes, &clipped, carr) != GPSIQ_OK)
+                    return die("generate filtered");
+                filter_clipped += clipped;
             } else if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
             if (acquire && done == 0 && b == 0) {
@@ -410,6 +437,7 @@ int main(int argc, char **argv)
     }
     fclose(fo);
     printf("%d blocks, %d channels, %d allocation passes, last nsat %d, ephemeris set %d of %d\n", nblocks, nchan, nalloc, nsat, h.ieph, nsets);
+    if (filter) printf("filter: cutoff %g Hz, %d taps, decimation %d, %llu elements clipped\n", filter_hz, ftaps, fdecim, (unsigned long long) filter_clipped);
     gpsiq_host_free(buf);
     gpsiq_destroy(gq);
     free(desc); free(xyz);

@@ -146,7 +146,8 @@ def kernel_hashes(lib, pattern):
             dem = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
             for n, d in zip(names, dem):
                 if re.search(pattern, d):
-                    out[d.split("(")[0]] = (hashlib.sha256("\n".join(funcs[n]).encode()).hexdigest()[:16], len(funcs[n]))
+                    # (a kernel in an anonymous namespace keeps its name: the first "(" of it is not its parameter list's)
+                    out[d.replace("(anonymous namespace)", "{anonymous}").split("(")[0]] =(hashlib.sha256("\n".join(funcs[n]).encode()).hexdigest()[:16], len(funcs[n]))
     return out
 
 
