@@ -502,6 +502,53 @@ int gpsiq_generate_batch_filtered(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int 
                                   int sample_size, const int16_t *taps, int ntaps, int shift, int decim, int out_sample_size,
                                   void *dst_host, size_t dst_block_stride, uint64_t *clipped, double *carr_phase_out);
 
+/* ---- Spectrum: the exact integer power spectrum of a device stream ------------------------------------------------------------------
+ * The instrument that looks at a stream in the frequency domain: a Welch-style averaged periodogram of ONE span, a dense DFT over the
+ * library's own carrier table, in integers end to end, so that a restatement in numpy agrees with the device bit for bit.
+ *
+ * Input.  src is ONE contiguous span of nsamp complex samples, interleaved I,Q, int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16, elements
+ * as stored, base 4-byte aligned and no more, in device memory or page-locked memory of gpsiq_host_alloc -- the span gpsiq_acquire,
+ * gpsiq_follow and gpsiq_filter take.  No resident descriptors and no NCO mode are needed.
+ * Segments.  N = nfft.  Segment q starts at sample q*hop; nseg = nsamp < N ? 0 : (nsamp - N)/hop + 1; ngroups = nseg / navg; group g is
+ * segments g*navg .. g*navg + navg - 1.  Segments past the last whole group are not part of the result, and samples at or past
+ * (ngroups*navg - 1)*hop + N are never read.  (gpsiq_spectrum_span: host arithmetic, either result pointer may be NULL.)
+ * Arithmetic.  Everything is an exact integer.  c(i), s(i) are cosTable512[i & 511], sinTable512[i & 511], the unit table of
+ * gpsiq_despread (amplitude 250; gpsiq_carrier_table of the plumbing reads it back), and T = 512 / N.  For segment q and bin k in
+ * [0, N), with m = q*hop + n and idx = (k*n*T) mod 512:
+ *     Xi[k] = sum over n < N of I(m)*c(idx) + Q(m)*s(idx)        Xq[k] = sum over n < N of Q(m)*c(idx) - I(m)*s(idx)
+ * gpsiq_despread's formulas and signs: a tone turning at +k0*fs/N peaks in bin k0.  Window: GPSIQ_WINDOW_RECT is Y = X;
+ * GPSIQ_WINDOW_HANN is Y[k] = 2*X[k] - X[(k-1) mod N] - X[(k+1) mod N], i and q separately: the Hann window applied across bins,
+ * scaled by 4, exact because it is the definition.  Y' = Y >> shift on each component, an arithmetic shift that floors (Y' = Y at
+ * shift 0).  power[g][k] = sum over the group's segments of Yi'^2 + Yq'^2, exact in uint64.  The sum does not depend on its order:
+ * the device accumulates as it likes and the same call twice gives the same bytes.
+ * Bound.  The sum can never wrap: with xmax 128 for int8 and 32768 for int16, W 1 for the rectangular window and 4 for Hann,
+ * Ymax = W*N*500*xmax (|I c + Q s| <= 250 (|I| + |Q|)), Ys = Ymax at shift 0 and (Ymax >> shift) + 1 otherwise, a call needs
+ * 2*navg*Ys^2 <= 2^64 - 1 (128-bit host arithmetic), else GPSIQ_E_RANGE.  gpsiq_spectrum_min_shift returns the smallest shift in
+ * 0..40 that satisfies it (GPSIQ_E_RANGE if none does, GPSIQ_E_ARG for a bad argument): int8, N 512, Hann has Ymax = 2^17 * 1000 and
+ * takes shift 0 up to navg 536 and shift 1 from 537.
+ * Ranges.  nfft in {64, 128, 256, 512}; hop nfft/2 or nfft; window GPSIQ_WINDOW_RECT or GPSIQ_WINDOW_HANN; navg >= 1; 0 <= shift <= 40;
+ * nsamp >= 0; sample_size GPSIQ_SC08 or GPSIQ_SC16; src not NULL and 4-byte aligned; power not NULL: anything else is GPSIQ_E_ARG.
+ * With ngroups == 0 the call launches nothing, writes nothing to power and returns GPSIQ_OK with *ngroups = 0.
+ * Stream order and return.  The kernels are queued on hip_stream (a hipStream_t, NULL = the null stream) behind the caller's work
+ * there; the call then waits, copies power [ngroups][nfft] to the host and returns: synchronous, like gpsiq_acquire.  *ngroups (may be
+ * NULL) is the group count, kernel_ms (may be NULL) the kernels' device time.  GPSIQ_SPECTRUM_KERNEL=generic|mfma in the environment,
+ * read per call, forces a kernel where it can serve (the matrix kernel: int8 input); the bytes do not depend on it.
+ *
+ * gpsiq_spectrum_scale gives the factor that turns a cell of power into stream units squared per Hz, two-sided and complex:
+ * 4^shift / (navg * 250^2 * G * N * fs), G = 1 for the rectangular window and 6 for Hann (as defined above w(n) = 2 - 2 cos(2 pi n/N)
+ * and sum w^2 = 6N).  White noise of variance sigma^2 per component then reads 2 sigma^2 / fs in every bin.  Double arithmetic: its
+ * value is contract to a relative 1e-12, its bits are not.  The table is a half-sample-offset sine, so every twiddle carries the same
+ * rotation by pi/512, which drops out of the power; it is rounded, which puts a floor under the bins beside a strong one
+ * (DESIGN.md 8h). */
+#define GPSIQ_WINDOW_RECT 0
+#define GPSIQ_WINDOW_HANN 1
+int gpsiq_spectrum(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                   int nfft, int hop, int window, int navg, int shift,
+                   uint64_t *power /* host [ngroups][nfft] */, int *ngroups /* may be NULL */, float *kernel_ms /* may be NULL */);
+int gpsiq_spectrum_span(int nsamp, int nfft, int hop, int navg, int *nseg, int *ngroups);   /* host arithmetic */
+int gpsiq_spectrum_min_shift(int sample_size, int nfft, int window, int navg);              /* host arithmetic: the shift, or a negative error */
+int gpsiq_spectrum_scale(int nfft, int window, int navg, int shift, double fs, double *scale); /* host arithmetic */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -31,7 +31,7 @@ void *gpsiq_plumbing(const char *name);
  * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements.
  * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise, and "follow" is gpsiq_follow (ibid., "Follow";
  * csrc/gpsiq_follow.cpp).  "filter" and "generate_batch_filtered" are gpsiq_filter and gpsiq_generate_batch_filtered (ibid., "Filter";
- * csrc/gpsiq_filter.cpp). */
+ * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -206,6 +206,10 @@ int gpsiq_follow_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
  * -1: nothing was launched, or no call yet), out[1] the grid, out[2] the outputs of a workgroup's run, out[3] the pieces of a batch call
  * (0: not one; a batch call reports the plan of a full piece). */
 int gpsiq_filter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
+/* What the context's last gpsiq_spectrum took (csrc/gpsiq_spectrum_plan.h): out[0] the kernel (0 generic, 1 mfma; -1: nothing was
+ * launched, no call yet, or one that failed), out[1] the grid, out[2] the segments of a unit (generic) or of a pass (matrix kernel),
+ * out[3] the groups of the result. */
+int gpsiq_spectrum_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
 
 #ifdef __cplusplus
 }

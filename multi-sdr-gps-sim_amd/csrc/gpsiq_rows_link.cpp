@@ -142,3 +142,13 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_filte
     static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_filtered)>("generate_batch_filtered");
     return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, taps, ntaps, shift, decim, out_sample_size, dst_host, dst_block_stride, clipped, carr_phase_out);
 }
+
+// The spectrum runs on the context's device (csrc/gpsiq_spectrum.cpp) and is exported here like the filter (include/gpsiq_rows.h,
+// "Spectrum"); gpsiq_spectrum_span, gpsiq_spectrum_min_shift and gpsiq_spectrum_scale, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_spectrum(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, void *hip_stream,
+                                                                     int nfft, int hop, int window, int navg, int shift, uint64_t *power, int *ngroups,
+                                                                     float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_spectrum)>("spectrum");
+    return f(ctx, nsamp, sample_size, src, hip_stream, nfft, hop, window, navg, shift, power, ngroups, kernel_ms);
+}

@@ -1,10 +1,11 @@
 // gpsiq_stage_math.cpp -- the plain arithmetic that goes with the noise, the output level and the stream stages (include/gpsiq_rows.h):
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
-// and the taps of a filter.  Host code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves:
+// and the taps of a filter, the segments, the shift and the scale of a spectrum.  Host code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves:
 // gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
+#include "gpsiq_spectrum_plan.h"
 
 #include <cmath>
 
@@ -190,6 +191,37 @@ int gpsiq_filter_design(double fs, double cutoff_hz, int ntaps, int shift, int16
     for (int k = 0; k < ntaps; ++k) mag += q[k] < 0 ? -q[k] : q[k];
     if (mag > kFiltTapSum || q[mid] > 32767 || q[mid] < -32768) return fail(GPSIQ_E_RANGE, "taps outside the filter's range (sum |taps| %ld)", mag);
     for (int k = 0; k < ntaps; ++k) taps[k] = (int16_t) q[k];
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Spectrum": the segments and whole groups of a span (spectrum_span, gpsiq_spectrum_plan.h)
+int gpsiq_spectrum_span(int nsamp, int nfft, int hop, int navg, int *nseg, int *ngroups)
+{
+    if (nsamp < 0 || !spectrum_shape_ok(nfft, hop, 0, navg))
+        return fail(GPSIQ_E_ARG, "nsamp %d >= 0, nfft %d in {64, 128, 256, 512}, hop %d nfft/2 or nfft, navg %d >= 1", nsamp, nfft, hop, navg);
+    int s = 0, g = 0;
+    spectrum_span(nsamp, nfft, hop, navg, &s, &g);
+    if (nseg) *nseg = s;
+    if (ngroups) *ngroups = g;
+    return GPSIQ_OK;
+}
+
+// ibid.: the smallest shift with 2 navg Ys^2 <= 2^64 - 1 (spectrum_fits, ibid.), or a negative error
+int gpsiq_spectrum_min_shift(int sample_size, int nfft, int window, int navg)
+{
+    if ((sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) || !spectrum_shape_ok(nfft, nfft, window, navg))
+        return fail(GPSIQ_E_ARG, "sample size %d, nfft %d in {64, 128, 256, 512}, window %d 0 or 1, navg %d >= 1", sample_size, nfft, window, navg);
+    const int s = spectrum_min_shift(sample_size, nfft, window, navg);
+    return s < 0 ? fail(GPSIQ_E_RANGE, "no shift up to %d holds the sum of %d segments", kSpecMaxShift, navg) : s;
+}
+
+// ibid.: 4^shift / (navg 250^2 G N fs), G = sum w^2 / N of the window as the bins apply it (1 rectangular, 6 Hann)
+int gpsiq_spectrum_scale(int nfft, int window, int navg, int shift, double fs, double *scale)
+{
+    if (!scale) return fail(GPSIQ_E_ARG, "null argument");
+    if (!spectrum_shape_ok(nfft, nfft, window, navg) || shift < 0 || shift > kSpecMaxShift || !(fs > 0.0) || !std::isfinite(fs))
+        return fail(GPSIQ_E_ARG, "nfft %d, window %d, navg %d, shift %d in 0..%d, fs %g positive and finite", nfft, window, navg, shift, kSpecMaxShift, fs);
+    *scale = std::ldexp(1.0, 2 * shift) / ((double) navg * 62500.0 * (window ? 6.0 : 1.0) * (double) nfft * fs);
     return GPSIQ_OK;
 }
 

@@ -173,6 +173,11 @@ _filter_span = _sig("gpsiq_filter_span", _i, _i, _i, _i, C.POINTER(_i), C.POINTE
 _filter_design = _sig("gpsiq_filter_design", _i, _d, _d, _i, _i, _vp)
 _generate_batch_filtered = _sig("gpsiq_generate_batch_filtered", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(C.c_uint64), _vp)
 _filter_last_plan = _sig("gpsiq_filter_last_plan", _i, _vp, _vp)
+_spectrum = _sig("gpsiq_spectrum", _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(C.c_float))
+_spectrum_span = _sig("gpsiq_spectrum_span", _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i))
+_spectrum_min_shift = _sig("gpsiq_spectrum_min_shift", _i, _i, _i, _i, _i)
+_spectrum_scale = _sig("gpsiq_spectrum_scale", _i, _i, _i, _i, _i, _d, C.POINTER(_d))
+_spectrum_last_plan = _sig("gpsiq_spectrum_last_plan", _i, _vp, _vp)
 
 
 class NoiseSettings(C.Structure):
@@ -716,6 +721,28 @@ def filter_design(fs, cutoff_hz, ntaps, shift=14):
     return taps
 
 
+def spectrum_span(nsamp, nfft, hop=None, navg=1):
+    """gpsiq_spectrum_span: (segments of nfft samples, hop apart, in a span of nsamp samples; whole groups of navg of them)."""
+    nseg, ngroups = _i(0), _i(0)
+    _check(_spectrum_span(int(nsamp), int(nfft), int(nfft if hop is None else hop), int(navg), C.byref(nseg), C.byref(ngroups)))
+    return nseg.value, ngroups.value
+
+
+def spectrum_min_shift(sample_size, nfft, window, navg):
+    """gpsiq_spectrum_min_shift: the smallest shift at which the sum of navg segments cannot pass 2**64 - 1."""
+    s = _spectrum_min_shift(int(sample_size), int(nfft), int(window), int(navg))
+    if s < 0:
+        _check(s)
+    return s
+
+
+def spectrum_scale(nfft, window, navg, shift, fs):
+    """gpsiq_spectrum_scale: the factor that turns a cell of Context.spectrum() into stream units squared per Hz."""
+    v = _d(0.0)
+    _check(_spectrum_scale(int(nfft), int(window), int(navg), int(shift), float(fs), C.byref(v)))
+    return v.value
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -1020,6 +1047,34 @@ class Context:
         """What the last filter() / generate_batch_filtered() took: (kernel name or None, grid, outputs of a workgroup's run, pieces)."""
         out = (C.c_long * 4)()
         _check(_filter_last_plan(self._h, out))
+        return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def spectrum(self, nsamp, sample_size, device_ptr, nfft, hop=None, window=1, navg=None, shift=None, stream=None, out=None):
+        """gpsiq_spectrum: the exact integer power spectrum of the nsamp complex samples at device_ptr -> uint64 [ngroups][nfft].  hop
+        defaults to nfft, navg to all segments in one group, shift to spectrum_min_shift.  out: a C-contiguous uint64 array the call
+        writes instead of a fresh one (the caller's to size).  The kernels' device time of the last call is self.spectrum_ms."""
+        hop = int(nfft) if hop is None else int(hop)
+        if navg is None:
+            navg = max(spectrum_span(nsamp, nfft, hop, 1)[0], 1)
+        if shift is None:
+            shift = spectrum_min_shift(sample_size, nfft, window, navg)
+        if out is None:
+            try:
+                groups = spectrum_span(nsamp, nfft, hop, navg)[1]
+            except GpsiqError:
+                groups = 0                                            # the call itself refuses what the span arithmetic refuses
+            out = np.zeros((max(groups, 1), max(int(nfft), 1)), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous
+        ng, ms = _i(0), C.c_float(0.0)
+        _check(_spectrum(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(stream or 0), int(nfft), hop, int(window), int(navg), int(shift),
+                         _p(out), C.byref(ng), C.byref(ms)))
+        self.spectrum_ms = float(ms.value)
+        return out.reshape(-1, int(nfft))[:ng.value]
+
+    def spectrum_last_plan(self):
+        """What the last spectrum() took: (kernel name or None, grid, segments of a unit or a pass, groups)."""
+        out = (C.c_longlong * 4)()
+        _check(_spectrum_last_plan(self._h, out))
         return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def pack_last_plan(self):

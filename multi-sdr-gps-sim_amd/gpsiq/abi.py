@@ -10,6 +10,9 @@ SC08, SC16 = 1, 2
 PK4, PK2 = 4, 2          # packed stream formats (include/gpsiq_rows.h, "Packed streams"): bits per component
 # gpsiq_filter (include/gpsiq_rows.h, "Filter"): the ranges of its arguments
 FILTER_MAX_TAPS, FILTER_MAX_DECIM, FILTER_MAX_SHIFT, FILTER_TAP_SUM = 512, 16, 24, 65535
+# gpsiq_spectrum (include/gpsiq_rows.h, "Spectrum"): the windows, the sizes and the largest shift
+WINDOW_RECT, WINDOW_HANN = 0, 1
+SPECTRUM_NFFT, SPECTRUM_MAX_SHIFT = (64, 128, 256, 512), 40
 SINK_IQFILE, SINK_HACKRF, SINK_PLUTOSDR = 1, 2, 3
 HACKRF_CHUNK = 262144
 

@@ -15,7 +15,7 @@
  *
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
  *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
- *                  [--filter cutoff_hz [--taps n] [--decim d]]
+ *                  [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -58,6 +58,10 @@
  * gpsiq_filter_design(fs, cutoff, n, 14): --taps <n> (odd, 3..511, default 65), --decim <d> (1..16, default 1; the block length must be
  * a multiple of it).  The cutoff lies in (0, fs/2).  Every call to the library starts from a history of zeros.  The elements the
  * filter's clamp changed are counted and printed.  Not with --pack, --acquire or --follow.
+ * Spectrum (optional, same place): --spectrum <nfft> (64, 128, 256 or 512) analyses the run's FIRST block, as written and where it lies
+ * (page-locked, so the device reads it in place), with gpsiq_spectrum (include/gpsiq_rows.h, "Spectrum"): Hann window, half overlap, every
+ * segment in one group, at gpsiq_spectrum_min_shift; it writes one "bin_hz density" line per bin, from -fs/2 up, to <out.bin>.psd --
+ * density in stream units squared per Hz through gpsiq_spectrum_scale, fs the rate of the written stream.  Not with --pack.
  */
 #include <math.h>
 #include <stdint.h>
@@ -156,6 +160,31 @@ static int refresh_ephemeris(struct host_state *h, double t)
     return 0;
 }
 
+/* --spectrum: the power spectral density of one written block (page-locked, so the device reads it in place), one line per bin */
+static int run_spectrum(gpsiq_ctx_t *gq, const void *block, int nsamp, int ss, double fs, int nfft, const char *out_path)
+{
+    static uint64_t power[512];
+    char path[4096];
+    int nseg = 0, ngroups = 0;
+    double scale = 0.0;
+    if (snprintf(path, sizeof path, "%s.psd", out_path) >= (int) sizeof path) return -1;
+    if (gpsiq_spectrum_span(nsamp, nfft, nfft / 2, 1, &nseg, NULL) != GPSIQ_OK) return -1;
+    if (nseg < 1) { fprintf(stderr, "gpsiq_runahead: a block of %d samples holds no segment of %d\n", nsamp, nfft); return -1; }
+    const int shift = gpsiq_spectrum_min_shift(ss, nfft, GPSIQ_WINDOW_HANN, nseg);
+    if (shift < 0) return -1;
+    if (gpsiq_spectrum(gq, nsamp, ss, block, NULL, nfft, nfft / 2, GPSIQ_WINDOW_HANN, nseg, shift, power, &ngroups, NULL) != GPSIQ_OK || ngroups != 1) return -1;
+    if (gpsiq_spectrum_scale(nfft, GPSIQ_WINDOW_HANN, nseg, shift, fs, &scale) != GPSIQ_OK) return -1;
+    FILE *f = fopen(path, "w");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return -1; }
+    for (int i = 0; i < nfft; ++i) {
+        const int k = (i + nfft / 2) % nfft;                                   /* from -fs/2 up */
+        fprintf(f, "%.3f %.9e\n", (double) (k < nfft / 2 ? k : k - nfft) * fs / (double) nfft, (double) power[k] * scale);
+    }
+    fclose(f);
+    printf("spectrum: %d bins of %.3f Hz, %d segments, shift %d -> %s\n", nfft, fs / (double) nfft, nseg, shift, path);
+    return 0;
+}
+
 /* --acquire: the blind search of one rendered block (page-locked, so the device reads it in place), one line per satellite */
 #define ACQ_BINS 21
 #define ACQ_BINS_FOLLOW 41      /* with --follow: bins of 250 Hz, the follower's pull-in range */
@@ -244,11 +273,13 @@ int main(int argc, char **argv)
     int follow = 0;
     double filter_hz = NAN;
     int filter = 0, ftaps = 65, fdecim = 1, fopts = 0;
+    int spectrum = 0, spec_nfft = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
                         strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0 ||
-                        strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0))) break;
+                        strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0 ||
+                        strcmp(argv[argc - 2], "--spectrum") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
@@ -257,6 +288,7 @@ int main(int argc, char **argv)
         else if (strcmp(argv[argc - 2], "--filter") == 0) { filter_hz = atof(argv[argc - 1]); filter = 1; }
         else if (strcmp(argv[argc - 2], "--taps") == 0) { ftaps = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--decim") == 0) { fdecim = atoi(argv[argc - 1]); fopts = 1; }
+        else if (strcmp(argv[argc - 2], "--spectrum") == 0) { spec_nfft = atoi(argv[argc - 1]); spectrum = 1; }
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
@@ -274,13 +306,16 @@ int main(int argc, char **argv)
     const int filter_bad = (fopts && !filter) ||
                            (filter && (pack_given || acquire || follow || !(filter_hz > 0.0) || !(filter_hz < fs_arg / 2.0) || ftaps < 3 || ftaps > 511 ||
                                        !(ftaps & 1) || fdecim < 1 || fdecim > 16 || (int) floor(fs_arg / 10.0 + 0.5) % fdecim != 0));
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]]\n"
+    /* --spectrum: one of the four sizes, on rendered elements */
+    const int spectrum_bad = spectrum && (pack_given || (spec_nfft != 64 && spec_nfft != 128 && spec_nfft != 256 && spec_nfft != 512));
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft]\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
                         "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
                         "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n"
                         "       --filter needs a cutoff in (0, fs/2), odd --taps 3..511 (default 65), --decim 1..16 (default 1) dividing the block length;\n"
-                        "                not with --pack, --acquire or --follow\n", argv[0]);
+                        "                not with --pack, --acquire or --follow\n"
+                        "       --spectrum needs 64, 128, 256 or 512; not with --pack\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -414,6 +449,7 @@ int main(int argc, char **argv)
                     if (run_follow(gq, buf, (int) span, ss, fs, 250.0, &found) != 0) return die("follow");
                 }
             }
+            if (spectrum && done == 0 && b == 0 && run_spectrum(gq, buf, nsamp / fdecim, ss, fs / (double) fdecim, spec_nfft, argv[10]) != 0) return die("spectrum");
             if (fwrite(buf, blk_bytes, (size_t) nb, fo) != (size_t) nb) { fprintf(stderr, "short write\n"); return 1; }
         }
         done += n;
