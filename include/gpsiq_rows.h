@@ -549,6 +549,86 @@ int gpsiq_spectrum_span(int nsamp, int nfft, int hop, int navg, int *nseg, int *
 int gpsiq_spectrum_min_shift(int sample_size, int nfft, int window, int navg);              /* host arithmetic: the shift, or a negative error */
 int gpsiq_spectrum_scale(int nfft, int window, int navg, int shift, double fs, double *scale); /* host arithmetic */
 
+/* ---- Mix: tones, chirps and delayed streams summed on the device -----------------------------------------------------------------------
+ * The stage that puts something hostile or second-hand into a stream: a CW or swept jammer at a set J/S, a pulsed interferer, a
+ * repeater (the stream again, delayed and turned in frequency), a second scenario.  One operation: a sum of up to GPSIQ_MIX_MAX_TERMS
+ * terms onto an output stream, then the rounding shift and the counted symmetric clamp of the filter and the level stage.  Integers
+ * only, like every other stage: a restatement in numpy agrees with the device byte for byte.
+ *
+ * Sample index.  For output sample n in [0, nsamp) the absolute index is m = m0 + n, a uint64 that wraps mod 2^64.
+ * Terms.  terms is host memory, 1 <= nterms <= 8.  For term k:
+ *   Gate.  on(m) = gate_period == 0 || (m + gate_offset) mod gate_period < gate_on (m + gate_offset wraps mod 2^64 first).  A term
+ *   that is off contributes 0.
+ *   Source sample (GPSIQ_MIX_STREAM, GPSIQ_MIX_ROTATED).  x(n) = 0 for n < skip, otherwise sample n - skip of src: interleaved I,Q, int8
+ *   for sample_size GPSIQ_SC08 and int16 for GPSIQ_SC16, elements as stored.  Exactly max(0, nsamp - skip) samples of src are read; with
+ *   skip >= nsamp nothing is.
+ *   Sweep position.  r = m with sweep_period == 0, otherwise r = (m + sweep_offset) mod sweep_period (the sum wraps mod 2^64 first).
+ *   Phase.  theta = (phase0 + m*step + tri(r)*rate) mod 2^59 in units of 2^-59 cycle, tri(r) = r(r-1)/2 the exact integer: the
+ *   instantaneous step at sweep position r is step + r*rate.  Every product is taken mod 2^64, which is exact because 2^59 divides it.
+ *   Table.  idx = theta >> 50, (c, s) = (cosTable512[idx], sinTable512[idx]): the unit table of gpsiq_despread, amplitude 250.
+ *   Value.  GPSIQ_MIX_STREAM: t = (xi, xq).  GPSIQ_MIX_ROTATED: t = (xi*c - xq*s, xi*s + xq*c).  GPSIQ_MIX_TONE: t = (c, s).  A tone
+ *   with a positive step peaks in the positive bin of gpsiq_spectrum.
+ * Sum and output.  acc = sum over k of gain_k * t_k in int64, I and Q alike; it cannot wrap (|t| < 2^24, |gain| < 2^31, 8 terms).
+ * y = acc at shift 0, otherwise y = floor((acc + 2^(shift-1)) / 2^shift); out = min(max(y, -qmax), qmax).  *clipped is the number of
+ * elements the clamp changed.
+ * Ranges.  1 <= nterms <= 8; 0 <= shift <= 40; 1 <= qmax <= 127 for an int8 dst (out_sample_size GPSIQ_SC08) and <= 32767 for an int16
+ * dst; nsamp >= 0; kind one of the three; gate_on <= gate_period; sweep_offset < sweep_period where sweep_period != 0 and gate_offset <
+ * gate_period where gate_period != 0 (0 otherwise); reserved fields 0; for the stream kinds src not NULL, 4-byte aligned, sample_size
+ * GPSIQ_SC08 or GPSIQ_SC16; for a tone src NULL, skip 0; dst not NULL and 4-byte aligned: anything else is GPSIQ_E_ARG.
+ * Memory.  dst and every src are device memory or page-locked memory of gpsiq_host_alloc.  dst may be THE SAME ADDRESS as a stream
+ * term's src if that term has skip 0 and dst's sample size: the in-place case, a jammer added to a rendered stream where it lies.  Any
+ * other overlap of dst with a range a term reads is GPSIQ_E_ARG.  Bytes past the ranges above are never read, bytes past
+ * 2*nsamp*out_sample_size of dst never written.
+ * Stream order and return.  The terms cross to the device on hip_stream (a hipStream_t, NULL = the null stream) and the kernel is
+ * queued there, behind the caller's work; the call then waits, fetches the count and returns: synchronous, like gpsiq_filter.
+ * nsamp == 0 launches nothing and returns GPSIQ_OK with a count of 0.  kernel_ms (may be NULL) is the kernel's device time.  The same
+ * call twice gives the same bytes.  GPSIQ_MIX_KERNEL=generic|rows in the environment, read per call, forces a kernel where it can
+ * serve; the bytes and the count do not depend on it.
+ * Continuation is part of the contract: mixing a span in pieces gives exactly the bytes and the count of one call, when each later
+ * piece is called with m0 advanced by the samples done and its terms advanced by gpsiq_mix_advance: for the stream kinds
+ * skip' = max(0, skip - done) and src moves forward by max(0, done - skip) samples; everything else is untouched.
+ *
+ * gpsiq_mix_tone turns frequencies into the integers of a term: step = rint(f0/fs * 2^59); with sweep_s == 0 rate 0 and period 0,
+ * otherwise period = rint(sweep_s*fs) and rate = rint((f1 - f0)/fs/period * 2^59): a sawtooth sweep from f0 to f1.  GPSIQ_E_RANGE where
+ * |step| or |rate*period| reaches 2^58 (half the sampling rate), or the period is < 2 or >= 2^32; GPSIQ_E_ARG for an fs that is not
+ * positive and finite, or a value that is not finite.
+ * gpsiq_mix_gain gives gain = rint(amplitude * 2^shift / unit), unit 1 for GPSIQ_MIX_STREAM and 250 otherwise; GPSIQ_E_RANGE at
+ * |gain| >= 2^31.  Units: a satellite of descriptor gain g has amplitude 250*g in an unlevelled stream and 250*g*mult/65536 with the
+ * output level on (gpsiq_level_mult); a tone of amplitude A has power A^2; so J/S in dB is 20 log10(A / that amplitude).
+ *
+ * gpsiq_generate_batch_mixed is gpsiq_generate_batch_filtered's piece loop with the mixer in the filter's place: a piece is rendered
+ * into device staging, mixed IN PLACE on a side stream -- a GPSIQ_MIX_STREAM term (base_gain, skip 0) plus the ntones tones (0..7,
+ * GPSIQ_MIX_TONE only), at m0 + b0*nsamp for a piece that starts at block b0 -- and its rows cross to HOST memory while the next piece
+ * renders.  The result is byte for byte, and count for count, gpsiq_mix of what ONE gpsiq_generate_batch over the whole timeline
+ * writes, in both NCO models, with noise and level; carrier continuation, the noise block counter and carr_phase_out are that call's.
+ * ch is host memory only, as for the filtered call.  GPSIQ_MIX_PIECE_BLOCKS=n in the environment, read per call, sets the blocks per
+ * piece (default: about 32 MiB of rendered stream). */
+#define GPSIQ_MIX_STREAM  0   /* t = x                       (unit 1)   */
+#define GPSIQ_MIX_ROTATED 1   /* t = x * (c + j s)           (unit 250) */
+#define GPSIQ_MIX_TONE    2   /* t = (c, s)                  (unit 250) */
+#define GPSIQ_MIX_MAX_TERMS 8
+typedef struct gpsiq_mix_term {
+    int32_t  kind, sample_size;      /* sample_size: stream kinds, GPSIQ_SC08 / GPSIQ_SC16 */
+    const void *src;                 /* stream kinds: sample 0 of the term; NULL for a tone */
+    uint64_t skip;                   /* stream kinds: delay in samples, zeros before it */
+    int32_t  gain, reserved;         /* signed integer gain; reserved 0 */
+    uint64_t phase0;                 /* 2^-59 cycle, at absolute sample 0 */
+    int64_t  step;                   /* 2^-59 cycle per sample */
+    int64_t  rate;                   /* 2^-59 cycle per sample^2: the step grows by rate every sample */
+    uint32_t sweep_period, sweep_offset;        /* 0: the sweep never restarts */
+    uint32_t gate_period, gate_on, gate_offset, reserved2;   /* gate_period 0: always on */
+} gpsiq_mix_term_t;
+int gpsiq_mix(gpsiq_ctx_t *ctx, int nsamp, uint64_t m0, const gpsiq_mix_term_t *terms /* host */, int nterms,
+              int shift, int qmax, int out_sample_size, void *dst, void *hip_stream,
+              uint64_t *clipped /* may be NULL */, float *kernel_ms /* may be NULL */);
+int gpsiq_mix_advance(gpsiq_mix_term_t *terms, int nterms, uint64_t done);                    /* host arithmetic */
+int gpsiq_mix_tone(double fs, double f0_hz, double f1_hz, double sweep_s, int64_t *step, int64_t *rate,
+                   uint32_t *sweep_period);                                                  /* host arithmetic */
+int gpsiq_mix_gain(double amplitude, int kind, int shift, int32_t *gain);                    /* host arithmetic */
+int gpsiq_generate_batch_mixed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+                               int32_t base_gain, const gpsiq_mix_term_t *tones, int ntones /* 0..7, GPSIQ_MIX_TONE only */, uint64_t m0,
+                               int shift, int qmax, void *dst_host, size_t dst_block_stride, uint64_t *clipped, double *carr_phase_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

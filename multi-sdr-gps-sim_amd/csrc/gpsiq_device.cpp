@@ -487,7 +487,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         GPSIQ_P(gpsiq_device_eval_stats), GPSIQ_P(gpsiq_device_eval_host_ms),
         GPSIQ_P(gpsiq_prn_code), GPSIQ_P(gpsiq_carrier_table), GPSIQ_P(gpsiq_generate_seeded), GPSIQ_P(gpsiq_noise_state), GPSIQ_P(gpsiq_noise_host),
         GPSIQ_P(gpsiq_despread_last_plan), GPSIQ_P(gpsiq_pack_last_plan), GPSIQ_P(gpsiq_acquire_last_plan), GPSIQ_P(gpsiq_follow_last_plan),
-        GPSIQ_P(gpsiq_filter_last_plan), GPSIQ_P(gpsiq_spectrum_last_plan),
+        GPSIQ_P(gpsiq_filter_last_plan), GPSIQ_P(gpsiq_spectrum_last_plan), GPSIQ_P(gpsiq_mix_last_plan),
 #undef GPSIQ_P
         // the internals libgpsiq_rows.so runs on (gpsiq_rows_link.cpp): one pool, one quantiser, one error text per thread
         {"set_error", reinterpret_cast<void *>(&gpsiq::set_error)}, {"parallel_for", reinterpret_cast<void *>(&gpsiq::parallel_for)},
@@ -502,6 +502,8 @@ extern "C" void *gpsiq_plumbing(const char *name)
         {"filter", reinterpret_cast<void *>(&gpsiq_filter_impl)},          // gpsiq_filter and gpsiq_generate_batch_filtered of libgpsiq_rows.so
         {"generate_batch_filtered", reinterpret_cast<void *>(&gpsiq_generate_batch_filtered_impl)},      // (ibid., "Filter"; gpsiq_filter.cpp)
         {"spectrum", reinterpret_cast<void *>(&gpsiq_spectrum_impl)},      // gpsiq_spectrum of libgpsiq_rows.so (ibid., "Spectrum"; gpsiq_spectrum.cpp)
+        {"mix", reinterpret_cast<void *>(&gpsiq_mix_impl)},                // gpsiq_mix and gpsiq_generate_batch_mixed of libgpsiq_rows.so
+        {"generate_batch_mixed", reinterpret_cast<void *>(&gpsiq_generate_batch_mixed_impl)},            // (ibid., "Mix"; gpsiq_mix.cpp)
     };
     if (!name) return nullptr;
     for (const auto &e : table)

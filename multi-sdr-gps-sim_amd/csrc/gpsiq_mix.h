@@ -1,0 +1,62 @@
+// gpsiq_mix.h -- what the device context holds for gpsiq_mix / gpsiq_generate_batch_mixed (include/gpsiq_rows.h, "Mix") and what their
+// host side (gpsiq_mix.cpp) and their kernels (gpsiq_mix_kernels.hip, with gpsiq_mix_geometry.h) use of each other.  The plan is in
+// gpsiq_mix_plan.h.  Host code; gpsiq_ctx.h includes this header for the context's member `mix`.
+#ifndef GPSIQ_MIX_H
+#define GPSIQ_MIX_H
+
+#include <vector>
+
+#include "gpsiq_internal.h"
+#include "gpsiq_own.h"
+#include "gpsiq_mix_geometry.h"
+
+namespace gpsiq {
+
+// the carrier table as the kernels read it (512 dwords: cos below, sin above) on the device (have: it has arrived) and page-locked on
+// its way there, the counter of clamped elements and its page-locked twin, the two events a kernel is timed with, and what the batch
+// call works through its pieces with -- two rendered staging buffers taken in turn (the mixer works in place), a stream for the
+// mixer, one for the copies, and per buffer the events "mixed" and "copied"
+struct MixSet {
+    DevBuf<uint32_t>              d_table;   PinnedBuf<uint32_t>           h_table;       // [512]
+    bool                          have_table = false;
+    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
+    DevBuf<uint8_t>               d_render[2];                                            // bytes
+    Stream         mix_stream, copy_stream;
+    Event          t0, t1, mixed[2], copied[2];
+    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, units, pieces (gpsiq_mix_last_plan)
+    int reserve(size_t render_bytes);               // first use + room for one call (0: gpsiq_mix)
+};
+
+// (table, counter, events and streams on first use; the staging pair grows together)
+inline int MixSet::reserve(size_t render_bytes)
+{
+    HIP_TRY(t0.ensure(hipEventDefault));
+    HIP_TRY(t1.ensure(hipEventDefault));
+    HIP_TRY(reserve_together(512, 512, d_table, h_table));
+    HIP_TRY(d_count.reserve(1));
+    HIP_TRY(h_count.reserve(1));
+    if (!render_bytes) return GPSIQ_OK;
+    HIP_TRY(mix_stream.ensure());
+    HIP_TRY(copy_stream.ensure());
+    for (auto &e : mixed) HIP_TRY(e.ensure());
+    for (auto &e : copied) HIP_TRY(e.ensure());
+    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
+    return GPSIQ_OK;
+}
+
+// the mix kernels (gpsiq_mix_kernels.hip).  Arguments: the terms, m0, the samples, shift, qmax, destination; row kernel: the samples
+// of the first slot before sample 0 and the slots of the launch (gpsiq_mix_plan.h); the table; the counter of clamped elements
+using MixGenericFn = void (*)(const MixDevTerms, uint64_t, int, int, int, uint8_t *, const uint32_t *, unsigned long long *);
+using MixRowsFn    = void (*)(const MixDevTerms, uint64_t, int, int, int, uint8_t *, int, uint64_t, const uint32_t *, unsigned long long *);
+MixGenericFn mix_generic_kernel(int out_fmt);
+MixRowsFn    mix_rows_kernel(int out_fmt);
+
+}  // namespace gpsiq
+
+// gpsiq_mix.cpp: gpsiq_mix and gpsiq_generate_batch_mixed themselves, behind the plumbing entries "mix" and "generate_batch_mixed".
+// Declared from the public prototypes, and hidden: a definition that has drifted from include/gpsiq_rows.h is another function, and
+// the library no longer links
+__attribute__((visibility("hidden"))) decltype(gpsiq_mix) gpsiq_mix_impl;
+__attribute__((visibility("hidden"))) decltype(gpsiq_generate_batch_mixed) gpsiq_generate_batch_mixed_impl;
+#endif

@@ -31,7 +31,8 @@ void *gpsiq_plumbing(const char *name);
  * csrc/gpsiq_pack.cpp) in the same way, each with the signature of the call it implements.
  * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise, and "follow" is gpsiq_follow (ibid., "Follow";
  * csrc/gpsiq_follow.cpp).  "filter" and "generate_batch_filtered" are gpsiq_filter and gpsiq_generate_batch_filtered (ibid., "Filter";
- * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp). */
+ * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp).  "mix" and
+ * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -210,6 +211,10 @@ int gpsiq_filter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
  * launched, no call yet, or one that failed), out[1] the grid, out[2] the segments of a unit (generic) or of a pass (matrix kernel),
  * out[3] the groups of the result. */
 int gpsiq_spectrum_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
+/* What the context's last gpsiq_mix / gpsiq_generate_batch_mixed took (csrc/gpsiq_mix_plan.h): out[0] the kernel (0 generic, 1 rows;
+ * -1: nothing was launched, no call yet, or one that failed), out[1] the grid, out[2] the units of the launch (samples for the generic
+ * kernel, 16-byte slots for the row kernel), out[3] the pieces of a batch call (0: not one; a batch call reports its first piece). */
+int gpsiq_mix_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
 
 #ifdef __cplusplus
 }

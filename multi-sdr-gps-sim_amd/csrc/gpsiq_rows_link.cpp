@@ -152,3 +152,23 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_spectrum(gpsiq_ctx_t
     static const auto f = gpsiq::core<decltype(&gpsiq_spectrum)>("spectrum");
     return f(ctx, nsamp, sample_size, src, hip_stream, nfft, hop, window, navg, shift, power, ngroups, kernel_ms);
 }
+
+// The mixer runs on the context's device (csrc/gpsiq_mix.cpp) and is exported here like the filter (include/gpsiq_rows.h, "Mix");
+// gpsiq_mix_advance, gpsiq_mix_tone and gpsiq_mix_gain, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_mix(gpsiq_ctx_t *ctx, int nsamp, uint64_t m0, const gpsiq_mix_term_t *terms, int nterms,
+                                                                int shift, int qmax, int out_sample_size, void *dst, void *hip_stream, uint64_t *clipped,
+                                                                float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_mix)>("mix");
+    return f(ctx, nsamp, m0, terms, nterms, shift, qmax, out_sample_size, dst, hip_stream, clipped, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_mixed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
+                                                                                 double fs, int sample_size, int32_t base_gain,
+                                                                                 const gpsiq_mix_term_t *tones, int ntones, uint64_t m0, int shift,
+                                                                                 int qmax, void *dst_host, size_t dst_block_stride, uint64_t *clipped,
+                                                                                 double *carr_phase_out)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_mixed)>("generate_batch_mixed");
+    return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, base_gain, tones, ntones, m0, shift, qmax, dst_host, dst_block_stride, clipped, carr_phase_out);
+}

@@ -1,11 +1,12 @@
 // gpsiq_stage_math.cpp -- the plain arithmetic that goes with the noise, the output level and the stream stages (include/gpsiq_rows.h):
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
-// and the taps of a filter, the segments, the shift and the scale of a spectrum.  Host code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves:
-// gpsiq_rows_link.cpp).
+// and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix.  Host
+// code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves: gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
 #include "gpsiq_spectrum_plan.h"
+#include "gpsiq_mix_geometry.h"
 
 #include <cmath>
 
@@ -222,6 +223,56 @@ int gpsiq_spectrum_scale(int nfft, int window, int navg, int shift, double fs, d
     if (!spectrum_shape_ok(nfft, nfft, window, navg) || shift < 0 || shift > kSpecMaxShift || !(fs > 0.0) || !std::isfinite(fs))
         return fail(GPSIQ_E_ARG, "nfft %d, window %d, navg %d, shift %d in 0..%d, fs %g positive and finite", nfft, window, navg, shift, kSpecMaxShift, fs);
     *scale = std::ldexp(1.0, 2 * shift) / ((double) navg * 62500.0 * (window ? 6.0 : 1.0) * (double) nfft * fs);
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Mix": the terms of a continuation, `done` samples on -- a stream term's delay shrinks, and once it is used up
+// its source moves forward; gates, sweeps and phases are functions of the absolute index and stay as they are
+int gpsiq_mix_advance(gpsiq_mix_term_t *terms, int nterms, uint64_t done)
+{
+    if (!terms || nterms < 0 || nterms > kMixMaxTerms) return fail(GPSIQ_E_ARG, "null terms or nterms %d outside 0..%d", nterms, kMixMaxTerms);
+    for (int k = 0; k < nterms; ++k) {
+        gpsiq_mix_term_t &t = terms[k];
+        if (t.kind != GPSIQ_MIX_STREAM && t.kind != GPSIQ_MIX_ROTATED) continue;
+        if (t.sample_size != GPSIQ_SC08 && t.sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "term %d: bad sample size %d", k, t.sample_size);
+        if (done <= t.skip) { t.skip -= done; continue; }
+        t.src = static_cast<const uint8_t *>(t.src) + (size_t) (done - t.skip) * 2 * (size_t) t.sample_size;
+        t.skip = 0;
+    }
+    return GPSIQ_OK;
+}
+
+// ibid.: frequencies into units of 2^-59 cycle per sample (and per sample squared); half the sampling rate is 2^58
+int gpsiq_mix_tone(double fs, double f0_hz, double f1_hz, double sweep_s, int64_t *step, int64_t *rate, uint32_t *sweep_period)
+{
+    if (!step || !rate || !sweep_period) return fail(GPSIQ_E_ARG, "null argument");
+    if (!(fs > 0.0) || !std::isfinite(fs) || !std::isfinite(f0_hz) || !std::isfinite(f1_hz) || !std::isfinite(sweep_s) || sweep_s < 0.0)
+        return fail(GPSIQ_E_ARG, "fs %g positive and finite, f0 %g and f1 %g finite, sweep %g finite and not negative", fs, f0_hz, f1_hz, sweep_s);
+    const double unit = std::ldexp(1.0, 59), half = std::ldexp(1.0, 58);
+    const double st = std::rint(f0_hz / fs * unit);
+    if (!(std::fabs(st) < half)) return fail(GPSIQ_E_RANGE, "f0 %g Hz reaches half the sampling rate %g", f0_hz, fs);
+    double period = 0.0, rt = 0.0;
+    if (sweep_s != 0.0) {
+        period = std::rint(sweep_s * fs);
+        if (!(period >= 2.0) || !(period < 4294967296.0)) return fail(GPSIQ_E_RANGE, "a sweep of %g s is %g samples: outside [2, 2^32)", sweep_s, period);
+        rt = std::rint((f1_hz - f0_hz) / fs / period * unit);
+        if (!(std::fabs(rt * period) < half)) return fail(GPSIQ_E_RANGE, "a sweep over %g Hz reaches half the sampling rate %g", f1_hz - f0_hz, fs);
+    }
+    *step = (int64_t) st;
+    *rate = (int64_t) rt;
+    *sweep_period = (uint32_t) period;
+    return GPSIQ_OK;
+}
+
+// ibid.: an amplitude in stream units into a term's integer gain; the table's amplitude is 250
+int gpsiq_mix_gain(double amplitude, int kind, int shift, int32_t *gain)
+{
+    if (!gain) return fail(GPSIQ_E_ARG, "null argument");
+    if ((kind != GPSIQ_MIX_STREAM && kind != GPSIQ_MIX_ROTATED && kind != GPSIQ_MIX_TONE) || shift < 0 || shift > kMixMaxShift || !std::isfinite(amplitude))
+        return fail(GPSIQ_E_ARG, "kind %d, shift %d in 0..%d, amplitude %g finite", kind, shift, kMixMaxShift, amplitude);
+    const double g = std::rint(std::ldexp(amplitude, shift) / (kind == GPSIQ_MIX_STREAM ? 1.0 : 250.0));
+    if (!(std::fabs(g) < 2147483648.0)) return fail(GPSIQ_E_RANGE, "a gain of %g does not fit 32 bits: lower the shift", g);
+    *gain = (int32_t) g;
     return GPSIQ_OK;
 }
 

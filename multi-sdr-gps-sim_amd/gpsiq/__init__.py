@@ -14,7 +14,7 @@ from .abi import (CHAN_DTYPE, QCHAN_DTYPE, SC08, SC16, SINK_HACKRF, SINK_IQFILE,
                   SINK_PLUTOSDR, HACKRF_CHUNK, MAX_CHAN, elem_dtype, EPHEM_DTYPE, IONO_DTYPE, TRACK_DTYPE,
                   NAV_EPH_DTYPE, NAV_UTC_DTYPE, NAV_ALM_DTYPE, NAV_STATE_DTYPE, RINEX_EPH_DTYPE, PATCH_DTYPE,
                   NCO_FIXED, NCO_REFERENCE, SHARD_CARRY_DTYPE, DESPREAD_SUM_DTYPE, BLOCK_STATS_DTYPE, ACQ_PEAK_DTYPE,
-                  FOLLOW_STATE_DTYPE, FOLLOW_EPOCH_DTYPE, FOLLOW_CFG_DTYPE)
+                  FOLLOW_STATE_DTYPE, FOLLOW_EPOCH_DTYPE, FOLLOW_CFG_DTYPE, MIX_STREAM, MIX_ROTATED, MIX_TONE, MIX_MAX_TERMS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPSIQ_LIB: another build of the library (tests/test_gpu_build.py loads the one it has just compiled on the GPU box)
@@ -178,6 +178,13 @@ _spectrum_span = _sig("gpsiq_spectrum_span", _i, _i, _i, _i, _i, C.POINTER(_i), 
 _spectrum_min_shift = _sig("gpsiq_spectrum_min_shift", _i, _i, _i, _i, _i)
 _spectrum_scale = _sig("gpsiq_spectrum_scale", _i, _i, _i, _i, _i, _d, C.POINTER(_d))
 _spectrum_last_plan = _sig("gpsiq_spectrum_last_plan", _i, _vp, _vp)
+_mix = _sig("gpsiq_mix", _i, _vp, _i, C.c_uint64, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_mix_advance = _sig("gpsiq_mix_advance", _i, _vp, _i, C.c_uint64)
+_mix_tone = _sig("gpsiq_mix_tone", _i, _d, _d, _d, _d, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32))
+_mix_gain = _sig("gpsiq_mix_gain", _i, _d, _i, _i, C.POINTER(C.c_int32))
+_generate_batch_mixed = _sig("gpsiq_generate_batch_mixed", _i, _vp, _vp, _i, _i, _i, _d, _i, C.c_int32, _vp, _i, C.c_uint64, _i, _i, _vp, _sz,
+                             C.POINTER(C.c_uint64), _vp)
+_mix_last_plan = _sig("gpsiq_mix_last_plan", _i, _vp, _vp)
 
 
 class NoiseSettings(C.Structure):
@@ -188,6 +195,40 @@ class NoiseSettings(C.Structure):
 class LevelSettings(C.Structure):
     """gpsiq_level_t (include/gpsiq_rows.h)."""
     _fields_ = [("mult", C.c_uint32), ("qmax", C.c_int32)]
+
+
+class MixTerm(C.Structure):
+    """gpsiq_mix_term_t (include/gpsiq_rows.h, "Mix"): one term of Context.mix().  MixTerm.stream / .rotated / .tone build one."""
+    _fields_ = [("kind", C.c_int32), ("sample_size", C.c_int32), ("src", C.c_void_p), ("skip", C.c_uint64), ("gain", C.c_int32),
+                ("reserved", C.c_int32), ("phase0", C.c_uint64), ("step", C.c_int64), ("rate", C.c_int64), ("sweep_period", C.c_uint32),
+                ("sweep_offset", C.c_uint32), ("gate_period", C.c_uint32), ("gate_on", C.c_uint32), ("gate_offset", C.c_uint32),
+                ("reserved2", C.c_uint32)]
+
+    @classmethod
+    def stream(cls, src, sample_size, gain, skip=0, gate=(0, 0, 0)):
+        """t = x: the stream at src (a device or page-locked address), delayed by skip samples; gate: (period, on, offset)."""
+        return cls(kind=MIX_STREAM, sample_size=int(sample_size), src=int(src), skip=int(skip), gain=int(gain), gate_period=int(gate[0]),
+                   gate_on=int(gate[1]), gate_offset=int(gate[2]))
+
+    @classmethod
+    def rotated(cls, src, sample_size, gain, step, skip=0, phase0=0, rate=0, sweep=(0, 0), gate=(0, 0, 0)):
+        """t = x (c + j s): the stream at src turned by the NCO (step, rate in 2**-59 cycle; sweep: (period, offset))."""
+        return cls(kind=MIX_ROTATED, sample_size=int(sample_size), src=int(src), skip=int(skip), gain=int(gain), phase0=int(phase0) % 2 ** 64,
+                   step=int(step), rate=int(rate), sweep_period=int(sweep[0]), sweep_offset=int(sweep[1]), gate_period=int(gate[0]),
+                   gate_on=int(gate[1]), gate_offset=int(gate[2]))
+
+    @classmethod
+    def tone(cls, gain, step, phase0=0, rate=0, sweep=(0, 0), gate=(0, 0, 0)):
+        """t = (c, s): the bare NCO, a tone (rate 0) or a chirp."""
+        return cls(kind=MIX_TONE, gain=int(gain), phase0=int(phase0) % 2 ** 64, step=int(step), rate=int(rate), sweep_period=int(sweep[0]),
+                   sweep_offset=int(sweep[1]), gate_period=int(gate[0]), gate_on=int(gate[1]), gate_offset=int(gate[2]))
+
+
+def _mix_terms(terms):
+    arr = (MixTerm * max(len(terms), 1))()
+    for k, t in enumerate(terms):
+        C.memmove(C.byref(arr, k * C.sizeof(MixTerm)), C.byref(t), C.sizeof(MixTerm))
+    return arr
 
 
 def _check(rc):
@@ -743,6 +784,32 @@ def spectrum_scale(nfft, window, navg, shift, fs):
     return v.value
 
 
+def mix_tone(fs, f0_hz, f1_hz=None, sweep_s=0.0):
+    """gpsiq_mix_tone: (step, rate, sweep_period) of a tone at f0_hz, or of a sawtooth sweep from f0_hz to f1_hz every sweep_s seconds."""
+    step, rate, period = C.c_int64(0), C.c_int64(0), C.c_uint32(0)
+    _check(_mix_tone(float(fs), float(f0_hz), float(f0_hz if f1_hz is None else f1_hz), float(sweep_s), C.byref(step), C.byref(rate), C.byref(period)))
+    return step.value, rate.value, period.value
+
+
+def mix_gain(amplitude, kind, shift):
+    """gpsiq_mix_gain: the integer gain that gives a term the amplitude (stream units) behind a rounding shift."""
+    g = C.c_int32(0)
+    _check(_mix_gain(float(amplitude), int(kind), int(shift), C.byref(g)))
+    return g.value
+
+
+def mix_advance(terms, done):
+    """gpsiq_mix_advance: the terms of a continuation `done` samples on, as a new list (the arguments stay as they are)."""
+    arr = _mix_terms(terms)
+    _check(_mix_advance(arr, len(terms), int(done)))
+    out = []
+    for k in range(len(terms)):
+        t = MixTerm()
+        C.memmove(C.byref(t), C.byref(arr, k * C.sizeof(MixTerm)), C.sizeof(MixTerm))
+        out.append(t)
+    return out
+
+
 def noise_host(seed, sigma, block, nsamp):
     """The library's host twin of the receiver noise: int32 array [nsamp, 2] of (zI, zQ) for absolute block `block`."""
     out = np.zeros((int(nsamp), 2), dtype=np.int32)
@@ -1076,6 +1143,42 @@ class Context:
         out = (C.c_longlong * 4)()
         _check(_spectrum_last_plan(self._h, out))
         return {0: "generic", 1: "mfma"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def mix(self, nsamp, m0, terms, shift, qmax, out_sample_size, dst_device_ptr, stream=None):
+        """gpsiq_mix: the sum of the MixTerm list `terms` over nsamp samples from absolute index m0, rounded by `shift`, clamped to
+        +-qmax into out_sample_size at dst_device_ptr (which may be a stream term's own source: in place) -> (elements the clamp
+        changed, kernel milliseconds)."""
+        arr = _mix_terms(terms)
+        clipped, ms = C.c_uint64(0), C.c_float(0.0)
+        _check(_mix(self._h, int(nsamp), int(m0) % 2 ** 64, arr, len(terms), int(shift), int(qmax), int(out_sample_size), _vp(dst_device_ptr),
+                    _vp(stream or 0), C.byref(clipped), C.byref(ms)))
+        return int(clipped.value), float(ms.value)
+
+    def generate_batch_mixed(self, desc, nsamp, fs, sample_size, base_gain, tones, shift, qmax, m0=0, host_ptr=None, block_stride=None,
+                             carr_out=None):
+        """gpsiq_generate_batch_mixed: the run-ahead call with base_gain times the rendered stream plus the MixTerm tones, rounded by
+        `shift` and clamped to +-qmax, in host memory.  Returns (int8 / int16 [nblocks][2 * nsamp], elements the clamp changed), the
+        array None when host_ptr names the caller's buffer (pageable or page-locked; block_stride bytes between blocks, default: back
+        to back)."""
+        desc = np.ascontiguousarray(desc, dtype=CHAN_DTYPE)
+        nb, nc = desc.shape
+        rlen = 2 * int(nsamp) * int(sample_size)
+        stride = rlen if block_stride is None else int(block_stride)
+        co = None if carr_out is None else _p(carr_out)
+        clipped = C.c_uint64(0)
+        out = None if host_ptr is not None else np.zeros((nb, stride), dtype=np.uint8)
+        arr = _mix_terms(tones)
+        _check(_generate_batch_mixed(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(sample_size), int(base_gain), arr, len(tones),
+                                     int(m0) % 2 ** 64, int(shift), int(qmax), _vp(host_ptr) if out is None else _p(out), stride, C.byref(clipped), co))
+        if out is None:
+            return None, int(clipped.value)
+        return np.ascontiguousarray(out[:, :rlen]).view(np.int8 if int(sample_size) == 1 else np.int16), int(clipped.value)
+
+    def mix_last_plan(self):
+        """What the last mix() / generate_batch_mixed() took: (kernel name or None, grid, units of the launch, pieces)."""
+        out = (C.c_longlong * 4)()
+        _check(_mix_last_plan(self._h, out))
+        return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def pack_last_plan(self):
         """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""

@@ -13,6 +13,9 @@ FILTER_MAX_TAPS, FILTER_MAX_DECIM, FILTER_MAX_SHIFT, FILTER_TAP_SUM = 512, 16, 2
 # gpsiq_spectrum (include/gpsiq_rows.h, "Spectrum"): the windows, the sizes and the largest shift
 WINDOW_RECT, WINDOW_HANN = 0, 1
 SPECTRUM_NFFT, SPECTRUM_MAX_SHIFT = (64, 128, 256, 512), 40
+# gpsiq_mix (include/gpsiq_rows.h, "Mix"): the kinds of a term, the terms of a call and the largest shift
+MIX_STREAM, MIX_ROTATED, MIX_TONE = 0, 1, 2
+MIX_MAX_TERMS, MIX_MAX_SHIFT = 8, 40
 SINK_IQFILE, SINK_HACKRF, SINK_PLUTOSDR = 1, 2, 3
 HACKRF_CHUNK = 262144
 

@@ -15,7 +15,7 @@
  *
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
  *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
- *                  [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft]
+ *                  [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]...
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -62,6 +62,12 @@
  * (page-locked, so the device reads it in place), with gpsiq_spectrum (include/gpsiq_rows.h, "Spectrum"): Hann window, half overlap, every
  * segment in one group, at gpsiq_spectrum_min_shift; it writes one "bin_hz density" line per bin, from -fs/2 up, to <out.bin>.psd --
  * density in stream units squared per Hz through gpsiq_spectrum_scale, fs the rate of the written stream.  Not with --pack.
+ * Tones (optional, same place, up to four times): --tone <f Hz>,<J/S dB> adds a CW jammer at baseband frequency f, --tone <f0>,<J/S>,<f1>,
+ * <sweep s> one that sweeps from f0 to f1 every <sweep s> seconds, and the run is written through gpsiq_generate_batch_mixed
+ * (include/gpsiq_rows.h, "Mix"): the rendered stream at gain 1 (2^8 behind a rounding shift of 8) plus the tones, at the absolute sample
+ * index of the run, clamped to --qmax (or the format's largest value) and the clamped elements counted and printed.  J/S is relative to
+ * a satellite of descriptor gain 1: amplitude 250, or 250 * mult / 65536 with --level (gpsiq_mix_gain has the units).  Not with --pack or
+ * --filter.
  */
 #include <math.h>
 #include <stdint.h>
@@ -261,6 +267,23 @@ static int run_follow(gpsiq_ctx_t *gq, const void *stream, int span, int ss, dou
     return 0;
 }
 
+/* --tone f_hz,js_db[,f1_hz,sweep_s]: the integers of gpsiq_mix_tone at fs and the J/S; nonzero for a value the flag refuses */
+#define MAX_TONES 4
+#define TONE_SHIFT 8
+struct tone { int64_t step, rate; uint32_t period; double js_db; };
+static int parse_tone(const char *arg, double fs, struct tone *t)
+{
+    double f0 = 0.0, js = 0.0, f1 = 0.0, sweep = 0.0;
+    char extra;
+    const int n = sscanf(arg, "%lf,%lf,%lf,%lf%c", &f0, &js, &f1, &sweep, &extra);
+    if (n == 2) { f1 = f0; sweep = 0.0; }
+    else if (n != 4 || !(sweep > 0.0)) return 1;
+    if (n == 2 && strchr(strchr(arg, ',') + 1, ',')) return 1;                 /* f,js, and then something that is no number */
+    if (!isfinite(js) || !(js >= -200.0) || !(js <= 200.0)) return 1;
+    t->js_db = js;
+    return gpsiq_mix_tone(fs, f0, f1, sweep, &t->step, &t->rate, &t->period) != GPSIQ_OK;
+}
+
 int main(int argc, char **argv)
 {
     double cn0 = NAN;
@@ -274,12 +297,14 @@ int main(int argc, char **argv)
     double filter_hz = NAN;
     int filter = 0, ftaps = 65, fdecim = 1, fopts = 0;
     int spectrum = 0, spec_nfft = 0;
+    const char *tone_arg[MAX_TONES + 1];
+    int ntone = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
                         strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0 ||
                         strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0 ||
-                        strcmp(argv[argc - 2], "--spectrum") == 0))) break;
+                        strcmp(argv[argc - 2], "--spectrum") == 0 || strcmp(argv[argc - 2], "--tone") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
@@ -289,6 +314,7 @@ int main(int argc, char **argv)
         else if (strcmp(argv[argc - 2], "--taps") == 0) { ftaps = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--decim") == 0) { fdecim = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--spectrum") == 0) { spec_nfft = atoi(argv[argc - 1]); spectrum = 1; }
+        else if (strcmp(argv[argc - 2], "--tone") == 0) { if (ntone <= MAX_TONES) tone_arg[ntone] = argv[argc - 1]; ++ntone; }
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
     }
@@ -308,14 +334,20 @@ int main(int argc, char **argv)
                                        !(ftaps & 1) || fdecim < 1 || fdecim > 16 || (int) floor(fs_arg / 10.0 + 0.5) % fdecim != 0));
     /* --spectrum: one of the four sizes, on rendered elements */
     const int spectrum_bad = spectrum && (pack_given || (spec_nfft != 64 && spec_nfft != 128 && spec_nfft != 256 && spec_nfft != 512));
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft]\n"
+    /* --tone: at most four, f,js or f0,js,f1,sweep with steps gpsiq_mix_tone accepts at this fs; not with --pack or --filter */
+    struct tone tone[MAX_TONES];
+    int tone_bad = ntone > MAX_TONES || (ntone && (pack_given || filter));
+    for (int k = 0; k < ntone && !tone_bad; ++k) tone_bad = parse_tone(tone_arg[ntone - 1 - k], fs_arg, &tone[k]);     /* (read from the end: as given) */
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad || tone_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]...\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
                         "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
                         "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n"
                         "       --filter needs a cutoff in (0, fs/2), odd --taps 3..511 (default 65), --decim 1..16 (default 1) dividing the block length;\n"
                         "                not with --pack, --acquire or --follow\n"
-                        "       --spectrum needs 64, 128, 256 or 512; not with --pack\n", argv[0]);
+                        "       --spectrum needs 64, 128, 256 or 512; not with --pack\n"
+                        "       --tone (up to four) needs f,J/S or f0,J/S,f1,sweep: frequencies inside (-fs/2, fs/2), a sweep of 2 samples or more;\n"
+                        "              not with --pack or --filter\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -390,6 +422,10 @@ int main(int argc, char **argv)
     if (!isnan(level_rms) && !(level_rms > 0.0)) { fprintf(stderr, "bad --level\n"); return 2; }
     if (qmax && isnan(level_rms)) { fprintf(stderr, "--qmax needs --level\n"); return 2; }
     int level_set = isnan(level_rms);                                          /* nothing to set without --level */
+    uint32_t level_mult = 0;                                                   /* the multiplier in force, 0: no level */
+    gpsiq_mix_term_t tones[MAX_TONES];
+    int tones_set = 0;
+    uint64_t tone_clipped = 0;
     const size_t blk_bytes = pack ? gpsiq_packed_block_bytes(nsamp, pack) : (size_t) 2 * (size_t) (nsamp / fdecim) * (size_t) ss;      /* as written */
     static int16_t taps[511];
     uint64_t filter_clipped = 0;
@@ -426,6 +462,7 @@ int main(int argc, char **argv)
                 const gpsiq_level_t lv = {gpsiq_level_mult(gpsiq_composite_rms(gain, ng, sigma), level_rms), qmax ? qmax : ss == 1 ? 127 : 32767};
                 if (gpsiq_set_level(gq, &lv) != GPSIQ_OK) return die("level");
                 level_set = 1;
+                level_mult = lv.mult;
             }
             if (pack) {
                 if (gpsiq_generate_batch_packed(gq, desc, nb, nchan, nsamp, fs, pack, buf, blk_bytes, carr) != GPSIQ_OK) return die("generate packed");
@@ -434,6 +471,22 @@ int main(int argc, char **argv)
                 if (gpsiq_generate_batch_filtered(gq, desc, nb, nchan, nsamp, fs, ss, taps, ftaps, 14, fdecim, ss, buf, blk_bytes, &clipped, carr) != GPSIQ_OK)
                     return die("generate filtered");
                 filter_clipped += clipped;
+            } else if (ntone) {
+                if (!tones_set) {                                              /* once: J/S against a satellite of descriptor gain 1 */
+                    const double unit = level_mult ? 250.0 * (double) level_mult / 65536.0 : 250.0;
+                    for (int k = 0; k < ntone; ++k) {
+                        memset(&tones[k], 0, sizeof tones[k]);
+                        tones[k].kind = GPSIQ_MIX_TONE;
+                        tones[k].step = tone[k].step; tones[k].rate = tone[k].rate; tones[k].sweep_period = tone[k].period;
+                        if (gpsiq_mix_gain(unit * pow(10.0, tone[k].js_db / 20.0), GPSIQ_MIX_TONE, TONE_SHIFT, &tones[k].gain) != GPSIQ_OK) return die("tone gain");
+                    }
+                    tones_set = 1;
+                }
+                uint64_t clipped = 0;
+                if (gpsiq_generate_batch_mixed(gq, desc, nb, nchan, nsamp, fs, ss, 1 << TONE_SHIFT, tones, ntone, (uint64_t) (done + b) * (uint64_t) nsamp,
+                                               TONE_SHIFT, qmax ? qmax : ss == 1 ? 127 : 32767, buf, blk_bytes, &clipped, carr) != GPSIQ_OK)
+                    return die("generate mixed");
+                tone_clipped += clipped;
             } else if (gpsiq_generate_batch(gq, desc, nb, nchan, nsamp, fs, ss, buf, 0, carr) != GPSIQ_OK) return die("generate");
             have_carr = 1;
             if (acquire && done == 0 && b == 0) {
@@ -474,6 +527,7 @@ int main(int argc, char **argv)
     fclose(fo);
     printf("%d blocks, %d channels, %d allocation passes, last nsat %d, ephemeris set %d of %d\n", nblocks, nchan, nalloc, nsat, h.ieph, nsets);
     if (filter) printf("filter: cutoff %g Hz, %d taps, decimation %d, %llu elements clipped\n", filter_hz, ftaps, fdecim, (unsigned long long) filter_clipped);
+    if (ntone) printf("tones: %d, %llu elements clipped\n", ntone, (unsigned long long) tone_clipped);
     gpsiq_host_free(buf);
     gpsiq_destroy(gq);
     free(desc); free(xyz);
