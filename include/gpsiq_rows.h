@@ -629,6 +629,86 @@ int gpsiq_generate_batch_mixed(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nbl
                                int32_t base_gain, const gpsiq_mix_term_t *tones, int ntones /* 0..7, GPSIQ_MIX_TONE only */, uint64_t m0,
                                int shift, int qmax, void *dst_host, size_t dst_block_stride, uint64_t *clipped, double *carr_phase_out);
 
+/* ---- Resample: a device polyphase resampler for rate and clock offset ------------------------------------------------------------------
+ * The stage that takes a stream off the sample clock it was rendered on: one render feeds front ends at other rates (2.6 Msps to a
+ * 2.048 Msps receiver), a stream that can no longer be rendered again (a jammer mixed in) changes rate, and a receiver whose clock is
+ * off by some parts per million is a step slightly away from one.  gpsiq_filter decimates by whole numbers; this stage moves by any
+ * ratio from 1/8 to 8, with a table of FIR rows indexed by the fraction of the output's position.  Integers only, like every other
+ * stage: a restatement in numpy agrees with the device byte for byte.
+ *
+ * Input.  src is ONE contiguous span of nsamp complex samples, interleaved I,Q, int8 for GPSIQ_SC08 and int16 for GPSIQ_SC16, elements
+ * as stored, base 4-byte aligned -- the filter's span.  x(m) is sample m of src for 0 <= m < nsamp.  For -(ntaps-1) <= m < 0, x(m) is
+ * sample ntaps-1+m of head: ntaps-1 samples in the same format, 4-byte aligned; head == NULL means those samples are zeros.
+ * Position.  pos0 and step are uint64_t in units of 2^-32 input sample.  Output j sits at p_j = pos0 + j*step, with integer index
+ * m_j = p_j >> 32 and fraction f_j = p_j & 0xffffffff.  nout = 0 if pos0 >= nsamp * 2^32, otherwise nout = ceil((nsamp * 2^32 - pos0) /
+ * step): every j with m_j < nsamp.  next_pos = pos0 + nout*step - nsamp * 2^32.  (gpsiq_resample_span: host arithmetic in 128 bits,
+ * either result pointer may be NULL; its nsamp is 64 bits wide because the batch call spans more than an int, and must stay below
+ * 2^60.)  nout can reach 2^34 when upsampling: it is 64 bits everywhere.
+ * Taps.  taps is host memory, int16_t [nphases + 1][ntaps] with nphases = 2^log2_phases.  Row nphases is the caller's "phase 0, one
+ * sample later"; it is read only when interp != 0, and it is always present.  With L = log2_phases: q_j = f_j >> (32 - L) (0 when
+ * L == 0) and mu_j = interp ? (f_j >> (24 - L)) & 255 : 0 -- the eight bits of the fraction below the row index.
+ * Arithmetic.  For I and Q alike: a0 = sum over k < ntaps of taps[q_j][k] * x(m_j - k), and with interp a1 = sum over k of
+ * taps[q_j + 1][k] * x(m_j - k), both exact.  Without interp y = a0 at shift == 0, otherwise y = floor((a0 + 2^(shift-1)) / 2^shift).
+ * With interp y = floor(((256 - mu_j) * a0 + mu_j * a1 + 2^(shift+7)) / 2^(shift+8)), evaluated in 64 bits.  out = min(max(y, -qmax),
+ * qmax) with qmax 127 for an int8 dst and 32767 for an int16 dst.  *clipped is the number of elements the clamp changed.  The stage is
+ * causal like the filter: the group delay is the taps' own, (ntaps-1)/2 input samples for the designed ones.
+ * Ranges.  0 <= log2_phases <= 8, 1 <= ntaps <= 64, (nphases + 1) * ntaps <= 8256, 0 <= shift <= 16, interp 0 or 1,
+ * 2^29 <= step <= 2^35 (a ratio from 1/8 to 8), pos0 < 2^63, nsamp >= 0, both sample sizes GPSIQ_SC08 or GPSIQ_SC16 in any of the four
+ * combinations: anything else is GPSIQ_E_ARG.  Every one of the nphases + 1 rows must have sum over k of |taps[r][k]| <= 65535, else
+ * GPSIQ_E_RANGE: with it |a0|, |a1| < 2^31 for both input formats, so there is one accumulator width; only the interpolated combine
+ * needs 64 bits.
+ * Memory.  dst is device memory, 4-byte aligned, and receives exactly nout complex samples back to back; bytes past them are never
+ * written, bytes past 2*nsamp*sample_size of src never read.  dst must not overlap src or head (GPSIQ_E_ARG).  src, head and dst may
+ * also be page-locked memory of gpsiq_host_alloc.  taps is host memory.
+ * Stream order and return.  The taps cross to the device on hip_stream (a hipStream_t, NULL = the null stream) and the kernel is
+ * queued there: it runs behind the caller's work on that stream.  The call then waits, fetches the count and returns: synchronous,
+ * like gpsiq_filter; taps may be overwritten once it has returned.  nsamp == 0 or nout == 0 launches nothing and returns GPSIQ_OK with
+ * a count of 0.  *nout, *next_pos, *clipped and *kernel_ms (the kernel's device time) may each be NULL.  The same call twice gives the
+ * same bytes.  GPSIQ_RESAMPLE_KERNEL=generic|rows in the environment, read per call by both calls, forces a kernel; the bytes and the
+ * count do not depend on it.
+ * Continuation is part of the contract: resampling a span in pieces gives exactly the bytes, the count and the final next_pos of one
+ * call over the whole span, when each piece is called with head set to the last ntaps-1 samples before it (of more than one earlier
+ * piece, where a piece is shorter than that) and pos0 set to the previous piece's next_pos -- also where a piece is so short that it
+ * yields no output (pos0 >= nsamp * 2^32: next_pos = pos0 - nsamp * 2^32).  A drifting clock is a step that changes between pieces:
+ * that is why there is no in-call rate term.
+ *
+ * gpsiq_resample_step gives step = rint(2^32 * fs_in / (fs_out * (1 + ppb * 1e-9))): fs_out is the nominal rate of the receiver, ppb
+ * how far its clock runs fast.  GPSIQ_E_RANGE outside the legal steps; GPSIQ_E_ARG for a rate that is not positive and finite, a ppb
+ * that is not finite, or a NULL pointer.
+ * gpsiq_resample_design fills taps [nphases + 1][ntaps] from a Hamming-windowed sinc prototype g with its cutoff at bandwidth * 0.5 *
+ * min(1, 2^32/step) of the input rate, 0 < bandwidth <= 1: row r, tap k is g(k + r/nphases - (ntaps-1)/2), r = 0..nphases, with
+ * g(t) = sinc(2 fc t) * (0.54 + 0.46 cos(2 pi t / (ntaps-1))) for |t| <= (ntaps-1)/2 and zero outside: the Hamming window of ntaps
+ * points, centred like the sinc.  Row nphases therefore is row 0 shifted by one tap (taps[nphases][k] against taps[0][k+1]) with a zero
+ * in the vacated last place, and every row between has its last tap zero.  Each row is scaled to a sum of 2^shift and rounded with
+ * rint; the remainder goes to its largest tap (the first of equals), so every row sums to 2^shift exactly and the DC gain is 1 at every
+ * phase.  Row 0 carries one end tap more than row nphases, so the two are scaled a little differently: they agree to that ratio, not to
+ * the bit.  For 0 < r < nphases row nphases - r is row r mirrored, taps[nphases-r][k] == taps[r][ntaps-2-k], to the bit (the row
+ * r = nphases/2 of an odd ntaps, whose two largest taps are equal, carries its remainder on the first of them).  8 <= shift <= 14,
+ * 2 <= ntaps <= 64, the ranges above otherwise (GPSIQ_E_ARG); GPSIQ_E_RANGE if a row would break the bound on its sum of magnitudes.
+ * Double arithmetic: its properties are contract, its bits are not.
+ *
+ * gpsiq_generate_batch_resampled is gpsiq_generate_batch_filtered's piece loop with the resampler in the filter's place: a piece is
+ * rendered into one of two device staging buffers at sample_size, resampled on a side stream, and its samples cross to HOST memory
+ * (pageable or page-locked) while the next piece renders; history and next_pos pass from piece to piece inside the call.  The output is
+ * ONE contiguous stream of *nout samples of out_sample_size at dst_host, with no block structure, because the count per block varies.
+ * Byte for byte, count for count and carr_phase_out bit for bit it equals gpsiq_resample, with head NULL, of what ONE
+ * gpsiq_generate_batch over the whole timeline writes, in both NCO models, with noise and level.  dst_capacity (in samples) below
+ * gpsiq_resample_span(nblocks*nsamp, pos0, step) is GPSIQ_E_ARG before anything is launched.  ch is host memory only, as for the
+ * filtered call.  GPSIQ_RESAMPLE_PIECE_BLOCKS=n in the environment, read per call, sets the blocks per piece (default: about 32 MiB of
+ * rendered stream).  *clipped (may be NULL) is the sum over the pieces. */
+int gpsiq_resample(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head /* may be NULL */,
+                   const int16_t *taps /* host [2^log2_phases + 1][ntaps] */, int log2_phases, int ntaps, int shift, int interp,
+                   uint64_t step, uint64_t pos0, int out_sample_size, void *dst, void *hip_stream,
+                   uint64_t *nout /* may be NULL */, uint64_t *next_pos /* may be NULL */, uint64_t *clipped /* may be NULL */,
+                   float *kernel_ms /* may be NULL */);
+int gpsiq_resample_span(uint64_t nsamp, uint64_t pos0, uint64_t step, uint64_t *nout, uint64_t *next_pos);     /* host arithmetic */
+int gpsiq_resample_step(double fs_in, double fs_out, double ppb, uint64_t *step);                             /* host arithmetic */
+int gpsiq_resample_design(uint64_t step, double bandwidth, int log2_phases, int ntaps, int shift, int16_t *taps);   /* host arithmetic */
+int gpsiq_generate_batch_resampled(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+                                   const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step, uint64_t pos0,
+                                   int out_sample_size, void *dst_host, uint64_t dst_capacity /* samples */, uint64_t *nout,
+                                   uint64_t *clipped, double *carr_phase_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -5,7 +5,7 @@
 // chain and the device evaluation, what the translation units above use of each other, and the synthesis kernels by type.  What a
 // stream stage keeps in the context is in that stage's header, included below; HIP_TRY is in gpsiq_own.h.
 //
-// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix):
+// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample):
 //   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
 //   gpsiq_<s>.h                 the stage's member of gpsiq_ctx (resources, reserve()), its kernels by type and their look-ups,
 //                               and `decltype(gpsiq_<s>) gpsiq_<s>_impl;`
@@ -37,6 +37,7 @@
 #include "gpsiq_filter.h"
 #include "gpsiq_spectrum.h"
 #include "gpsiq_mix.h"
+#include "gpsiq_resample.h"
 
 struct gpsiq_ctx {
     template <typename T> using DevBuf = gpsiq::DevBuf<T>;
@@ -171,7 +172,7 @@ struct gpsiq_ctx {
     } evd;
     // the stream stages, each in the header of its name: gpsiq_despread; gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed;
     // gpsiq_acquire; gpsiq_follow; gpsiq_filter / gpsiq_generate_batch_filtered; gpsiq_spectrum;
-    // gpsiq_mix / gpsiq_generate_batch_mixed
+    // gpsiq_mix / gpsiq_generate_batch_mixed; gpsiq_resample / gpsiq_generate_batch_resampled
     gpsiq::DespreadSet dsp;
     gpsiq::PackSet     pack;
     gpsiq::AcquireSet  acq;
@@ -179,6 +180,7 @@ struct gpsiq_ctx {
     gpsiq::FilterSet   filt;
     gpsiq::SpectrumSet spec;
     gpsiq::MixSet      mix;
+    gpsiq::ResampleSet rs;
 };
 
 // ---- first use and growth of the chain's and the device evaluation's resources (the rule: reserve_together, gpsiq_own.h) ------

@@ -32,7 +32,8 @@ void *gpsiq_plumbing(const char *name);
  * "acquire" is gpsiq_acquire (ibid., "Acquisition"; csrc/gpsiq_acquire.cpp), likewise, and "follow" is gpsiq_follow (ibid., "Follow";
  * csrc/gpsiq_follow.cpp).  "filter" and "generate_batch_filtered" are gpsiq_filter and gpsiq_generate_batch_filtered (ibid., "Filter";
  * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp).  "mix" and
- * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp). */
+ * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp).  "resample" and
+ * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -215,6 +216,11 @@ int gpsiq_spectrum_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
  * -1: nothing was launched, no call yet, or one that failed), out[1] the grid, out[2] the units of the launch (samples for the generic
  * kernel, 16-byte slots for the row kernel), out[3] the pieces of a batch call (0: not one; a batch call reports its first piece). */
 int gpsiq_mix_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
+/* What the context's last gpsiq_resample / gpsiq_generate_batch_resampled took (csrc/gpsiq_resample_plan.h): out[0] the kernel (0 generic,
+ * 1 rows; -1: nothing was launched, or no call yet), out[1] the grid, out[2] the outputs of a unit (a run of the row kernel, a
+ * workgroup's threads for the generic one), out[3] the pieces of a batch call (0: not one; a batch call reports the plan of its first
+ * piece). */
+int gpsiq_resample_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
 
 #ifdef __cplusplus
 }

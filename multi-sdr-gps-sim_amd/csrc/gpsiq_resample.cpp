@@ -1,0 +1,236 @@
+// gpsiq_resample.cpp -- host side of gpsiq_resample and gpsiq_generate_batch_resampled (include/gpsiq_rows.h, "Resample"): checks,
+// plan (gpsiq_resample_plan.h, pure and pinned on the CPU), the tap table on its way to the device, kernel look-up
+// (gpsiq_resample_kernels.hip holds the kernels and the table of those that exist), launch, count, and the batch call's pieces.
+// libgpsiq_rows.so exports the typed calls and reaches these through the plumbing entries "resample" and "generate_batch_resampled".
+// Host code: nothing here decides device code, so the file is not one of the device sources behind gpsiq_kernels_id().
+#include <cstdlib>
+#include <cstring>
+
+#include "gpsiq_ctx.h"
+#include "gpsiq_resample.h"
+#include "gpsiq_resample_plan.h"
+
+using namespace gpsiq;
+
+namespace {
+
+// what both calls ask of the table, the step and the formats
+int check_table(const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step, uint64_t pos0, int sample_size, int out_sample_size)
+{
+    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
+    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (log2_phases < 0 || log2_phases > kRsMaxLog2Phases) return fail(GPSIQ_E_ARG, "log2_phases %d outside 0..%d", log2_phases, kRsMaxLog2Phases);
+    if (ntaps < 1 || ntaps > kRsMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kRsMaxTaps);
+    const int rows = (1 << log2_phases) + 1;
+    if (rows * ntaps > kRsMaxTable) return fail(GPSIQ_E_ARG, "%d rows of %d taps: more than %d entries", rows, ntaps, kRsMaxTable);
+    if (shift < 0 || shift > kRsMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kRsMaxShift);
+    if (interp != 0 && interp != 1) return fail(GPSIQ_E_ARG, "interp %d: 0 or 1", interp);
+    if (step < kRsMinStep || step > kRsMaxStep) return fail(GPSIQ_E_ARG, "step %llu outside 2^29..2^35", (unsigned long long) step);
+    if (pos0 >= kRsMaxPos) return fail(GPSIQ_E_ARG, "pos0 %llu: 2^63 or more", (unsigned long long) pos0);
+    if (!taps) return fail(GPSIQ_E_ARG, "null taps");
+    for (int r = 0; r < rows; ++r) {
+        long mag = 0;
+        for (int k = 0; k < ntaps; ++k) { const long t = taps[(size_t) r * (size_t) ntaps + (size_t) k]; mag += t < 0 ? -t : t; }
+        if (mag > kRsTapSum) return fail(GPSIQ_E_RANGE, "row %d: sum |taps| %ld above %ld: the accumulator would not hold the sum", r, mag, kRsTapSum);
+    }
+    return GPSIQ_OK;
+}
+
+int forced_kernel()
+{
+    const char *env = std::getenv("GPSIQ_RESAMPLE_KERNEL");
+    if (!env) return kRsAuto;
+    return !std::strcmp(env, "generic") ? kRsForceGeneric : !std::strcmp(env, "rows") ? kRsForceRows : kRsAuto;
+}
+
+void note_plan(gpsiq_ctx *c, const ResamplePlan &p, long long pieces)
+{
+    c->rs.last[0] = p.launch ? (long long) p.kernel : -1; c->rs.last[1] = (long long) p.grid; c->rs.last[2] = (long long) p.run; c->rs.last[3] = pieces;
+}
+
+// The table of a call, page-locked, then queued for the device on s.  The caller has made sure nothing queued earlier still reads
+// h_taps (every call ends synchronised).
+int stage_table(gpsiq_ctx *c, const int16_t *taps, int log2_phases, int ntaps, hipStream_t s)
+{
+    ResampleSet &k = c->rs;
+    const size_t entries = (size_t) ((1 << log2_phases) + 1) * (size_t) ntaps;
+    std::memcpy(k.h_taps.get(), taps, entries * sizeof(int16_t));
+    HIP_TRY(hipMemcpyAsync(k.d_taps.get(), k.h_taps.get(), entries * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    return GPSIQ_OK;
+}
+
+// the resampler queued on s behind its table: the counter is NOT zeroed here (the batch call adds its pieces up)
+int queue_resample(gpsiq_ctx *c, const ResamplePlan &p, int nsamp, int sample_size, const uint8_t *src, const uint8_t *head, int log2_phases, int ntaps,
+                   int shift, int interp, uint64_t step, uint64_t pos0, int out_sample_size, uint8_t *dst, hipStream_t s)
+{
+    ResampleSet &k = c->rs;
+    if (p.kernel == kRsRows) {
+        const ResampleRowsFn kernel = resample_rows_kernel(sample_size, out_sample_size, p.pad);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no row resampler kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const int16_t *) k.d_taps.get(), log2_phases, ntaps, shift, interp,
+                           step, pos0, dst, p.nout, p.run, p.runs, k.d_count.get());
+    } else {
+        const ResampleGenericFn kernel = resample_generic_kernel(sample_size, out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no resampler kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const int16_t *) k.d_taps.get(), log2_phases, ntaps, shift, interp,
+                           step, pos0, dst, p.nout, p.runs, k.d_count.get());
+    }
+    HIP_TRY(hipGetLastError());
+    return GPSIQ_OK;
+}
+
+bool overlap(const void *a, size_t alen, const void *b, size_t blen)
+{
+    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
+}
+
+}  // namespace
+
+int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, const void *head, const int16_t *taps, int log2_phases, int ntaps,
+                        int shift, int interp, uint64_t step, uint64_t pos0, int out_sample_size, void *dst, void *hip_stream, uint64_t *nout,
+                        uint64_t *next_pos, uint64_t *clipped, float *kernel_ms)
+{
+    if (!c) return fail(GPSIQ_E_ARG, "null context");
+    if (int rc = check_table(taps, log2_phases, ntaps, shift, interp, step, pos0, sample_size, out_sample_size)) return rc;
+    if (nsamp < 0) return fail(GPSIQ_E_ARG, "negative size");
+    const ResamplePlan p = plan_resample((uint64_t) nsamp, log2_phases, ntaps, step, pos0, forced_kernel());
+    if (!src && nsamp) return fail(GPSIQ_E_ARG, "null source");
+    if (!dst && p.nout) return fail(GPSIQ_E_ARG, "null destination");
+    if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
+    if ((uintptr_t) head & 3) return fail(GPSIQ_E_ARG, "head %p not 4-byte aligned", head);
+    if ((uintptr_t) dst & 3) return fail(GPSIQ_E_ARG, "destination %p not 4-byte aligned", dst);
+    const size_t src_len = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, head_len = head ? (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size : 0;
+    const size_t dst_len = (size_t) 2 * (size_t) p.nout * (size_t) out_sample_size;
+    if (overlap(dst, dst_len, src, src_len)) return fail(GPSIQ_E_ARG, "source [%p, +%zu) and destination [%p, +%zu) overlap", src, src_len, dst, dst_len);
+    if (overlap(dst, dst_len, head, head_len)) return fail(GPSIQ_E_ARG, "head [%p, +%zu) and destination [%p, +%zu) overlap", head, head_len, dst, dst_len);
+    if (nout) *nout = p.nout;
+    if (next_pos) *next_pos = p.next_pos;
+    if (clipped) *clipped = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    note_plan(c, p, 0);
+    if (!p.launch) return GPSIQ_OK;                                   // no output: nothing to write
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t) hip_stream;
+    ResampleSet &k = c->rs;
+    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = stage_table(c, taps, log2_phases, ntaps, s)) return rc;
+    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
+    HIP_TRY(hipEventRecord(k.t0.get(), s));
+    if (int rc = queue_resample(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), log2_phases, ntaps, shift,
+                                interp, step, pos0, out_sample_size, static_cast<uint8_t *>(dst), s)) return rc;
+    HIP_TRY(hipEventRecord(k.t1.get(), s));
+    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (clipped) *clipped = (uint64_t) k.h_count[0];
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
+    return GPSIQ_OK;
+}
+
+// nothing of the call may still read the staging or write dst when it returns, on any path
+static int drain_resample(gpsiq_ctx *c, int rc)
+{
+    hipError_t e = hipStreamSynchronize(c->rs.rs_stream.get());
+    const hipError_t d = hipStreamSynchronize(c->rs.copy_stream.get());
+    if (e == hipSuccess) e = d;
+    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
+    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "resampled batch: %s", hipGetErrorString(e));
+}
+
+// The piece loop of gpsiq_generate_batch_filtered (gpsiq_filter.cpp) with the resampler in the filter's place.  Piece k is rendered
+// into d_render[k & 1] BEHIND a head region of `hb` bytes (synchronous), the resampler turns head region and piece into d_out[k & 1]
+// on rs_stream, and the samples cross to the host on copy_stream behind it, to where the pieces before ended -- while the calling
+// thread is already in the render of piece k + 1, which uses the other pair.  The history crosses inside the staging as the filtered
+// call's does; the position crosses on the host: piece k + 1 starts at piece k's next_pos, also where piece k gave no output.
+int gpsiq_generate_batch_resampled_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+                                        const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step, uint64_t pos0,
+                                        int out_sample_size, void *dst, uint64_t dst_capacity, uint64_t *nout, uint64_t *clipped, double *carr_phase_out)
+{
+    if (!c || (!ch && nblocks)) return fail(GPSIQ_E_ARG, "null argument");
+    if (int rc = check_table(taps, log2_phases, ntaps, shift, interp, step, pos0, sample_size, out_sample_size)) return rc;
+    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
+    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    uint64_t total = 0, end_pos = 0;
+    resample_span((uint64_t) nblocks * (uint64_t) nsamp, pos0, step, &total, &end_pos);
+    if (dst_capacity < total) return fail(GPSIQ_E_ARG, "room for %llu samples, the call writes %llu", (unsigned long long) dst_capacity, (unsigned long long) total);
+    if (!dst && total) return fail(GPSIQ_E_ARG, "null destination");
+    if (clipped) *clipped = 0;
+    if (nout) *nout = 0;
+    if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
+    // the pieces' first rows are rewritten on the host: ch is host memory
+    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_resampled", nullptr)) return rc;
+    const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, out_sample_bytes = (size_t) 2 * (size_t) out_sample_size;
+    const char *env = std::getenv("GPSIQ_RESAMPLE_PIECE_BLOCKS");
+    const int piece = resample_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
+    const int npieces = (nblocks + piece - 1) / piece;
+    const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
+    const int force = forced_kernel();
+    HIP_TRY(hipSetDevice(c->device));
+    ResampleSet &k = c->rs;
+    const size_t piece_out = (size_t) resample_piece_outputs((uint64_t) piece * (uint64_t) nsamp, step) * out_sample_bytes;
+    if (int rc = k.reserve(hb + blk_bytes * (size_t) piece + 4, piece_out + 4)) return rc;     // (+4: never a request of no bytes)
+    note_plan(c, plan_resample((uint64_t) (nblocks < piece ? nblocks : piece) * (uint64_t) nsamp, log2_phases, ntaps, step, pos0, force), npieces);
+    hipStream_t rs_ = k.rs_stream.get();
+    if (nsamp) {
+        if (int rc = stage_table(c, taps, log2_phases, ntaps, rs_)) return drain_resample(c, rc);
+        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), rs_));
+        if (hb) HIP_TRY(hipMemsetAsync(k.d_render[0].get(), 0, hb, rs_));             // the first block's history
+    }
+    double carr[GPSIQ_MAX_CHAN] = {};
+    uint64_t pos = pos0, done = 0;
+    int rc = GPSIQ_OK;
+    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
+        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, pair = p & 1;
+        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
+        if (p > 0) {
+            k.row.assign(rows, rows + (size_t) nb * nchan);
+            for (int i = 0; i < nchan; ++i)
+                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
+            rows = k.row.data();
+        }
+        if (p >= 2) {                                                 // the pair's last user: piece p - 2
+            const hipError_t e = hipEventSynchronize(k.copied[pair].get());
+            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "resampled batch: %s", hipGetErrorString(e)); break; }
+        }
+        uint8_t *span = k.d_render[pair].get() + hb;
+        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, sample_size, span, 1, carr);
+        if (rc != GPSIQ_OK) break;
+        if (nsamp == 0) continue;
+        const ResamplePlan pl = plan_resample((uint64_t) nb * (uint64_t) nsamp, log2_phases, ntaps, step, pos, force);
+        if (pl.launch) {
+            rc = queue_resample(c, pl, nb * nsamp, sample_size, span, hist ? span - hist : nullptr, log2_phases, ntaps, shift, interp, step, pos,
+                                out_sample_size, k.d_out[pair].get(), rs_);
+            if (rc != GPSIQ_OK) break;
+        }
+        hipError_t e = hipSuccess;
+        if (hist && p + 1 < npieces)                                  // the next piece's history
+            e = hipMemcpyAsync(k.d_render[pair ^ 1].get() + hb - hist, span + blk_bytes * (size_t) nb - hist, hist, hipMemcpyDeviceToDevice, rs_);
+        if (e == hipSuccess) e = hipEventRecord(k.resampled[pair].get(), rs_);
+        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.resampled[pair].get(), 0);
+        if (e == hipSuccess && pl.nout)
+            e = hipMemcpyAsync(static_cast<uint8_t *>(dst) + (size_t) done * out_sample_bytes, k.d_out[pair].get(), (size_t) pl.nout * out_sample_bytes,
+                               hipMemcpyDeviceToHost, k.copy_stream.get());
+        if (e == hipSuccess) e = hipEventRecord(k.copied[pair].get(), k.copy_stream.get());
+        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "resampled batch piece: %s", hipGetErrorString(e));
+        pos = pl.next_pos;
+        done += pl.nout;
+    }
+    if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last resampler
+        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, rs_);
+        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "resampled batch count: %s", hipGetErrorString(e));
+    }
+    rc = drain_resample(c, rc);
+    if (rc != GPSIQ_OK) return rc;
+    if (done != total) return fail(GPSIQ_E_DEVICE, "resampled batch: the pieces gave %llu samples, the span has %llu", (unsigned long long) done, (unsigned long long) total);
+    if (clipped && nsamp) *clipped = (uint64_t) k.h_count[0];
+    if (nout) *nout = total;
+    if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
+    return GPSIQ_OK;
+}
+
+extern "C" int gpsiq_resample_last_plan(const gpsiq_ctx_t *c, long long out[4])
+{
+    if (!c || !out) return fail(GPSIQ_E_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = c->rs.last[i];
+    return GPSIQ_OK;
+}

@@ -172,3 +172,27 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_mixed
     static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_mixed)>("generate_batch_mixed");
     return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, base_gain, tones, ntones, m0, shift, qmax, dst_host, dst_block_stride, clipped, carr_phase_out);
 }
+
+// The resampler runs on the context's device (csrc/gpsiq_resample.cpp) and is exported here like the filter (include/gpsiq_rows.h,
+// "Resample"); gpsiq_resample_span, gpsiq_resample_step and gpsiq_resample_design, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_resample(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head,
+                                                                     const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step,
+                                                                     uint64_t pos0, int out_sample_size, void *dst, void *hip_stream, uint64_t *nout,
+                                                                     uint64_t *next_pos, uint64_t *clipped, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_resample)>("resample");
+    return f(ctx, nsamp, sample_size, src, head, taps, log2_phases, ntaps, shift, interp, step, pos0, out_sample_size, dst, hip_stream, nout, next_pos, clipped,
+             kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_resampled(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan,
+                                                                                     int nsamp, double fs, int sample_size, const int16_t *taps,
+                                                                                     int log2_phases, int ntaps, int shift, int interp, uint64_t step,
+                                                                                     uint64_t pos0, int out_sample_size, void *dst_host,
+                                                                                     uint64_t dst_capacity, uint64_t *nout, uint64_t *clipped,
+                                                                                     double *carr_phase_out)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_resampled)>("generate_batch_resampled");
+    return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, taps, log2_phases, ntaps, shift, interp, step, pos0, out_sample_size, dst_host, dst_capacity, nout,
+             clipped, carr_phase_out);
+}

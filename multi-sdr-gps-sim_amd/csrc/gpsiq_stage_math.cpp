@@ -1,12 +1,14 @@
 // gpsiq_stage_math.cpp -- the plain arithmetic that goes with the noise, the output level and the stream stages (include/gpsiq_rows.h):
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
-// and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix.  Host
-// code of libgpsiq_rows.so; nothing here touches a context or the device (the calls themselves: gpsiq_rows_link.cpp).
+// and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix, the
+// output count, the step and the tap table of a resampler.  Host code of libgpsiq_rows.so; nothing here touches a context or the
+// device (the calls themselves: gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
 #include "gpsiq_spectrum_plan.h"
 #include "gpsiq_mix_geometry.h"
+#include "gpsiq_resample_plan.h"
 
 #include <cmath>
 
@@ -273,6 +275,81 @@ int gpsiq_mix_gain(double amplitude, int kind, int shift, int32_t *gain)
     const double g = std::rint(std::ldexp(amplitude, shift) / (kind == GPSIQ_MIX_STREAM ? 1.0 : 250.0));
     if (!(std::fabs(g) < 2147483648.0)) return fail(GPSIQ_E_RANGE, "a gain of %g does not fit 32 bits: lower the shift", g);
     *gain = (int32_t) g;
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Resample": the outputs of a span and the position its continuation starts at (resample_span,
+// gpsiq_resample_plan.h)
+int gpsiq_resample_span(uint64_t nsamp, uint64_t pos0, uint64_t step, uint64_t *nout, uint64_t *next_pos)
+{
+    if (nsamp >= kRsMaxSpan || pos0 >= kRsMaxPos || step < kRsMinStep || step > kRsMaxStep)
+        return fail(GPSIQ_E_ARG, "nsamp %llu below 2^60, pos0 %llu below 2^63, step %llu in 2^29..2^35", (unsigned long long) nsamp, (unsigned long long) pos0,
+                    (unsigned long long) step);
+    uint64_t n = 0, next = 0;
+    resample_span(nsamp, pos0, step, &n, &next);
+    if (nout) *nout = n;
+    if (next_pos) *next_pos = next;
+    return GPSIQ_OK;
+}
+
+// ibid.: input samples per output sample in units of 2^-32, for a receiver whose clock runs ppb parts per billion fast
+int gpsiq_resample_step(double fs_in, double fs_out, double ppb, uint64_t *step)
+{
+    if (!step) return fail(GPSIQ_E_ARG, "null argument");
+    if (!(fs_in > 0.0) || !std::isfinite(fs_in) || !(fs_out > 0.0) || !std::isfinite(fs_out) || !std::isfinite(ppb) || !(1.0 + ppb * 1e-9 > 0.0))
+        return fail(GPSIQ_E_ARG, "rates %g, %g positive and finite, ppb %g finite and above -1e9", fs_in, fs_out, ppb);
+    const double s = std::rint(std::ldexp(1.0, 32) * fs_in / (fs_out * (1.0 + ppb * 1e-9)));
+    if (!(s >= (double) kRsMinStep && s <= (double) kRsMaxStep)) return fail(GPSIQ_E_RANGE, "%g Hz to %g Hz is a step of %g: outside 2^29..2^35", fs_in, fs_out, s);
+    *step = (uint64_t) s;
+    return GPSIQ_OK;
+}
+
+// ibid.: the rows of a Hamming-windowed sinc at the fractions r / nphases.  Tap k of row r sits at t = n / (2 nphases), n the integer
+// 2 k nphases + 2 r - (ntaps - 1) nphases, and the prototype is evaluated from |n|: mirrored places get the same bits.  The rows above
+// the middle are copied from their mirrors, so the mirror property does not hang on the order of a sum
+int gpsiq_resample_design(uint64_t step, double bandwidth, int log2_phases, int ntaps, int shift, int16_t *taps)
+{
+    if (!taps) return fail(GPSIQ_E_ARG, "null argument");
+    if (log2_phases < 0 || log2_phases > kRsMaxLog2Phases || ntaps < 2 || ntaps > kRsMaxTaps || ((1 << log2_phases) + 1) * ntaps > kRsMaxTable)
+        return fail(GPSIQ_E_ARG, "log2_phases %d in 0..%d, ntaps %d in 2..%d, (nphases + 1) * ntaps at most %d", log2_phases, kRsMaxLog2Phases, ntaps, kRsMaxTaps,
+                    kRsMaxTable);
+    if (shift < 8 || shift > 14) return fail(GPSIQ_E_ARG, "shift %d: 8..14", shift);
+    if (step < kRsMinStep || step > kRsMaxStep || !(bandwidth > 0.0) || !(bandwidth <= 1.0))
+        return fail(GPSIQ_E_ARG, "step %llu in 2^29..2^35, bandwidth %g in (0, 1]", (unsigned long long) step, bandwidth);
+    const double pi = 3.14159265358979323846;
+    const double w = bandwidth * (step > kRsOne ? (double) kRsOne / (double) step : 1.0);           // 2 fc: the cutoff against half the input rate
+    const int nph = 1 << log2_phases;
+    const long edge = (long) (ntaps - 1) * nph;                                                     // |n| at the window's ends
+    for (int r = 0; r <= nph; ++r) {
+        int16_t *row = taps + (size_t) r * (size_t) ntaps;
+        if (r > nph - r && r < nph) {                                                               // the mirror of a row already made
+            const int16_t *m = taps + (size_t) (nph - r) * (size_t) ntaps;
+            for (int k = 0; k + 1 < ntaps; ++k) row[k] = m[ntaps - 2 - k];
+            row[ntaps - 1] = 0;
+            continue;
+        }
+        double g[kRsMaxTaps], sum = 0.0;
+        for (int k = 0; k < ntaps; ++k) {
+            long n = 2L * k * nph + 2L * r - edge;
+            if (n < 0) n = -n;
+            const double t = (double) n / (double) (2 * nph), x = w * t;
+            g[k] = n > edge ? 0.0 : (n ? std::sin(pi * x) / (pi * x) : 1.0) * (0.54 + 0.46 * std::cos(2.0 * pi * t / (double) (ntaps - 1)));
+            sum += g[k];
+        }
+        if (!(sum > 0.0)) return fail(GPSIQ_E_RANGE, "row %d of the design sums to %g", r, sum);
+        const double scale = std::ldexp(1.0, shift) / sum;
+        long q[kRsMaxTaps], total = 0, mag = 0;
+        int big = 0;
+        for (int k = 0; k < ntaps; ++k) {
+            q[k] = std::lrint(g[k] * scale);
+            total += q[k];
+            if (q[k] > q[big]) big = k;                                                             // the first of equals stays
+        }
+        q[big] += (1L << shift) - total;                                                            // the remainder of the rounding
+        for (int k = 0; k < ntaps; ++k) mag += q[k] < 0 ? -q[k] : q[k];
+        if (mag > kRsTapSum || q[big] > 32767) return fail(GPSIQ_E_RANGE, "row %d outside the resampler's range (sum |taps| %ld)", r, mag);
+        for (int k = 0; k < ntaps; ++k) row[k] = (int16_t) q[k];
+    }
     return GPSIQ_OK;
 }
 

@@ -185,6 +185,15 @@ _mix_gain = _sig("gpsiq_mix_gain", _i, _d, _i, _i, C.POINTER(C.c_int32))
 _generate_batch_mixed = _sig("gpsiq_generate_batch_mixed", _i, _vp, _vp, _i, _i, _i, _d, _i, C.c_int32, _vp, _i, C.c_uint64, _i, _i, _vp, _sz,
                              C.POINTER(C.c_uint64), _vp)
 _mix_last_plan = _sig("gpsiq_mix_last_plan", _i, _vp, _vp)
+_u64 = C.c_uint64
+_resample = _sig("gpsiq_resample", _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _u64, _u64, _i, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64),
+                 C.POINTER(_u64), C.POINTER(C.c_float))
+_resample_span = _sig("gpsiq_resample_span", _i, _u64, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64))
+_resample_step = _sig("gpsiq_resample_step", _i, _d, _d, _d, C.POINTER(_u64))
+_resample_design = _sig("gpsiq_resample_design", _i, _u64, _d, _i, _i, _i, _vp)
+_generate_batch_resampled = _sig("gpsiq_generate_batch_resampled", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _u64, _u64, _i, _vp, _u64,
+                                 C.POINTER(_u64), C.POINTER(_u64), _vp)
+_resample_last_plan = _sig("gpsiq_resample_last_plan", _i, _vp, _vp)
 
 
 class NoiseSettings(C.Structure):
@@ -762,6 +771,37 @@ def filter_design(fs, cutoff_hz, ntaps, shift=14):
     return taps
 
 
+def _u64_arg(v, what):
+    v = int(v)
+    if not 0 <= v < 2 ** 64:
+        raise GpsiqError(-1, f"{what} {v} does not fit 64 unsigned bits")
+    return v
+
+
+def resample_span(nsamp, pos0, step):
+    """gpsiq_resample_span: (outputs of a span of nsamp samples from position pos0 at `step` input samples an output, the position its
+    continuation starts at); positions and steps in units of 2**-32 input sample."""
+    nout, nxt = _u64(0), _u64(0)
+    _check(_resample_span(_u64_arg(nsamp, "nsamp"), _u64_arg(pos0, "pos0"), _u64_arg(step, "step"), C.byref(nout), C.byref(nxt)))
+    return int(nout.value), int(nxt.value)
+
+
+def resample_step(fs_in, fs_out, ppb=0.0):
+    """gpsiq_resample_step: the step from a stream at fs_in to a receiver at fs_out whose clock runs ppb parts per billion fast."""
+    step = _u64(0)
+    _check(_resample_step(float(fs_in), float(fs_out), float(ppb), C.byref(step)))
+    return int(step.value)
+
+
+def resample_design(step, bandwidth=0.8, log2_phases=7, ntaps=16, shift=14):
+    """gpsiq_resample_design: int16 taps [2**log2_phases + 1][ntaps] of a Hamming-windowed sinc at every phase, its cutoff at
+    `bandwidth` of the lower of the two Nyquist rates, every row summing to 2**shift."""
+    rows = (1 << min(max(int(log2_phases), 0), 8)) + 1
+    taps = np.zeros((rows, max(int(ntaps), 1)), dtype=np.int16)
+    _check(_resample_design(_u64_arg(step, "step"), float(bandwidth), int(log2_phases), int(ntaps), int(shift), _p(taps)))
+    return taps
+
+
 def spectrum_span(nsamp, nfft, hop=None, navg=1):
     """gpsiq_spectrum_span: (segments of nfft samples, hop apart, in a span of nsamp samples; whole groups of navg of them)."""
     nseg, ngroups = _i(0), _i(0)
@@ -1178,6 +1218,49 @@ class Context:
         """What the last mix() / generate_batch_mixed() took: (kernel name or None, grid, units of the launch, pieces)."""
         out = (C.c_longlong * 4)()
         _check(_mix_last_plan(self._h, out))
+        return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def resample(self, nsamp, sample_size, device_ptr, taps, log2_phases, shift, interp, step, pos0, out_sample_size, dst_device_ptr, head_ptr=None,
+                 stream=None):
+        """gpsiq_resample: the nsamp complex samples at device_ptr resampled at positions pos0 + j * step (2**-32 input sample) through the
+        table `taps` (int16 [2**log2_phases + 1][ntaps], host), rounded by `shift`, clamped into out_sample_size at dst_device_ptr;
+        head_ptr: the ntaps - 1 samples before the span (None: zeros) -> (outputs written, next position, elements the clamp changed,
+        kernel milliseconds)."""
+        taps = np.ascontiguousarray(taps, dtype=np.int16)
+        ntaps = taps.shape[-1] if taps.ndim == 2 else 0
+        nout, nxt, clipped, ms = _u64(0), _u64(0), _u64(0), C.c_float(0.0)
+        _check(_resample(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(head_ptr or 0), _p(taps) if taps.size else None, int(log2_phases),
+                         int(ntaps), int(shift), int(interp), _u64_arg(step, "step"), _u64_arg(pos0, "pos0"), int(out_sample_size),
+                         _vp(dst_device_ptr), _vp(stream or 0), C.byref(nout), C.byref(nxt), C.byref(clipped), C.byref(ms)))
+        return int(nout.value), int(nxt.value), int(clipped.value), float(ms.value)
+
+    def generate_batch_resampled(self, desc, nsamp, fs, sample_size, taps, log2_phases, shift, interp, step, pos0, out_sample_size, host_ptr=None,
+                                 capacity=None, carr_out=None):
+        """gpsiq_generate_batch_resampled: the run-ahead call rendered at sample_size and resampled on the device into ONE stream of
+        out_sample_size in host memory.  Returns (int8 / int16 [nout][2], elements the clamp changed), with the count in the array's
+        place when host_ptr names the caller's buffer of `capacity` samples (pageable or page-locked)."""
+        desc = np.ascontiguousarray(desc, dtype=CHAN_DTYPE)
+        taps = np.ascontiguousarray(taps, dtype=np.int16)
+        ntaps = taps.shape[-1] if taps.ndim == 2 else 0
+        nb, nc = desc.shape
+        co = None if carr_out is None else _p(carr_out)
+        nout, clipped = _u64(0), _u64(0)
+        out = None
+        if host_ptr is None:
+            capacity = resample_span(nb * int(nsamp), pos0, step)[0] if capacity is None else int(capacity)
+            out = np.zeros((max(capacity, 1), 2), dtype=np.int8 if int(out_sample_size) == 1 else np.int16)
+        _check(_generate_batch_resampled(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(sample_size), _p(taps) if taps.size else None,
+                                         int(log2_phases), int(ntaps), int(shift), int(interp), _u64_arg(step, "step"), _u64_arg(pos0, "pos0"),
+                                         int(out_sample_size), _vp(host_ptr) if out is None else _p(out), _u64_arg(capacity, "capacity"), C.byref(nout),
+                                         C.byref(clipped), co))
+        if out is None:
+            return int(nout.value), int(clipped.value)
+        return out[:int(nout.value)], int(clipped.value)
+
+    def resample_last_plan(self):
+        """What the last resample() / generate_batch_resampled() took: (kernel name or None, grid, outputs of a unit, pieces)."""
+        out = (C.c_longlong * 4)()
+        _check(_resample_last_plan(self._h, out))
         return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def pack_last_plan(self):

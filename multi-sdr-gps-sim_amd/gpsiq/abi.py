@@ -16,6 +16,9 @@ SPECTRUM_NFFT, SPECTRUM_MAX_SHIFT = (64, 128, 256, 512), 40
 # gpsiq_mix (include/gpsiq_rows.h, "Mix"): the kinds of a term, the terms of a call and the largest shift
 MIX_STREAM, MIX_ROTATED, MIX_TONE = 0, 1, 2
 MIX_MAX_TERMS, MIX_MAX_SHIFT = 8, 40
+# gpsiq_resample (include/gpsiq_rows.h, "Resample"): the ranges of its arguments; positions and steps are in units of 2**-32 input sample
+RESAMPLE_MAX_TAPS, RESAMPLE_MAX_LOG2_PHASES, RESAMPLE_MAX_SHIFT, RESAMPLE_MAX_TABLE, RESAMPLE_TAP_SUM = 64, 8, 16, 8256, 65535
+RESAMPLE_ONE, RESAMPLE_MIN_STEP, RESAMPLE_MAX_STEP = 1 << 32, 1 << 29, 1 << 35
 SINK_IQFILE, SINK_HACKRF, SINK_PLUTOSDR = 1, 2, 3
 HACKRF_CHUNK = 262144
 

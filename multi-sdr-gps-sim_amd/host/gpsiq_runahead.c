@@ -16,6 +16,7 @@
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
  *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
  *                  [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]...
+ *                  [--resample fs_out[,ppb]]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -68,6 +69,13 @@
  * index of the run, clamped to --qmax (or the format's largest value) and the clamped elements counted and printed.  J/S is relative to
  * a satellite of descriptor gain 1: amplitude 250, or 250 * mult / 65536 with --level (gpsiq_mix_gain has the units).  Not with --pack or
  * --filter.
+ * Resample (optional, same place): --resample <fs_out>[,<ppb>] renders at <fs> and writes the stream at <fs_out>, as a receiver samples it
+ * whose clock runs <ppb> parts per billion fast (default 0), in the run's own sample size, through gpsiq_generate_batch_resampled
+ * (include/gpsiq_rows.h, "Resample") at the step of gpsiq_resample_step(fs, fs_out, ppb) with the table of gpsiq_resample_design(step,
+ * 0.8, 7, 16, 14): 128 phases of 16 taps, interpolated between.  The ratio lies in [1/8, 8].  The output is one stream without block
+ * structure; the position runs on from call to call of the library, and every call starts from a history of zeros, as with --filter.
+ * The samples written and the elements the clamp changed are printed.  Not with --pack, --filter, --tone, --acquire, --follow or
+ * --spectrum.
  */
 #include <math.h>
 #include <stdint.h>
@@ -270,6 +278,11 @@ static int run_follow(gpsiq_ctx_t *gq, const void *stream, int span, int ss, dou
 /* --tone f_hz,js_db[,f1_hz,sweep_s]: the integers of gpsiq_mix_tone at fs and the J/S; nonzero for a value the flag refuses */
 #define MAX_TONES 4
 #define TONE_SHIFT 8
+/* --resample: the designed table */
+#define RESAMPLE_LOG2_PHASES 7
+#define RESAMPLE_PHASES (1 << RESAMPLE_LOG2_PHASES)
+#define RESAMPLE_TAPS 16
+#define RESAMPLE_SHIFT 14
 struct tone { int64_t step, rate; uint32_t period; double js_db; };
 static int parse_tone(const char *arg, double fs, struct tone *t)
 {
@@ -299,12 +312,14 @@ int main(int argc, char **argv)
     int spectrum = 0, spec_nfft = 0;
     const char *tone_arg[MAX_TONES + 1];
     int ntone = 0;
+    const char *resample_arg = NULL;
+    int resample = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
                         strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0 ||
                         strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0 ||
-                        strcmp(argv[argc - 2], "--spectrum") == 0 || strcmp(argv[argc - 2], "--tone") == 0))) break;
+                        strcmp(argv[argc - 2], "--spectrum") == 0 || strcmp(argv[argc - 2], "--tone") == 0 || strcmp(argv[argc - 2], "--resample") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
@@ -314,6 +329,7 @@ int main(int argc, char **argv)
         else if (strcmp(argv[argc - 2], "--taps") == 0) { ftaps = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--decim") == 0) { fdecim = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--spectrum") == 0) { spec_nfft = atoi(argv[argc - 1]); spectrum = 1; }
+        else if (strcmp(argv[argc - 2], "--resample") == 0) { resample_arg = argv[argc - 1]; ++resample; }
         else if (strcmp(argv[argc - 2], "--tone") == 0) { if (ntone <= MAX_TONES) tone_arg[ntone] = argv[argc - 1]; ++ntone; }
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
@@ -338,8 +354,18 @@ int main(int argc, char **argv)
     struct tone tone[MAX_TONES];
     int tone_bad = ntone > MAX_TONES || (ntone && (pack_given || filter));
     for (int k = 0; k < ntone && !tone_bad; ++k) tone_bad = parse_tone(tone_arg[ntone - 1 - k], fs_arg, &tone[k]);     /* (read from the end: as given) */
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad || tone_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]...\n"
+    /* --resample: once, fs_out[,ppb] with a step gpsiq_resample_step accepts at this fs; on its own */
+    uint64_t rs_step = 0;
+    double rs_fs = 0.0, rs_ppb = 0.0;
+    int resample_bad = resample > 1 || (resample && (pack_given || filter || fopts || ntone || acquire || follow || spectrum));
+    if (resample == 1 && !resample_bad) {
+        char extra;
+        const int n = sscanf(resample_arg, "%lf,%lf%c", &rs_fs, &rs_ppb, &extra);
+        resample_bad = (n != 1 && n != 2) || (n == 1 && strchr(resample_arg, ',')) || !(fs_arg > 0.0) ||
+                       gpsiq_resample_step(fs_arg, rs_fs, rs_ppb, &rs_step) != GPSIQ_OK;
+    }
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad || tone_bad || resample_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]... [--resample fs_out[,ppb]]\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
                         "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
                         "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n"
@@ -347,7 +373,9 @@ int main(int argc, char **argv)
                         "                not with --pack, --acquire or --follow\n"
                         "       --spectrum needs 64, 128, 256 or 512; not with --pack\n"
                         "       --tone (up to four) needs f,J/S or f0,J/S,f1,sweep: frequencies inside (-fs/2, fs/2), a sweep of 2 samples or more;\n"
-                        "              not with --pack or --filter\n", argv[0]);
+                        "              not with --pack or --filter\n"
+                        "       --resample needs a rate between fs/8 and 8 fs and, behind a comma, a clock offset in parts per billion; once, and\n"
+                        "              not with --pack, --filter, --tone, --acquire, --follow or --spectrum\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -430,7 +458,15 @@ int main(int argc, char **argv)
     static int16_t taps[511];
     uint64_t filter_clipped = 0;
     if (filter && gpsiq_filter_design(fs, filter_hz, ftaps, 14, taps) != GPSIQ_OK) return die("filter design");
-    void *buf = gpsiq_host_alloc(blk_bytes * BLOCKS_PER_CALL);
+    /* --resample: the table, and room for the most samples a call of BLOCKS_PER_CALL blocks can give */
+    static int16_t rs_taps[(RESAMPLE_PHASES + 1) * RESAMPLE_TAPS];
+    uint64_t rs_pos = 0, rs_room = 0, rs_written = 0, rs_clipped = 0;
+    if (resample) {
+        if (gpsiq_resample_design(rs_step, 0.8, RESAMPLE_LOG2_PHASES, RESAMPLE_TAPS, RESAMPLE_SHIFT, rs_taps) != GPSIQ_OK) return die("resample design");
+        if (gpsiq_resample_span((uint64_t) BLOCKS_PER_CALL * (uint64_t) nsamp, 0, rs_step, &rs_room, NULL) != GPSIQ_OK) return die("resample span");
+        rs_room += 1;
+    }
+    void *buf = gpsiq_host_alloc(resample ? (size_t) rs_room * 2 * (size_t) ss : blk_bytes * BLOCKS_PER_CALL);
     gpsiq_chan_t *desc = malloc(sizeof *desc * BLOCKS_PER_CALL * (size_t) nchan);
     FILE *fo = fopen(argv[10], "wb");
     if (!buf || !desc || !fo) { fprintf(stderr, "cannot allocate / open output\n"); return 1; }
@@ -471,6 +507,17 @@ int main(int argc, char **argv)
                 if (gpsiq_generate_batch_filtered(gq, desc, nb, nchan, nsamp, fs, ss, taps, ftaps, 14, fdecim, ss, buf, blk_bytes, &clipped, carr) != GPSIQ_OK)
                     return die("generate filtered");
                 filter_clipped += clipped;
+            } else if (resample) {
+                uint64_t clipped = 0, nout = 0, next = 0;
+                if (gpsiq_generate_batch_resampled(gq, desc, nb, nchan, nsamp, fs, ss, rs_taps, RESAMPLE_LOG2_PHASES, RESAMPLE_TAPS, RESAMPLE_SHIFT, 1, rs_step,
+                                                   rs_pos, ss, buf, rs_room, &nout, &clipped, carr) != GPSIQ_OK) return die("generate resampled");
+                if (gpsiq_resample_span((uint64_t) nb * (uint64_t) nsamp, rs_pos, rs_step, NULL, &next) != GPSIQ_OK) return die("resample span");
+                rs_pos = next;                                                 /* the next call's first output, from its first sample */
+                rs_clipped += clipped;
+                rs_written += nout;
+                if (fwrite(buf, (size_t) 2 * (size_t) ss, (size_t) nout, fo) != (size_t) nout) { fprintf(stderr, "short write\n"); return 1; }
+                have_carr = 1;
+                continue;
             } else if (ntone) {
                 if (!tones_set) {                                              /* once: J/S against a satellite of descriptor gain 1 */
                     const double unit = level_mult ? 250.0 * (double) level_mult / 65536.0 : 250.0;
@@ -527,6 +574,9 @@ int main(int argc, char **argv)
     fclose(fo);
     printf("%d blocks, %d channels, %d allocation passes, last nsat %d, ephemeris set %d of %d\n", nblocks, nchan, nalloc, nsat, h.ieph, nsets);
     if (filter) printf("filter: cutoff %g Hz, %d taps, decimation %d, %llu elements clipped\n", filter_hz, ftaps, fdecim, (unsigned long long) filter_clipped);
+    if (resample)
+        printf("resample: %g Hz to %g Hz at %g ppb, step %llu / 2^32, %llu samples written, %llu elements clipped\n", fs, rs_fs, rs_ppb,
+               (unsigned long long) rs_step, (unsigned long long) rs_written, (unsigned long long) rs_clipped);
     if (ntone) printf("tones: %d, %llu elements clipped\n", ntone, (unsigned long long) tone_clipped);
     gpsiq_host_free(buf);
     gpsiq_destroy(gq);
