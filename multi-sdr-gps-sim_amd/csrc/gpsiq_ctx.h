@@ -3,7 +3,8 @@
 // gpsiq_multi.cpp (gpsiq_generate_batch_multi) and gpsiq_evaldev.cpp (the batch calls whose descriptors are quantised / evaluated
 // on the device), and by the host side of every stream stage.  This header keeps the context itself, the first-use routines of the
 // chain and the device evaluation, what the translation units above use of each other, and the synthesis kernels by type.  What a
-// stream stage keeps in the context is in that stage's header, included below; HIP_TRY is in gpsiq_own.h.
+// stream stage keeps in the context is in that stage's header, included below; what the staged batch calls share (the staging ring
+// and the piece loop) is in gpsiq_stage_batch.h; HIP_TRY is in gpsiq_own.h.
 //
 // The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample):
 //   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
@@ -30,6 +31,7 @@
 #include "gpsiq_noise.h"
 #include "gpsiq_own.h"
 #include "gpsiq_pieces.h"
+#include "gpsiq_stage_batch.h"
 #include "gpsiq_despread.h"
 #include "gpsiq_pack.h"
 #include "gpsiq_acquire.h"
@@ -181,6 +183,9 @@ struct gpsiq_ctx {
     gpsiq::SpectrumSet spec;
     gpsiq::MixSet      mix;
     gpsiq::ResampleSet rs;
+    // the staging the four staged batch calls (_packed, _filtered, _mixed, _resampled) work through their pieces with: one ring for
+    // all of them -- calls on a context are serial and every one ends with the ring's streams drained (gpsiq_stage_batch.h)
+    gpsiq::PieceRing   ring;
 };
 
 // ---- first use and growth of the chain's and the device evaluation's resources (the rule: reserve_together, gpsiq_own.h) ------

@@ -97,12 +97,6 @@ int queue_filter(gpsiq_ctx *c, const FilterPlan &p, int nsamp, int sample_size, 
     return GPSIQ_OK;
 }
 
-bool overlap(const void *a, size_t alen, const void *b, size_t blen)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
-}
-
 }  // namespace
 
 int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, const void *head, const int16_t *taps, int ntaps, int shift, int decim,
@@ -131,7 +125,7 @@ int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *sr
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     FilterSet &k = c->filt;
-    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = k.reserve()) return rc;
     if (int rc = stage_coefficients(c, taps, ntaps, decim, p, s)) return rc;
     HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
     HIP_TRY(hipEventRecord(k.t0.get(), s));
@@ -145,25 +139,10 @@ int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *sr
     return GPSIQ_OK;
 }
 
-// nothing of the call may still read the staging or write dst when it returns, on any path
-static int drain_filter(gpsiq_ctx *c, int rc)
-{
-    hipError_t e = hipStreamSynchronize(c->filt.filt_stream.get());
-    const hipError_t d = hipStreamSynchronize(c->filt.copy_stream.get());
-    if (e == hipSuccess) e = d;
-    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
-    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "filtered batch: %s", hipGetErrorString(e));
-}
-
-// Piece k: gpsiq_generate_batch renders its blocks back to back into d_render[k & 1] BEHIND a head region of `hb` bytes (synchronous),
-// the filter turns head region and piece into d_out[k & 1] on filt_stream, the rows cross to the host on copy_stream behind it --
-// while the calling thread is already in the render of piece k + 1, which uses the other pair.  The history crosses inside the
-// staging: behind the filter of piece k, on filt_stream, the last ntaps - 1 samples of [head region | piece k] are copied to the end
-// of the other pair's head region -- right for a piece shorter than the history too, whose own head region then supplies the rest;
-// the first piece's head region is zeros.  Piece k + 2 takes pair k & 1 again once `copied` of piece k has been reached, which lies
-// behind `filtered` of piece k and with it behind that copy.  Every piece is a whole number of blocks and nsamp a multiple of
-// decim: the phase is 0 at every piece, and a piece's outputs are its blocks' rows back to back.
-// The pieces are chained as gpsiq_generate_batch_packed chains them (gpsiq_pack.cpp).
+// The pieces of gpsiq_stage_batch.h with the filter as the stage: a piece is rendered BEHIND a lead region of `hb` bytes whose last
+// `hist` bytes are the ntaps - 1 samples before it, and the filter turns lead region and piece into d_out[pair].  The first piece's
+// history is zeros, written per call.  Every piece is a whole number of blocks and nsamp a multiple of decim: the phase is 0 at every
+// piece, and a piece's outputs are its blocks' rows back to back.
 int gpsiq_generate_batch_filtered_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                                        const int16_t *taps, int ntaps, int shift, int decim, int out_sample_size, void *dst, size_t dst_block_stride,
                                        uint64_t *clipped, double *carr_phase_out)
@@ -179,64 +158,35 @@ int gpsiq_generate_batch_filtered_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, i
     if (dst_block_stride < row_bytes) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
     if (clipped) *clipped = 0;
     if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
-    // the pieces' first rows are rewritten on the host: ch is host memory
-    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_filtered", nullptr)) return rc;
     const char *env = std::getenv("GPSIQ_FILTER_PIECE_BLOCKS");
     const int piece = filter_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
-    const int npieces = (nblocks + piece - 1) / piece;
     const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
     const int force = forced_kernel();
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_filtered", ch, hb + blk_bytes * (size_t) piece + 4, row_bytes * (size_t) piece + 4)) return rc;     // (+4: never a request of no bytes)
     FilterSet &k = c->filt;
-    if (int rc = k.reserve(hb + blk_bytes * (size_t) piece + 4, row_bytes * (size_t) piece + 4)) return rc;     // (+4: never a request of no bytes)
+    if (int rc = k.reserve()) return rc;
+    const StageBatch stage = {"filtered batch", sample_size, hb, hist, piece, k.d_count.get(), k.h_count.get()};
     const FilterPlan whole = plan_filter(piece * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
-    note_plan(c, whole, npieces);
-    hipStream_t fs_ = k.filt_stream.get();
-    if (nsamp) {
+    note_plan(c, whole, (nblocks + piece - 1) / piece);
+    const hipStream_t ss = c->ring.stage_stream.get();
+    const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
         // one kernel for every piece (the choice does not look at the length), so one set of coefficients, queued once
-        if (int rc = stage_coefficients(c, taps, ntaps, decim, whole, fs_)) return drain_filter(c, rc);
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), fs_));
-        if (hb) HIP_TRY(hipMemsetAsync(k.d_render[0].get(), 0, hb, fs_));            // the first block's history
-    }
+        if (int rc = stage_coefficients(c, taps, ntaps, decim, whole, ss)) return rc;
+        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        if (hb) HIP_TRY(hipMemsetAsync(c->ring.d_render[0].get(), 0, hb, ss));       // the first block's history
+        return GPSIQ_OK;
+    }();
     double carr[GPSIQ_MAX_CHAN] = {};
-    int rc = GPSIQ_OK;
-    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
-        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, pair = p & 1;
-        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
-        if (p > 0) {
-            k.row.assign(rows, rows + (size_t) nb * nchan);
-            for (int i = 0; i < nchan; ++i)
-                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
-            rows = k.row.data();
-        }
-        if (p >= 2) {                                                 // the pair's last user: piece p - 2
-            const hipError_t e = hipEventSynchronize(k.copied[pair].get());
-            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "filtered batch: %s", hipGetErrorString(e)); break; }
-        }
-        uint8_t *span = k.d_render[pair].get() + hb;
-        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, sample_size, span, 1, carr);
-        if (rc != GPSIQ_OK) break;
-        if (nsamp == 0) continue;
-        const FilterPlan pl = plan_filter(nb * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
-        rc = queue_filter(c, pl, nb * nsamp, sample_size, span, hist ? span - hist : nullptr, ntaps, shift, decim, 0, out_sample_size, k.d_out[pair].get(), fs_);
-        if (rc != GPSIQ_OK) break;
-        hipError_t e = hipSuccess;
-        if (hist && p + 1 < npieces)                                  // the next piece's history
-            e = hipMemcpyAsync(k.d_render[pair ^ 1].get() + hb - hist, span + blk_bytes * (size_t) nb - hist, hist, hipMemcpyDeviceToDevice, fs_);
-        if (e == hipSuccess) e = hipEventRecord(k.filtered[pair].get(), fs_);
-        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.filtered[pair].get(), 0);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * dst_block_stride, dst_block_stride, k.d_out[pair].get(),
-                                                  row_bytes, row_bytes, (size_t) nb, hipMemcpyDeviceToHost, k.copy_stream.get());
-        if (e == hipSuccess) e = hipEventRecord(k.copied[pair].get(), k.copy_stream.get());
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "filtered batch piece: %s", hipGetErrorString(e));
-    }
-    if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last filter
-        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, fs_);
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "filtered batch count: %s", hipGetErrorString(e));
-    }
-    rc = drain_filter(c, rc);
+    uint64_t clamped = 0;
+    const int rc = gpsiq_stage_batch_run(c, stage, rc0, ch, nblocks, nchan, nsamp, fs, [&](const Piece &pc, PieceCopy *cp) -> int {
+        uint8_t *out = c->ring.d_out[pc.pair].get();
+        const FilterPlan pl = plan_filter(pc.nb * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
+        if (int rq = queue_filter(c, pl, pc.nb * nsamp, sample_size, pc.span, hist ? pc.span - hist : nullptr, ntaps, shift, decim, 0, out_sample_size, out, ss)) return rq;
+        *cp = {out, row_bytes, row_bytes, (size_t) pc.nb, static_cast<uint8_t *>(dst) + (size_t) pc.b0 * dst_block_stride, dst_block_stride};
+        return GPSIQ_OK;
+    }, carr, &clamped);
     if (rc != GPSIQ_OK) return rc;
-    if (clipped && nsamp) *clipped = (uint64_t) k.h_count[0];
+    if (clipped) *clipped = clamped;
     if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
     return GPSIQ_OK;
 }

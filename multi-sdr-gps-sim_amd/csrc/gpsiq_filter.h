@@ -4,8 +4,6 @@
 #ifndef GPSIQ_FILTER_H
 #define GPSIQ_FILTER_H
 
-#include <vector>
-
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
 #include "gpsiq_filter_geometry.h"
@@ -13,37 +11,25 @@
 namespace gpsiq {
 
 // the coefficients of a call on the device and page-locked on their way there (the taps as dwords, then the matrix kernel's digit
-// planes: one size, the largest a call can ask for), the counter of clamped elements and its page-locked twin, the two events a kernel
-// is timed with, and what the batch call works through its pieces with -- two rendered and two filtered staging buffers taken in
-// turn, a stream for the filter, one for the copies, and per buffer pair the events "filtered" and "copied"
+// planes: one size, the largest a call can ask for), the counter of clamped elements and its page-locked twin, and the two events a
+// kernel is timed with.  The batch call works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
 struct FilterSet {
     static constexpr size_t kTapBytes = 4 * (size_t) kFiltMaxTaps;
     static constexpr size_t kCoefBytes = kTapBytes + (size_t) filter_mfma_plane_bytes(kFiltMaxSteps);
     DevBuf<uint8_t>               d_coef;    PinnedBuf<uint8_t>            h_coef;        // [kCoefBytes]
     DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    DevBuf<uint8_t>               d_render[2], d_out[2];                                  // bytes
-    Stream         filt_stream, copy_stream;
-    Event          t0, t1, filtered[2], copied[2];
-    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    Event          t0, t1;
     long           last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, outputs per run, pieces (gpsiq_filter_last_plan)
-    int reserve(size_t render_bytes, size_t out_bytes);         // first use + room for one call (0, 0: gpsiq_filter)
+    int reserve();                                  // first use
 };
 
-// (coefficients, counter, events and streams on first use; the staging pairs grow together, rendered side first)
-inline int FilterSet::reserve(size_t render_bytes, size_t out_bytes)
+inline int FilterSet::reserve()
 {
     HIP_TRY(t0.ensure(hipEventDefault));
     HIP_TRY(t1.ensure(hipEventDefault));
     HIP_TRY(reserve_together(kCoefBytes, kCoefBytes, d_coef, h_coef));
     HIP_TRY(d_count.reserve(1));
     HIP_TRY(h_count.reserve(1));
-    if (!render_bytes && !out_bytes) return GPSIQ_OK;
-    HIP_TRY(filt_stream.ensure());
-    HIP_TRY(copy_stream.ensure());
-    for (auto &e : filtered) HIP_TRY(e.ensure());
-    for (auto &e : copied) HIP_TRY(e.ensure());
-    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
-    HIP_TRY(reserve_together(out_bytes, out_bytes + out_bytes / 4 + 256, d_out[0], d_out[1]));
     return GPSIQ_OK;
 }
 

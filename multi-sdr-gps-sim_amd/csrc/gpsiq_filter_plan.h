@@ -1,6 +1,7 @@
-// gpsiq_filter_plan.h -- the output count, the kernel and the grid a gpsiq_filter call (include/gpsiq_rows.h, "Filter") takes, and the
-// piece size of gpsiq_generate_batch_filtered.  Host code only, and pure: no HIP, no environment (the GPSIQ_FILTER_KERNEL and
-// GPSIQ_FILTER_PIECE_BLOCKS overrides are arguments, read per call by the caller).  tests/filter_plan.cpp pins every plan on the CPU.
+// gpsiq_filter_plan.h -- the output count, the kernel and the grid a gpsiq_filter call (include/gpsiq_rows.h, "Filter") takes.  Host
+// code only, and pure: no HIP, no environment (the GPSIQ_FILTER_KERNEL override is an argument, read per call by the caller; so is
+// GPSIQ_FILTER_PIECE_BLOCKS, for the piece size of gpsiq_generate_batch_filtered: stage_piece_blocks, gpsiq_pieces.h).
+// tests/filter_plan.cpp pins every plan on the CPU.
 // Not a device source: the geometry the kernels are compiled for is gpsiq_filter_geometry.h.
 #ifndef GPSIQ_FILTER_PLAN_H
 #define GPSIQ_FILTER_PLAN_H
@@ -9,6 +10,7 @@
 #include <cstdint>
 
 #include "gpsiq_filter_geometry.h"
+#include "gpsiq_pieces.h"
 
 namespace gpsiq {
 
@@ -66,24 +68,9 @@ inline FilterPlan plan_filter(int nsamp, int in_size, int ntaps, int decim, int 
     return p;
 }
 
-// Blocks per piece of gpsiq_generate_batch_filtered: the policy of pack_piece_blocks (gpsiq_pack_plan.h), ~32 MiB of rendered source
-// per piece, at least one block, at most the call's; override_blocks > 0 (GPSIQ_FILTER_PIECE_BLOCKS) replaces the default.  A piece is
-// one span of the filter: its samples fit an int, whatever was asked for (nsamp >= 1).
-inline int filter_piece_blocks(int nblocks, int nsamp, size_t src_block_bytes, long override_blocks)
-{
-    if (nblocks <= 0) return 0;
-    long n;
-    if (override_blocks > 0) n = override_blocks;
-    else {
-        const size_t target = (size_t) 32 << 20;
-        const size_t q = src_block_bytes ? (target + src_block_bytes - 1) / src_block_bytes : (size_t) nblocks;
-        n = q > (size_t) nblocks ? (long) nblocks : (long) q;
-    }
-    const long most = nsamp > 0 ? (long) (INT32_MAX / nsamp) : (long) nblocks;
-    if (n > most) n = most;
-    if (n < 1) n = 1;
-    return n > nblocks ? nblocks : (int) n;
-}
+// Blocks per piece of gpsiq_generate_batch_filtered: the one policy, stage_piece_blocks (gpsiq_pieces.h), under the call's name.  A
+// piece is one span of the filter: its samples fit an int
+inline int filter_piece_blocks(int nblocks, int nsamp, size_t src_block_bytes, long override_blocks) { return stage_piece_blocks(nblocks, nsamp, src_block_bytes, override_blocks); }
 
 }  // namespace gpsiq
 #endif

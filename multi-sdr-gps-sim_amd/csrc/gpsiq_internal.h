@@ -18,6 +18,12 @@ namespace gpsiq {
 
 int  fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int  set_error(int code, const char *text);
+// whether [a, a + alen) and [b, b + blen) share a byte (the stream stages' argument checks)
+inline bool overlap(const void *a, size_t alen, const void *b, size_t blen)
+{
+    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
+}
 void ca_code(int prn, uint8_t chips[GPSIQ_CA_SEQ_LEN]);
 void build_device_tables(DeviceTables *t);
 uint64_t carr_phase_to_fixed(double cycles);

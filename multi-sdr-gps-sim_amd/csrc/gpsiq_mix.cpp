@@ -57,12 +57,6 @@ int check_term(const gpsiq_mix_term_t &t, int k, MixDevTerm *d)
     return GPSIQ_OK;
 }
 
-bool overlap(const void *a, size_t alen, const void *b, size_t blen)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
-}
-
 // the table on the device, queued on s on first use.  The caller has made sure nothing queued earlier still reads the page-locked
 // staging (every call ends synchronised); have_table is set by the caller once the call has ended well
 int stage_table(MixSet &k, hipStream_t s)
@@ -130,7 +124,7 @@ int gpsiq_mix_impl(gpsiq_ctx_t *c, int nsamp, uint64_t m0, const gpsiq_mix_term_
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     MixSet &k = c->mix;
-    if (int rc = k.reserve(0)) return rc;
+    if (int rc = k.reserve()) return rc;
     if (int rc = stage_table(k, s)) return rc;
     HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
     HIP_TRY(hipEventRecord(k.t0.get(), s));
@@ -145,22 +139,9 @@ int gpsiq_mix_impl(gpsiq_ctx_t *c, int nsamp, uint64_t m0, const gpsiq_mix_term_
     return GPSIQ_OK;
 }
 
-// nothing of the call may still write the staging or dst when it returns, on any path
-static int drain_mix(gpsiq_ctx *c, int rc)
-{
-    hipError_t e = hipStreamSynchronize(c->mix.mix_stream.get());
-    const hipError_t d = hipStreamSynchronize(c->mix.copy_stream.get());
-    if (e == hipSuccess) e = d;
-    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
-    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "mixed batch: %s", hipGetErrorString(e));
-}
-
-// Piece k: gpsiq_generate_batch renders its blocks back to back into d_render[k & 1] (synchronous), the mixer works on them IN PLACE on
-// mix_stream -- the stream term is the staging itself, the tones run at the piece's absolute sample index -- and the rows cross to the
-// host on copy_stream behind it, while the calling thread is already in the render of piece k + 1, which uses the other buffer.
-// Piece k + 2 takes buffer k & 1 again once `copied` of piece k has been reached.  Nothing crosses from piece to piece but the carrier
-// phases: a tone's phase is a closed form of the absolute index.  The pieces are chained as gpsiq_generate_batch_filtered chains them
-// (gpsiq_filter.cpp).
+// The pieces of gpsiq_stage_batch.h with the mixer as the stage, IN PLACE: the stream term is the rendered piece itself, the tones
+// run at the piece's absolute sample index, and the rows cross to the host from the rendered pair (no lead region, no output pair).
+// Nothing crosses from piece to piece but the carrier phases: a tone's phase is a closed form of the absolute index.
 int gpsiq_generate_batch_mixed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size, int32_t base_gain,
                                     const gpsiq_mix_term_t *tones, int ntones, uint64_t m0, int shift, int qmax, void *dst, size_t dst_block_stride,
                                     uint64_t *clipped, double *carr_phase_out)
@@ -182,62 +163,35 @@ int gpsiq_generate_batch_mixed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int 
     if (dst_block_stride < blk_bytes) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
     if (clipped) *clipped = 0;
     if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
-    // the pieces' first rows are rewritten on the host: ch is host memory
-    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_mixed", nullptr)) return rc;
     const char *env = std::getenv("GPSIQ_MIX_PIECE_BLOCKS");
     const int piece = mix_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
     const int npieces = (nblocks + piece - 1) / piece;
     const int force = forced_kernel();
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_mixed", ch, blk_bytes * (size_t) piece + 16, 0)) return rc;       // (+16: never a request of no bytes)
     MixSet &k = c->mix;
-    if (int rc = k.reserve(blk_bytes * (size_t) piece + 16)) return rc;                 // (+16: never a request of no bytes)
-    MixPlan none;
-    note_plan(c, none, npieces);
-    hipStream_t ms = k.mix_stream.get();
-    if (nsamp) {
-        if (int rc = stage_table(k, ms)) return drain_mix(c, rc);
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ms));
-    }
+    if (int rc = k.reserve()) return rc;
+    const StageBatch stage = {"mixed batch", sample_size, 0, 0, piece, k.d_count.get(), k.h_count.get()};
+    note_plan(c, MixPlan(), npieces);
+    const hipStream_t ss = c->ring.stage_stream.get();
+    const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
+        if (int rc = stage_table(k, ss)) return rc;
+        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        return GPSIQ_OK;
+    }();
     double carr[GPSIQ_MAX_CHAN] = {};
-    int rc = GPSIQ_OK;
-    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
-        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, buf = p & 1;
-        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
-        if (p > 0) {
-            k.row.assign(rows, rows + (size_t) nb * nchan);
-            for (int i = 0; i < nchan; ++i)
-                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
-            rows = k.row.data();
-        }
-        if (p >= 2) {                                                 // the buffer's last user: piece p - 2
-            const hipError_t e = hipEventSynchronize(k.copied[buf].get());
-            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "mixed batch: %s", hipGetErrorString(e)); break; }
-        }
-        uint8_t *span = k.d_render[buf].get();
-        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, sample_size, span, 1, carr);
-        if (rc != GPSIQ_OK) break;
-        if (nsamp == 0) continue;
-        const uint64_t m = m0 + (uint64_t) b0 * (uint64_t) nsamp;
-        const MixPlan pl = plan_mix(nb * nsamp, m, sample_size, (uint64_t) (uintptr_t) span, force);
-        if (p == 0) note_plan(c, pl, npieces);
-        dev.t[0].src = span;
-        rc = queue_mix(c, pl, dev, m, nb * nsamp, shift, qmax, sample_size, span, ms);
-        if (rc != GPSIQ_OK) break;
-        hipError_t e = hipEventRecord(k.mixed[buf].get(), ms);
-        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.mixed[buf].get(), 0);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * dst_block_stride, dst_block_stride, span, blk_bytes, blk_bytes,
-                                                  (size_t) nb, hipMemcpyDeviceToHost, k.copy_stream.get());
-        if (e == hipSuccess) e = hipEventRecord(k.copied[buf].get(), k.copy_stream.get());
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "mixed batch piece: %s", hipGetErrorString(e));
-    }
-    if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last mixer
-        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ms);
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "mixed batch count: %s", hipGetErrorString(e));
-    }
-    rc = drain_mix(c, rc);
+    uint64_t clamped = 0;
+    const int rc = gpsiq_stage_batch_run(c, stage, rc0, ch, nblocks, nchan, nsamp, fs, [&](const Piece &pc, PieceCopy *cp) -> int {
+        const uint64_t m = m0 + (uint64_t) pc.b0 * (uint64_t) nsamp;
+        const MixPlan pl = plan_mix(pc.nb * nsamp, m, sample_size, (uint64_t) (uintptr_t) pc.span, force);
+        if (pc.p == 0) note_plan(c, pl, npieces);                     // (the plan looks at the span's address)
+        dev.t[0].src = pc.span;
+        if (int rq = queue_mix(c, pl, dev, m, pc.nb * nsamp, shift, qmax, sample_size, pc.span, ss)) return rq;
+        *cp = {pc.span, blk_bytes, blk_bytes, (size_t) pc.nb, static_cast<uint8_t *>(dst) + (size_t) pc.b0 * dst_block_stride, dst_block_stride};
+        return GPSIQ_OK;
+    }, carr, &clamped);
     if (rc != GPSIQ_OK) return rc;
     if (nsamp) k.have_table = true;
-    if (clipped && nsamp) *clipped = (uint64_t) k.h_count[0];
+    if (clipped) *clipped = clamped;
     if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
     return GPSIQ_OK;
 }

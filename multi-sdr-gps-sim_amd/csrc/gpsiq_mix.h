@@ -4,8 +4,6 @@
 #ifndef GPSIQ_MIX_H
 #define GPSIQ_MIX_H
 
-#include <vector>
-
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
 #include "gpsiq_mix_geometry.h"
@@ -13,35 +11,24 @@
 namespace gpsiq {
 
 // the carrier table as the kernels read it (512 dwords: cos below, sin above) on the device (have: it has arrived) and page-locked on
-// its way there, the counter of clamped elements and its page-locked twin, the two events a kernel is timed with, and what the batch
-// call works through its pieces with -- two rendered staging buffers taken in turn (the mixer works in place), a stream for the
-// mixer, one for the copies, and per buffer the events "mixed" and "copied"
+// its way there, the counter of clamped elements and its page-locked twin, and the two events a kernel is timed with.  The batch call
+// works through its pieces with the context's staging ring (gpsiq_stage_batch.h), in place in the rendered pair
 struct MixSet {
     DevBuf<uint32_t>              d_table;   PinnedBuf<uint32_t>           h_table;       // [512]
     bool                          have_table = false;
     DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    DevBuf<uint8_t>               d_render[2];                                            // bytes
-    Stream         mix_stream, copy_stream;
-    Event          t0, t1, mixed[2], copied[2];
-    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    Event          t0, t1;
     long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, units, pieces (gpsiq_mix_last_plan)
-    int reserve(size_t render_bytes);               // first use + room for one call (0: gpsiq_mix)
+    int reserve();                                  // first use
 };
 
-// (table, counter, events and streams on first use; the staging pair grows together)
-inline int MixSet::reserve(size_t render_bytes)
+inline int MixSet::reserve()
 {
     HIP_TRY(t0.ensure(hipEventDefault));
     HIP_TRY(t1.ensure(hipEventDefault));
     HIP_TRY(reserve_together(512, 512, d_table, h_table));
     HIP_TRY(d_count.reserve(1));
     HIP_TRY(h_count.reserve(1));
-    if (!render_bytes) return GPSIQ_OK;
-    HIP_TRY(mix_stream.ensure());
-    HIP_TRY(copy_stream.ensure());
-    for (auto &e : mixed) HIP_TRY(e.ensure());
-    for (auto &e : copied) HIP_TRY(e.ensure());
-    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
     return GPSIQ_OK;
 }
 

@@ -1,7 +1,7 @@
-// gpsiq_mix_plan.h -- the kernel and the grid a gpsiq_mix call (include/gpsiq_rows.h, "Mix") takes, and the piece size of
-// gpsiq_generate_batch_mixed.  Host code only, and pure: no HIP, no environment (the GPSIQ_MIX_KERNEL and GPSIQ_MIX_PIECE_BLOCKS
-// overrides are arguments, read per call by the caller).  tests/mix_plan.cpp pins every plan on the CPU.  Not a device source: the
-// geometry the kernels are compiled for is gpsiq_mix_geometry.h.
+// gpsiq_mix_plan.h -- the kernel and the grid a gpsiq_mix call (include/gpsiq_rows.h, "Mix") takes.  Host code only, and pure: no HIP,
+// no environment (the GPSIQ_MIX_KERNEL override is an argument, read per call by the caller; so is GPSIQ_MIX_PIECE_BLOCKS, for the
+// piece size of gpsiq_generate_batch_mixed: stage_piece_blocks, gpsiq_pieces.h).  tests/mix_plan.cpp pins every plan on the CPU.
+// Not a device source: the geometry the kernels are compiled for is gpsiq_mix_geometry.h.
 #ifndef GPSIQ_MIX_PLAN_H
 #define GPSIQ_MIX_PLAN_H
 
@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "gpsiq_mix_geometry.h"
+#include "gpsiq_pieces.h"
 
 namespace gpsiq {
 
@@ -57,24 +58,9 @@ inline MixPlan plan_mix(int nsamp, uint64_t m0, int out_size, uint64_t dst_addr,
     return p;
 }
 
-// Blocks per piece of gpsiq_generate_batch_mixed: the policy of filter_piece_blocks (gpsiq_filter_plan.h), ~32 MiB of rendered stream
-// per piece, at least one block, at most the call's; override_blocks > 0 (GPSIQ_MIX_PIECE_BLOCKS) replaces the default.  A piece is
-// one span of the mixer: its samples fit an int, whatever was asked for (nsamp >= 1).
-inline int mix_piece_blocks(int nblocks, int nsamp, size_t block_bytes, long override_blocks)
-{
-    if (nblocks <= 0) return 0;
-    long n;
-    if (override_blocks > 0) n = override_blocks;
-    else {
-        const size_t target = (size_t) 32 << 20;
-        const size_t q = block_bytes ? (target + block_bytes - 1) / block_bytes : (size_t) nblocks;
-        n = q > (size_t) nblocks ? (long) nblocks : (long) q;
-    }
-    const long most = nsamp > 0 ? (long) (INT32_MAX / nsamp) : (long) nblocks;
-    if (n > most) n = most;
-    if (n < 1) n = 1;
-    return n > nblocks ? nblocks : (int) n;
-}
+// Blocks per piece of gpsiq_generate_batch_mixed: the one policy, stage_piece_blocks (gpsiq_pieces.h), under the call's name.  A piece
+// is one span of the mixer: its samples fit an int
+inline int mix_piece_blocks(int nblocks, int nsamp, size_t block_bytes, long override_blocks) { return stage_piece_blocks(nblocks, nsamp, block_bytes, override_blocks); }
 
 }  // namespace gpsiq
 #endif

@@ -64,7 +64,7 @@ int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, con
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     PackSet &k = c->pack;
-    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = k.reserve()) return rc;
     HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
     HIP_TRY(hipEventRecord(k.t0.get(), s));
     if (int rc = queue_pack(c, p, nsamp, sample_size, bits, static_cast<const uint8_t *>(src), src_stride, static_cast<uint8_t *>(dst), dst_stride, s)) return rc;
@@ -88,7 +88,7 @@ int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const vo
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     PackSet &k = c->pack;
-    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = k.reserve()) return rc;
     const UnpackFn kernel = unpack_kernel(bits, sample_size);
     if (!kernel) return fail(GPSIQ_E_DEVICE, "no unpack kernel for %d bits, %d-byte samples", bits, sample_size);
     HIP_TRY(hipEventRecord(k.t0.get(), s));
@@ -101,22 +101,11 @@ int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const vo
     return GPSIQ_OK;
 }
 
-// nothing of the call may still read the staging or write dst when it returns, on any path
-static int drain_pack(gpsiq_ctx *c, int rc)
-{
-    hipError_t e = hipStreamSynchronize(c->pack.pack_stream.get());
-    const hipError_t d = hipStreamSynchronize(c->pack.copy_stream.get());
-    if (e == hipSuccess) e = d;
-    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
-    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "packed batch: %s", hipGetErrorString(e));
-}
-
-// Piece k: gpsiq_generate_batch renders its blocks into d_render[k & 1] (synchronous), the packer turns them into d_packed[k & 1] on
-// pack_stream, the rows cross to the host on copy_stream behind it -- while the calling thread is already in the render of piece
-// k + 1, which uses the other pair.  Piece k + 2 takes pair k & 1 again once `copied` of piece k has been reached.
-// The pieces are chained as a host chains calls (host/gpsiq_runahead.c): a piece's first block carries, in every slot that keeps its
-// satellite across the edge, the phase the piece before handed out; a slot whose satellite changes there seeds itself from its own
-// carr_phase, as it does inside one call.  gpsiq_generate_batch numbers the noise blocks on from call to call.
+// The pieces of gpsiq_stage_batch.h with the packer as the stage: the rendered blocks of a piece are packed into d_out[pair], rows of
+// `pstride` bytes.  gpsiq_generate_batch lays the rendered blocks back to back.  With an even nsamp every one of them is a packer's
+// source where it lies.  With an odd nsamp every other block starts 2 bytes off a dword: the blocks are rendered behind the rows the
+// packer reads, lead = `raw` bytes into the same buffer, and a device copy on the stage stream moves them to rows of `sstride` bytes
+// first -- nothing reads [0, raw) of the ring, whatever an earlier call left there, before that copy has written it.
 int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int bits, void *dst,
                                      size_t dst_block_stride, double *carr_phase_out)
 {
@@ -130,63 +119,30 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
     if (!c->level.mult || c->level.qmax > qmax)
         return fail(GPSIQ_E_STATE, "packed output at %d bits needs the output level on with qmax <= %d (gpsiq_set_level)", bits, qmax);
     if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
-    // the pieces' first rows are rewritten on the host: ch is host memory
-    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_packed", nullptr)) return rc;
     const char *env = std::getenv("GPSIQ_PACK_PIECE_BLOCKS");
     const int piece = pack_piece_blocks(nblocks, blk_bytes, env ? std::atol(env) : 0);
-    const int npieces = (nblocks + piece - 1) / piece;
     const size_t pstride = (plen + 3) & ~(size_t) 3;
-    // gpsiq_generate_batch lays the rendered blocks back to back.  With an even nsamp every one of them is a packer's source where it
-    // lies.  With an odd nsamp every other block starts 2 bytes off a dword: the blocks are rendered behind the rows the packer reads,
-    // `raw` bytes into the same buffer, and a device copy on pack_stream moves them to rows of `sstride` bytes
     const size_t sstride = (blk_bytes + 3) & ~(size_t) 3, raw = sstride != blk_bytes ? sstride * (size_t) piece : 0;
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_packed", ch, raw + blk_bytes * (size_t) piece + 4, pstride * (size_t) piece + 4)) return rc;      // (+4: never a request of no bytes)
     PackSet &k = c->pack;
-    if (int rc = k.reserve(raw + blk_bytes * (size_t) piece + 4, pstride * (size_t) piece + 4)) return rc;      // (+4: never a request of no bytes)
-    const PackPlan whole = plan_pack(piece, nsamp, GPSIQ_SC08, bits);
-    note_plan(c, whole, npieces);
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), k.pack_stream.get()));
+    if (int rc = k.reserve()) return rc;
+    const StageBatch st = {"packed batch", GPSIQ_SC08, raw, 0, piece, k.d_count.get(), k.h_count.get()};
+    note_plan(c, plan_pack(piece, nsamp, GPSIQ_SC08, bits), (nblocks + piece - 1) / piece);
+    const hipStream_t ss = c->ring.stage_stream.get();
+    const int rc0 = [&]() -> int { HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss)); return GPSIQ_OK; }();
     double carr[GPSIQ_MAX_CHAN] = {};
-    int rc = GPSIQ_OK;
-    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
-        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, pair = p & 1;
-        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
-        if (p > 0) {
-            k.row.assign(rows, rows + (size_t) nb * nchan);
-            for (int i = 0; i < nchan; ++i)
-                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
-            rows = k.row.data();
-        }
-        if (p >= 2) {                                                 // the pair's last user: piece p - 2
-            const hipError_t e = hipEventSynchronize(k.copied[pair].get());
-            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "packed batch: %s", hipGetErrorString(e)); break; }
-        }
-        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, GPSIQ_SC08, k.d_render[pair].get() + raw, 1, carr);
-        if (rc != GPSIQ_OK) break;
-        if (nsamp == 0) continue;
-        if (raw) {
-            const hipError_t e = hipMemcpy2DAsync(k.d_render[pair].get(), sstride, k.d_render[pair].get() + raw, blk_bytes, blk_bytes, (size_t) nb,
-                                                  hipMemcpyDeviceToDevice, k.pack_stream.get());
-            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "packed batch piece: %s", hipGetErrorString(e)); break; }
-        }
-        rc = queue_pack(c, plan_pack(nb, nsamp, GPSIQ_SC08, bits), nsamp, GPSIQ_SC08, bits, k.d_render[pair].get(), sstride, k.d_packed[pair].get(),
-                        pstride, k.pack_stream.get());
-        if (rc != GPSIQ_OK) break;
-        hipError_t e = hipEventRecord(k.packed[pair].get(), k.pack_stream.get());
-        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.packed[pair].get(), 0);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(static_cast<uint8_t *>(dst) + (size_t) b0 * dst_block_stride, dst_block_stride, k.d_packed[pair].get(),
-                                                  pstride, plen, (size_t) nb, hipMemcpyDeviceToHost, k.copy_stream.get());
-        if (e == hipSuccess) e = hipEventRecord(k.copied[pair].get(), k.copy_stream.get());
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "packed batch piece: %s", hipGetErrorString(e));
-    }
-    if (rc == GPSIQ_OK) {                                             // the pieces' sum, behind the last packer
-        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, k.pack_stream.get());
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "packed batch count: %s", hipGetErrorString(e));
-    }
-    rc = drain_pack(c, rc);
+    uint64_t clamped = 0;
+    const int rc = gpsiq_stage_batch_run(c, st, rc0, ch, nblocks, nchan, nsamp, fs, [&](const Piece &pc, PieceCopy *cp) -> int {
+        uint8_t *rows = c->ring.d_render[pc.pair].get(), *out = c->ring.d_out[pc.pair].get();
+        const hipError_t e = raw ? hipMemcpy2DAsync(rows, sstride, pc.span, blk_bytes, blk_bytes, (size_t) pc.nb, hipMemcpyDeviceToDevice, ss) : hipSuccess;
+        if (e != hipSuccess) return fail(GPSIQ_E_DEVICE, "packed batch piece: %s", hipGetErrorString(e));
+        if (int rq = queue_pack(c, plan_pack(pc.nb, nsamp, GPSIQ_SC08, bits), nsamp, GPSIQ_SC08, bits, rows, sstride, out, pstride, ss)) return rq;
+        *cp = {out, pstride, plen, (size_t) pc.nb, static_cast<uint8_t *>(dst) + (size_t) pc.b0 * dst_block_stride, dst_block_stride};
+        return GPSIQ_OK;
+    }, carr, &clamped);
     if (rc != GPSIQ_OK) return rc;
     // the level stage held every element inside the format (checked above): a packer that had to clamp says the stream is not that one
-    if (k.h_count[0]) return fail(GPSIQ_E_DEVICE, "packed batch: the packer clamped %llu elements of a stream levelled to qmax %d", k.h_count[0], c->level.qmax);
+    if (clamped) return fail(GPSIQ_E_DEVICE, "packed batch: the packer clamped %llu elements of a stream levelled to qmax %d", (unsigned long long) clamped, c->level.qmax);
     if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
     return GPSIQ_OK;
 }

@@ -4,40 +4,26 @@
 #ifndef GPSIQ_PACK_H
 #define GPSIQ_PACK_H
 
-#include <vector>
-
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
 
 namespace gpsiq {
 
-// the counter of clamped elements on the device and page-locked on its way back, the two events a kernel is timed with, and what the
-// batch call works through its pieces with -- two rendered and two packed staging buffers taken in turn, a stream for the packer,
-// one for the copies, and per buffer pair the events "packed" and "copied"
+// the counter of clamped elements on the device and page-locked on its way back, and the two events a kernel is timed with.  The
+// batch call works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
 struct PackSet {
     DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    DevBuf<uint8_t>               d_render[2], d_packed[2];                               // bytes
-    Stream         pack_stream, copy_stream;
-    Event          t0, t1, packed[2], copied[2];
-    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    Event          t0, t1;
     long           last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, units per block, tiles per block, pieces (gpsiq_pack_last_plan)
-    int reserve(size_t render_bytes, size_t packed_bytes);      // first use + room for one call (0, 0: gpsiq_pack / gpsiq_unpack)
+    int reserve();                                  // first use
 };
 
-// (the counter, events and streams on first use; the staging pairs grow together, rendered side first)
-inline int PackSet::reserve(size_t render_bytes, size_t packed_bytes)
+inline int PackSet::reserve()
 {
     HIP_TRY(t0.ensure(hipEventDefault));
     HIP_TRY(t1.ensure(hipEventDefault));
     HIP_TRY(d_count.reserve(1));
     HIP_TRY(h_count.reserve(1));
-    if (!render_bytes && !packed_bytes) return GPSIQ_OK;
-    HIP_TRY(pack_stream.ensure());
-    HIP_TRY(copy_stream.ensure());
-    for (auto &e : packed) HIP_TRY(e.ensure());
-    for (auto &e : copied) HIP_TRY(e.ensure());
-    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
-    HIP_TRY(reserve_together(packed_bytes, packed_bytes + packed_bytes / 4 + 256, d_packed[0], d_packed[1]));
     return GPSIQ_OK;
 }
 

@@ -1,7 +1,8 @@
-// gpsiq_pack_plan.h -- the grid a gpsiq_pack / gpsiq_unpack call (include/gpsiq_rows.h, "Packed streams") takes, and the piece size
-// of gpsiq_generate_batch_packed.  Host code only, and pure: no HIP, no environment (the GPSIQ_PACK_PIECE_BLOCKS override is an
-// argument, read per call by the caller).  tests/pack_plan.cpp pins every plan on the CPU.  Not a device source: the geometry the
-// kernels are compiled for is gpsiq_pack_geometry.h, the list of kernels that exist is in gpsiq_pack_kernels.hip.
+// gpsiq_pack_plan.h -- the grid a gpsiq_pack / gpsiq_unpack call (include/gpsiq_rows.h, "Packed streams") takes.  Host code only, and
+// pure: no HIP, no environment.  The piece size of gpsiq_generate_batch_packed is stage_piece_blocks (gpsiq_pieces.h), with the
+// GPSIQ_PACK_PIECE_BLOCKS override as an argument, read per call by the caller.  tests/pack_plan.cpp pins every plan on the CPU.
+// Not a device source: the geometry the kernels are compiled for is gpsiq_pack_geometry.h, the list of kernels that exist is in
+// gpsiq_pack_kernels.hip.
 #ifndef GPSIQ_PACK_PLAN_H
 #define GPSIQ_PACK_PLAN_H
 
@@ -9,6 +10,7 @@
 #include <cstdint>
 
 #include "gpsiq_pack_geometry.h"
+#include "gpsiq_pieces.h"
 
 namespace gpsiq {
 
@@ -57,22 +59,9 @@ inline PackPlan plan_unpack(int nblocks, int nsamp, int bits, int sample_size)
     return plan_units(nblocks, (uint64_t) 2 * (uint64_t) nsamp * (uint64_t) sample_size, unpack_unit_dst_bytes(bits, sample_size));
 }
 
-// Blocks per piece of gpsiq_generate_batch_packed: ~32 MiB of rendered source per piece (the policy of d2h_chunk_blocks,
-// gpsiq_pieces.h: >= 0.5 ms of rendering for the copy of the piece before to hide under), at least one block, at most the call's.
-// override_blocks > 0 (GPSIQ_PACK_PIECE_BLOCKS) replaces the default.
-inline int pack_piece_blocks(int nblocks, size_t src_block_bytes, long override_blocks)
-{
-    if (nblocks <= 0) return 0;
-    long n;
-    if (override_blocks > 0) n = override_blocks;
-    else {
-        const size_t target = (size_t) 32 << 20;
-        const size_t q = src_block_bytes ? (target + src_block_bytes - 1) / src_block_bytes : (size_t) nblocks;
-        n = q > (size_t) nblocks ? (long) nblocks : (long) q;
-    }
-    if (n < 1) n = 1;
-    return n > nblocks ? nblocks : (int) n;
-}
+// Blocks per piece of gpsiq_generate_batch_packed: the one policy, stage_piece_blocks (gpsiq_pieces.h), under the call's name.  The
+// packer takes a piece block by block, not as one span: no sample cap
+inline int pack_piece_blocks(int nblocks, size_t src_block_bytes, long override_blocks) { return stage_piece_blocks(nblocks, 0, src_block_bytes, override_blocks); }
 
 }  // namespace gpsiq
 #endif

@@ -10,13 +10,19 @@
 //   ref_chunk_blocks    reference model, host walk: the chunk of piece_ends; n <= 0 or n >= nblocks: one piece
 //   device_piece_ends   device evaluation: blocks of the first piece, each later one eight times the one before;
 //                       n <= 0 or 2 n > nblocks: one piece
+// The staged batch calls (gpsiq_stage_batch.h) have an override each, GPSIQ_PACK_ / FILTER_ / MIX_ / RESAMPLE_PIECE_BLOCKS = n:
+//   stage_piece_blocks  blocks per piece, as far as the call goes and a piece's samples fit an int; n <= 0: the plan below
+// This header also holds what the pieces of those calls hand each other on the host: piece_rows.
 #ifndef GPSIQ_PIECES_H
 #define GPSIQ_PIECES_H
 
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <optional>
 #include <vector>
+
+#include "../../include/gpsiq.h"             // gpsiq_chan_t: piece_rows
 
 namespace gpsiq {
 
@@ -157,6 +163,41 @@ inline void device_piece_ends(int nblocks, int nsamp, int nchan, bool host_rows,
         size *= growth;
     }
     ends->push_back(nblocks);
+}
+
+// Blocks per piece of a staged batch call (gpsiq_generate_batch_packed / _filtered / _mixed / _resampled): ~32 MiB of rendered
+// stream per piece (the policy of d2h_chunk_blocks: >= 0.5 ms of rendering for the copy of the piece before to hide under), at
+// least one block, at most the call's; override_blocks > 0 (the stage's GPSIQ_*_PIECE_BLOCKS) replaces the default.  Where a piece
+// is one span of its stage (nsamp >= 1: filter, mixer, resampler) its samples fit an int, whatever was asked for; nsamp = 0 (the
+// packer, which works block by block): no such cap.
+inline int stage_piece_blocks(int nblocks, int nsamp, size_t block_bytes, long override_blocks)
+{
+    if (nblocks <= 0) return 0;
+    long n;
+    if (override_blocks > 0) n = override_blocks;
+    else {
+        const size_t target = (size_t) 32 << 20;
+        const size_t q = block_bytes ? (target + block_bytes - 1) / block_bytes : (size_t) nblocks;
+        n = q > (size_t) nblocks ? (long) nblocks : (long) q;
+    }
+    const long most = nsamp > 0 ? (long) (INT32_MAX / nsamp) : (long) nblocks;
+    if (n > most) n = most;
+    if (n < 1) n = 1;
+    return n > nblocks ? nblocks : (int) n;
+}
+
+// The descriptors the piece of blocks [b0, b0 + nb) of such a call is rendered from.  The pieces are chained as a host chains calls
+// (host/gpsiq_runahead.c): the first piece takes the caller's rows as they lie; a later piece's first block carries, in every slot
+// that keeps its satellite across the edge, the phase the piece before handed out (carr), and a slot whose satellite changes there
+// seeds itself from its own carr_phase, as it does inside one call.  Every other row is the caller's.  row: the copy's home.
+inline const gpsiq_chan_t *piece_rows(const gpsiq_chan_t *ch, int b0, int nb, int nchan, const double *carr, std::vector<gpsiq_chan_t> *row)
+{
+    const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
+    if (b0 == 0) return rows;
+    row->assign(rows, rows + (size_t) nb * nchan);
+    for (int i = 0; i < nchan; ++i)
+        if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) (*row)[i].carr_phase = carr[i];
+    return row->data();
 }
 
 }  // namespace gpsiq

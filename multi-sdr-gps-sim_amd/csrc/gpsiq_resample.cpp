@@ -79,12 +79,6 @@ int queue_resample(gpsiq_ctx *c, const ResamplePlan &p, int nsamp, int sample_si
     return GPSIQ_OK;
 }
 
-bool overlap(const void *a, size_t alen, const void *b, size_t blen)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return alen && blen && a0 < b0 + blen && b0 < a0 + alen;
-}
-
 }  // namespace
 
 int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *src, const void *head, const int16_t *taps, int log2_phases, int ntaps,
@@ -113,7 +107,7 @@ int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
     ResampleSet &k = c->rs;
-    if (int rc = k.reserve(0, 0)) return rc;
+    if (int rc = k.reserve()) return rc;
     if (int rc = stage_table(c, taps, log2_phases, ntaps, s)) return rc;
     HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
     HIP_TRY(hipEventRecord(k.t0.get(), s));
@@ -127,21 +121,10 @@ int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *
     return GPSIQ_OK;
 }
 
-// nothing of the call may still read the staging or write dst when it returns, on any path
-static int drain_resample(gpsiq_ctx *c, int rc)
-{
-    hipError_t e = hipStreamSynchronize(c->rs.rs_stream.get());
-    const hipError_t d = hipStreamSynchronize(c->rs.copy_stream.get());
-    if (e == hipSuccess) e = d;
-    if (rc != GPSIQ_OK) return rc;                                    // the call has failed already: its error text stands
-    return e == hipSuccess ? GPSIQ_OK : fail(GPSIQ_E_DEVICE, "resampled batch: %s", hipGetErrorString(e));
-}
-
-// The piece loop of gpsiq_generate_batch_filtered (gpsiq_filter.cpp) with the resampler in the filter's place.  Piece k is rendered
-// into d_render[k & 1] BEHIND a head region of `hb` bytes (synchronous), the resampler turns head region and piece into d_out[k & 1]
-// on rs_stream, and the samples cross to the host on copy_stream behind it, to where the pieces before ended -- while the calling
-// thread is already in the render of piece k + 1, which uses the other pair.  The history crosses inside the staging as the filtered
-// call's does; the position crosses on the host: piece k + 1 starts at piece k's next_pos, also where piece k gave no output.
+// The pieces of gpsiq_stage_batch.h with the resampler as the stage: lead region and history as the filtered call's
+// (gpsiq_filter.cpp), the first piece's history zeros, written per call.  The position crosses on the host: piece p + 1 starts at
+// piece p's next_pos, also where piece p gave no output (nothing is launched for it); a piece's outputs are one run of samples and
+// cross to where the pieces before ended.
 int gpsiq_generate_batch_resampled_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
                                         const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step, uint64_t pos0,
                                         int out_sample_size, void *dst, uint64_t dst_capacity, uint64_t *nout, uint64_t *clipped, double *carr_phase_out)
@@ -157,72 +140,41 @@ int gpsiq_generate_batch_resampled_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, 
     if (clipped) *clipped = 0;
     if (nout) *nout = 0;
     if (nblocks == 0) return GPSIQ_OK;                                // an empty batch leaves the carried phases alone
-    // the pieces' first rows are rewritten on the host: ch is host memory
-    if (int rc = gpsiq_rows_kind(c, ch, "gpsiq_generate_batch_resampled", nullptr)) return rc;
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, out_sample_bytes = (size_t) 2 * (size_t) out_sample_size;
     const char *env = std::getenv("GPSIQ_RESAMPLE_PIECE_BLOCKS");
     const int piece = resample_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
-    const int npieces = (nblocks + piece - 1) / piece;
     const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
     const int force = forced_kernel();
-    HIP_TRY(hipSetDevice(c->device));
-    ResampleSet &k = c->rs;
     const size_t piece_out = (size_t) resample_piece_outputs((uint64_t) piece * (uint64_t) nsamp, step) * out_sample_bytes;
-    if (int rc = k.reserve(hb + blk_bytes * (size_t) piece + 4, piece_out + 4)) return rc;     // (+4: never a request of no bytes)
-    note_plan(c, plan_resample((uint64_t) (nblocks < piece ? nblocks : piece) * (uint64_t) nsamp, log2_phases, ntaps, step, pos0, force), npieces);
-    hipStream_t rs_ = k.rs_stream.get();
-    if (nsamp) {
-        if (int rc = stage_table(c, taps, log2_phases, ntaps, rs_)) return drain_resample(c, rc);
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), rs_));
-        if (hb) HIP_TRY(hipMemsetAsync(k.d_render[0].get(), 0, hb, rs_));             // the first block's history
-    }
+    if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_resampled", ch, hb + blk_bytes * (size_t) piece + 4, piece_out + 4)) return rc;     // (+4: never a request of no bytes)
+    ResampleSet &k = c->rs;
+    if (int rc = k.reserve()) return rc;
+    const StageBatch stage = {"resampled batch", sample_size, hb, hist, piece, k.d_count.get(), k.h_count.get()};
+    note_plan(c, plan_resample((uint64_t) piece * (uint64_t) nsamp, log2_phases, ntaps, step, pos0, force), (nblocks + piece - 1) / piece);
+    const hipStream_t ss = c->ring.stage_stream.get();
+    const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
+        if (int rc = stage_table(c, taps, log2_phases, ntaps, ss)) return rc;
+        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        if (hb) HIP_TRY(hipMemsetAsync(c->ring.d_render[0].get(), 0, hb, ss));       // the first block's history
+        return GPSIQ_OK;
+    }();
     double carr[GPSIQ_MAX_CHAN] = {};
-    uint64_t pos = pos0, done = 0;
-    int rc = GPSIQ_OK;
-    for (int p = 0; p < npieces && rc == GPSIQ_OK; ++p) {
-        const int b0 = p * piece, nb = nblocks - b0 < piece ? nblocks - b0 : piece, pair = p & 1;
-        const gpsiq_chan_t *rows = ch + (size_t) b0 * nchan;
-        if (p > 0) {
-            k.row.assign(rows, rows + (size_t) nb * nchan);
-            for (int i = 0; i < nchan; ++i)
-                if (rows[i].prn > 0 && rows[i].prn == ch[(size_t) (b0 - 1) * nchan + i].prn) k.row[i].carr_phase = carr[i];
-            rows = k.row.data();
-        }
-        if (p >= 2) {                                                 // the pair's last user: piece p - 2
-            const hipError_t e = hipEventSynchronize(k.copied[pair].get());
-            if (e != hipSuccess) { rc = fail(GPSIQ_E_DEVICE, "resampled batch: %s", hipGetErrorString(e)); break; }
-        }
-        uint8_t *span = k.d_render[pair].get() + hb;
-        rc = gpsiq_generate_batch(c, rows, nb, nchan, nsamp, fs, sample_size, span, 1, carr);
-        if (rc != GPSIQ_OK) break;
-        if (nsamp == 0) continue;
-        const ResamplePlan pl = plan_resample((uint64_t) nb * (uint64_t) nsamp, log2_phases, ntaps, step, pos, force);
-        if (pl.launch) {
-            rc = queue_resample(c, pl, nb * nsamp, sample_size, span, hist ? span - hist : nullptr, log2_phases, ntaps, shift, interp, step, pos,
-                                out_sample_size, k.d_out[pair].get(), rs_);
-            if (rc != GPSIQ_OK) break;
-        }
-        hipError_t e = hipSuccess;
-        if (hist && p + 1 < npieces)                                  // the next piece's history
-            e = hipMemcpyAsync(k.d_render[pair ^ 1].get() + hb - hist, span + blk_bytes * (size_t) nb - hist, hist, hipMemcpyDeviceToDevice, rs_);
-        if (e == hipSuccess) e = hipEventRecord(k.resampled[pair].get(), rs_);
-        if (e == hipSuccess) e = hipStreamWaitEvent(k.copy_stream.get(), k.resampled[pair].get(), 0);
-        if (e == hipSuccess && pl.nout)
-            e = hipMemcpyAsync(static_cast<uint8_t *>(dst) + (size_t) done * out_sample_bytes, k.d_out[pair].get(), (size_t) pl.nout * out_sample_bytes,
-                               hipMemcpyDeviceToHost, k.copy_stream.get());
-        if (e == hipSuccess) e = hipEventRecord(k.copied[pair].get(), k.copy_stream.get());
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "resampled batch piece: %s", hipGetErrorString(e));
+    uint64_t pos = pos0, done = 0, clamped = 0;
+    const int rc = gpsiq_stage_batch_run(c, stage, rc0, ch, nblocks, nchan, nsamp, fs, [&](const Piece &pc, PieceCopy *cp) -> int {
+        uint8_t *out = c->ring.d_out[pc.pair].get();
+        const ResamplePlan pl = plan_resample((uint64_t) pc.nb * (uint64_t) nsamp, log2_phases, ntaps, step, pos, force);
+        if (pl.launch)
+            if (int rq = queue_resample(c, pl, pc.nb * nsamp, sample_size, pc.span, hist ? pc.span - hist : nullptr, log2_phases, ntaps, shift, interp, step, pos,
+                                        out_sample_size, out, ss)) return rq;
+        const size_t bytes = (size_t) pl.nout * out_sample_bytes;
+        *cp = {out, bytes, bytes, pl.nout ? (size_t) 1 : 0, static_cast<uint8_t *>(dst) + (size_t) done * out_sample_bytes, bytes};
         pos = pl.next_pos;
         done += pl.nout;
-    }
-    if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last resampler
-        const hipError_t e = hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, rs_);
-        if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "resampled batch count: %s", hipGetErrorString(e));
-    }
-    rc = drain_resample(c, rc);
+        return GPSIQ_OK;
+    }, carr, &clamped);
     if (rc != GPSIQ_OK) return rc;
     if (done != total) return fail(GPSIQ_E_DEVICE, "resampled batch: the pieces gave %llu samples, the span has %llu", (unsigned long long) done, (unsigned long long) total);
-    if (clipped && nsamp) *clipped = (uint64_t) k.h_count[0];
+    if (clipped) *clipped = clamped;
     if (nout) *nout = total;
     if (carr_phase_out) std::memcpy(carr_phase_out, carr, sizeof(double) * (size_t) nchan);
     return GPSIQ_OK;

@@ -5,8 +5,6 @@
 #ifndef GPSIQ_RESAMPLE_H
 #define GPSIQ_RESAMPLE_H
 
-#include <vector>
-
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
 #include "gpsiq_resample_geometry.h"
@@ -14,36 +12,24 @@
 namespace gpsiq {
 
 // the tap table of a call on the device and page-locked on its way there (one size, the largest a call can ask for), the counter of
-// clamped elements and its page-locked twin, the two events a kernel is timed with, and what the batch call works through its pieces
-// with -- two rendered and two resampled staging buffers taken in turn, a stream for the resampler, one for the copies, and per
-// buffer pair the events "resampled" and "copied"
+// clamped elements and its page-locked twin, and the two events a kernel is timed with.  The batch call works through its pieces
+// with the context's staging ring (gpsiq_stage_batch.h)
 struct ResampleSet {
     static constexpr size_t kTableEntries = (size_t) kRsMaxTable;
     DevBuf<int16_t>               d_taps;    PinnedBuf<int16_t>            h_taps;        // [kTableEntries]
     DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    DevBuf<uint8_t>               d_render[2], d_out[2];                                  // bytes
-    Stream         rs_stream, copy_stream;
-    Event          t0, t1, resampled[2], copied[2];
-    std::vector<gpsiq_chan_t> row;                  // a piece's descriptors with the carrier phases handed over in its first block
+    Event          t0, t1;
     long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, outputs per unit, pieces (gpsiq_resample_last_plan)
-    int reserve(size_t render_bytes, size_t out_bytes);         // first use + room for one call (0, 0: gpsiq_resample)
+    int reserve();                                  // first use
 };
 
-// (table, counter, events and streams on first use; the staging pairs grow together, rendered side first)
-inline int ResampleSet::reserve(size_t render_bytes, size_t out_bytes)
+inline int ResampleSet::reserve()
 {
     HIP_TRY(t0.ensure(hipEventDefault));
     HIP_TRY(t1.ensure(hipEventDefault));
     HIP_TRY(reserve_together(kTableEntries, kTableEntries, d_taps, h_taps));
     HIP_TRY(d_count.reserve(1));
     HIP_TRY(h_count.reserve(1));
-    if (!render_bytes && !out_bytes) return GPSIQ_OK;
-    HIP_TRY(rs_stream.ensure());
-    HIP_TRY(copy_stream.ensure());
-    for (auto &e : resampled) HIP_TRY(e.ensure());
-    for (auto &e : copied) HIP_TRY(e.ensure());
-    HIP_TRY(reserve_together(render_bytes, render_bytes + render_bytes / 4 + 256, d_render[0], d_render[1]));
-    HIP_TRY(reserve_together(out_bytes, out_bytes + out_bytes / 4 + 256, d_out[0], d_out[1]));
     return GPSIQ_OK;
 }
 

@@ -1,7 +1,8 @@
 // gpsiq_resample_plan.h -- the output count, the kernel and the grid a gpsiq_resample call (include/gpsiq_rows.h, "Resample") takes,
-// and the piece size of gpsiq_generate_batch_resampled.  Host code only, and pure: no HIP, no environment (the GPSIQ_RESAMPLE_KERNEL
-// and GPSIQ_RESAMPLE_PIECE_BLOCKS overrides are arguments, read per call by the caller).  tests/resample_plan.cpp pins every plan on
-// the CPU.  Not a device source: the geometry the kernels are compiled for is gpsiq_resample_geometry.h.
+// and the staging a piece of gpsiq_generate_batch_resampled asks for.  Host code only, and pure: no HIP, no environment (the
+// GPSIQ_RESAMPLE_KERNEL override is an argument, read per call by the caller; so is GPSIQ_RESAMPLE_PIECE_BLOCKS, for the piece size
+// of the batch call: stage_piece_blocks, gpsiq_pieces.h).  tests/resample_plan.cpp pins every plan on the CPU.  Not a device
+// source: the geometry the kernels are compiled for is gpsiq_resample_geometry.h.
 #ifndef GPSIQ_RESAMPLE_PLAN_H
 #define GPSIQ_RESAMPLE_PLAN_H
 
@@ -9,6 +10,7 @@
 #include <cstdint>
 
 #include "gpsiq_resample_geometry.h"
+#include "gpsiq_pieces.h"
 
 namespace gpsiq {
 
@@ -68,24 +70,9 @@ inline ResamplePlan plan_resample(uint64_t nsamp, int log2_phases, int ntaps, ui
     return p;
 }
 
-// Blocks per piece of gpsiq_generate_batch_resampled: the policy of filter_piece_blocks (gpsiq_filter_plan.h), ~32 MiB of rendered
-// source per piece, at least one block, at most the call's; override_blocks > 0 (GPSIQ_RESAMPLE_PIECE_BLOCKS) replaces the default.
-// A piece is one span of the resampler: its samples fit an int, whatever was asked for (nsamp >= 1).
-inline int resample_piece_blocks(int nblocks, int nsamp, size_t src_block_bytes, long override_blocks)
-{
-    if (nblocks <= 0) return 0;
-    long n;
-    if (override_blocks > 0) n = override_blocks;
-    else {
-        const size_t target = (size_t) 32 << 20;
-        const size_t q = src_block_bytes ? (target + src_block_bytes - 1) / src_block_bytes : (size_t) nblocks;
-        n = q > (size_t) nblocks ? (long) nblocks : (long) q;
-    }
-    const long most = nsamp > 0 ? (long) (INT32_MAX / nsamp) : (long) nblocks;
-    if (n > most) n = most;
-    if (n < 1) n = 1;
-    return n > nblocks ? nblocks : (int) n;
-}
+// Blocks per piece of gpsiq_generate_batch_resampled: the one policy, stage_piece_blocks (gpsiq_pieces.h), under the call's name.  A
+// piece is one span of the resampler: its samples fit an int
+inline int resample_piece_blocks(int nblocks, int nsamp, size_t src_block_bytes, long override_blocks) { return stage_piece_blocks(nblocks, nsamp, src_block_bytes, override_blocks); }
 
 // the outputs a piece of `samples` input samples can give at the most, whatever its pos0: what the batch call sizes its staging by
 inline uint64_t resample_piece_outputs(uint64_t samples, uint64_t step) { return (uint64_t) ((((unsigned __int128) samples << 32) + step - 1) / step); }

@@ -1,5 +1,6 @@
 // filter_own.cpp -- FilterSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device
-// context, on the CPU, in the manner of tests/own_types.cpp (which may not change and so does not know this set).
+// context, and with it PieceRing::reserve (csrc/gpsiq_stage_batch.h), the staging ring the filtered batch call works through its
+// pieces with, on the CPU, in the manner of tests/own_types.cpp.  `Both` below is what that call reserves: its sixteen resources.
 // TEST INFRASTRUCTURE: tests/test_filter_own.py builds this file with the address and undefined-behaviour sanitizers and runs it.
 // No HIP runtime is linked: the entry points gpsiq_own.h calls are counting fakes over malloc / free that share one sequence number,
 // so that "the k-th resource the routine makes" can be made to fail whatever its kind, and that abort on a pointer they do not know.
@@ -73,15 +74,24 @@ int fail(int code, const char *fmt, ...)
 }
 
 using gpsiq::FilterSet;
+using gpsiq::PieceRing;
+
+// what gpsiq_generate_batch_filtered reserves, in its order: the ring, then the filter's own
+struct Both {
+    PieceRing r; FilterSet f;
+    int reserve(size_t render, size_t out) { if (int rc = r.reserve(render, out)) return rc; return f.reserve(); }
+};
 
 template <typename B>
 static bool room(const B &b, size_t n) { return b.get() != nullptr && b.cap() >= n; }
 
-static bool whole(const FilterSet &f, size_t n)
+static bool whole(const Both &b, size_t n)
 {
+    const FilterSet &f = b.f;
+    const PieceRing &r = b.r;
     return room(f.d_coef, FilterSet::kCoefBytes) && room(f.h_coef, FilterSet::kCoefBytes) && room(f.d_count, 1) && room(f.h_count, 1) &&
-           room(f.d_render[0], n) && room(f.d_render[1], n) && room(f.d_out[0], n) && room(f.d_out[1], n) && f.filt_stream.get() && f.copy_stream.get() &&
-           f.t0.get() && f.t1.get() && f.filtered[0].get() && f.filtered[1].get() && f.copied[0].get() && f.copied[1].get();
+           room(r.d_render[0], n) && room(r.d_render[1], n) && room(r.d_out[0], n) && room(r.d_out[1], n) && r.stage_stream.get() && r.copy_stream.get() &&
+           f.t0.get() && f.t1.get() && r.staged[0].get() && r.staged[1].get() && r.copied[0].get() && r.copied[1].get();
 }
 
 int main()
@@ -89,19 +99,19 @@ int main()
     // gpsiq_filter: coefficients, counter and the two timing events alone -- no stream, no staging
     {
         FilterSet f;
-        CHECK(f.reserve(0, 0) == GPSIQ_OK && g_created == 6 && room(f.d_coef, FilterSet::kCoefBytes) && room(f.h_count, 1) && !f.filt_stream.get() && !f.d_render[0].get());
+        CHECK(f.reserve() == GPSIQ_OK && g_created == 6 && room(f.d_coef, FilterSet::kCoefBytes) && room(f.h_count, 1));
         const long before = g_calls;
-        CHECK(f.reserve(0, 0) == GPSIQ_OK && g_calls == before);
+        CHECK(f.reserve() == GPSIQ_OK && g_calls == before);
     }
     reset();
     // first use of the batch call's set: with the k-th resource failing the first attempt reports, the second completes the set --
     // nothing made twice -- and a third makes no call
     long made = 0;
-    { FilterSet f; CHECK(f.reserve(1000, 1000) == GPSIQ_OK && whole(f, 1000)); made = g_created; CHECK((long) g_live.size() == made && made == 16); }
+    { Both f; CHECK(f.reserve(1000, 1000) == GPSIQ_OK && whole(f, 1000)); made = g_created; CHECK((long) g_live.size() == made && made == 16); }
     reset();
     for (long k = 1; k <= made; ++k) {
         {
-            FilterSet f;
+            Both f;
             g_fail_created_at = k;
             g_error[0] = 0;
             CHECK(f.reserve(1000, 1000) == GPSIQ_E_DEVICE && g_error[0] != 0 && (long) g_live.size() == k - 1);
@@ -115,7 +125,7 @@ int main()
     // the staging pairs grow together: a grow step that failed at any of its four allocations is completed by a later, smaller request
     for (long k = 1; k <= 4; ++k) {
         {
-            FilterSet f;
+            Both f;
             CHECK(f.reserve(1000, 1000) == GPSIQ_OK);
             g_fail_created_at = g_created + k;
             CHECK(f.reserve(5000, 5000) == GPSIQ_E_DEVICE);
@@ -123,7 +133,7 @@ int main()
             const long before = g_calls;
             CHECK(f.reserve(1000, 1000) == GPSIQ_OK && g_calls == before);
             CHECK(f.reserve(5000, 5000) == GPSIQ_OK && whole(f, 5000));
-            CHECK(f.d_render[0].cap() == f.d_render[1].cap() && f.d_out[0].cap() == f.d_out[1].cap() && f.d_out[0].cap() == 5000 + 5000 / 4 + 256);
+            CHECK(f.r.d_render[0].cap() == f.r.d_render[1].cap() && f.r.d_out[0].cap() == f.r.d_out[1].cap() && f.r.d_out[0].cap() == 5000 + 5000 / 4 + 256);
         }
         reset();
     }

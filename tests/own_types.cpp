@@ -107,6 +107,7 @@ using gpsiq::Event;
 using gpsiq::Stream;
 using gpsiq::DespreadSet;
 using gpsiq::PackSet;
+using gpsiq::PieceRing;
 using gpsiq::AcquireSet;
 using gpsiq::FollowSet;
 
@@ -312,7 +313,8 @@ int main()
     first_use_recovers<gpsiq_ctx::EvalDev>("device evaluation", [](gpsiq_ctx::EvalDev &e) { return e.reserve(1000, true, true); });
     first_use_recovers<gpsiq_ctx::EvalDev>("repair", [](gpsiq_ctx::EvalDev &e) { return e.reserve_repair(300); });
     first_use_recovers<DespreadSet>("despread", [](DespreadSet &d) { return d.reserve(1000, 1000, 1000); });
-    first_use_recovers<PackSet>("pack", [](PackSet &p) { return p.reserve(1000, 1000); });
+    first_use_recovers<PackSet>("pack", [](PackSet &p) { return p.reserve(); });
+    first_use_recovers<PieceRing>("piece ring", [](PieceRing &r) { return r.reserve(1000, 1000); });
     first_use_recovers<AcquireSet>("acquire", [](AcquireSet &a) { return a.reserve(1000, 1000, 1000, 1000); });
     first_use_recovers<FollowSet>("follow", [](FollowSet &f) { return f.reserve(1000); });
     grow_step_recovers<gpsiq_ctx::Chain>("chain", 5, [](gpsiq_ctx::Chain &k, size_t n) { return k.reserve(n); }, [](const gpsiq_ctx::Chain &k, size_t n) {
@@ -323,24 +325,26 @@ int main()
         return room(e.d_slot, n) && room(e.h_slot, n) && room(e.d_col, n) && room(e.h_col, n); });
     grow_step_recovers<DespreadSet>("despread", 6, [](DespreadSet &d, size_t n) { return d.reserve(n, n, n); }, [](const DespreadSet &d, size_t n) {
         return room(d.d_sums, n) && room(d.h_sums, n) && room(d.d_prn, n) && room(d.h_prn, n) && room(d.d_stats, n) && room(d.h_stats, n); });
-    grow_step_recovers<PackSet>("pack", 4, [](PackSet &p, size_t n) { return p.reserve(n, n); }, [](const PackSet &p, size_t n) {
-        return room(p.d_count, 1) && room(p.h_count, 1) && room(p.d_render[0], n) && room(p.d_render[1], n) && room(p.d_packed[0], n) && room(p.d_packed[1], n); });
+    grow_step_recovers<PieceRing>("piece ring", 4, [](PieceRing &r, size_t n) { return r.reserve(n, n); }, [](const PieceRing &r, size_t n) {
+        return r.stage_stream.get() && r.copy_stream.get() && room(r.d_render[0], n) && room(r.d_render[1], n) && room(r.d_out[0], n) && room(r.d_out[1], n); });
     grow_step_recovers<AcquireSet>("acquire", 5, [](AcquireSet &a, size_t n) { return a.reserve(n, n, n, n); }, [](const AcquireSet &a, size_t n) {
         return room(a.d_prn, 32) && room(a.h_prn, 32) && room(a.d_power, n) && room(a.d_peaks, n) && room(a.h_peaks, n) && room(a.d_corr, n) && room(a.d_planes, n); });
     grow_step_recovers<FollowSet>("follow", 1, [](FollowSet &f, size_t n) { return f.reserve(n); }, [](const FollowSet &f, size_t n) {
         return room(f.d_state, 32) && room(f.h_state, 32) && room(f.d_count, 32) && room(f.h_count, 32) && room(f.d_epochs, n); });
     // the sizes a grown stage set ends with are each site's own: n + n/4 + 256, but + 16 for the stream statistics and + 64 for peaks and records
     {
-        DespreadSet d; AcquireSet a; FollowSet f; PackSet p;
+        DespreadSet d; AcquireSet a; FollowSet f; PieceRing p;
         CHECK(d.reserve(5000, 5000, 5000) == GPSIQ_OK && a.reserve(5000, 5000, 5000, 5000) == GPSIQ_OK && f.reserve(5000) == GPSIQ_OK && p.reserve(5000, 5000) == GPSIQ_OK);
         const size_t base = 5000 + 5000 / 4;
         CHECK(d.d_sums.cap() == base + 256 && d.h_sums.cap() == base + 256 && d.d_prn.cap() == base + 256 && d.h_prn.cap() == base + 256);
         CHECK(d.d_stats.cap() == base + 16 && d.h_stats.cap() == base + 16);
         CHECK(a.d_power.cap() == base + 256 && a.d_peaks.cap() == base + 64 && a.h_peaks.cap() == base + 64 && a.d_corr.cap() == base + 256 && a.d_planes.cap() == base + 256);
         CHECK(f.d_epochs.cap() == base + 64);
-        CHECK(p.d_render[0].cap() == base + 256 && p.d_render[1].cap() == base + 256 && p.d_packed[0].cap() == base + 256 && p.d_packed[1].cap() == base + 256);
-        PackSet q;                                                                   // gpsiq_pack / gpsiq_unpack: the counter alone, no stream
-        CHECK(q.reserve(0, 0) == GPSIQ_OK && room(q.d_count, 1) && room(q.h_count, 1) && !q.pack_stream.get() && !q.d_render[0].get());
+        CHECK(p.d_render[0].cap() == base + 256 && p.d_render[1].cap() == base + 256 && p.d_out[0].cap() == base + 256 && p.d_out[1].cap() == base + 256);
+        PackSet q;                                                                   // the packer's own: the counter and its timing events
+        CHECK(q.reserve() == GPSIQ_OK && room(q.d_count, 1) && room(q.h_count, 1) && q.t0.get() && q.t1.get());
+        PieceRing m;                                                                 // a stage that works in place: no output pair
+        CHECK(m.reserve(100, 0) == GPSIQ_OK && room(m.d_render[0], 100) && room(m.d_render[1], 100) && !m.d_out[0].get() && !m.d_out[1].get());
         AcquireSet g;                                                                // the generic kernel without correlations: neither buffer made
         CHECK(g.reserve(100, 10, 0, 0) == GPSIQ_OK && !g.d_corr.get() && !g.d_planes.get() && room(g.d_power, 100));
     }
@@ -362,7 +366,7 @@ int main()
         CHECK(c.d_tab.reserve(1) == hipSuccess && c.buf[2].h_patch.reserve(256) == hipSuccess && c.aslot[3].out.reserve(16) == hipSuccess);
         CHECK(c.buf[0].use[3].ev.ensure() == hipSuccess && c.d_noise_tab.reserve(4) == hipSuccess && c.d_zero_tab.reserve(4) == hipSuccess);
         CHECK(c.chain.reserve(10) == GPSIQ_OK && c.evd.reserve(10, false, false) == GPSIQ_OK);
-        CHECK(c.dsp.reserve(10, 10, 1) == GPSIQ_OK && c.pack.reserve(10, 10) == GPSIQ_OK && c.acq.reserve(10, 10, 10, 10) == GPSIQ_OK && c.fol.reserve(10) == GPSIQ_OK);
+        CHECK(c.dsp.reserve(10, 10, 1) == GPSIQ_OK && c.pack.reserve() == GPSIQ_OK && c.ring.reserve(10, 10) == GPSIQ_OK && c.acq.reserve(10, 10, 10, 10) == GPSIQ_OK && c.fol.reserve(10) == GPSIQ_OK);
     }
     reset();
     std::printf("own types ok\n");

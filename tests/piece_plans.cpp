@@ -2,7 +2,9 @@
 // counts and GPSIQ_PIECE_BLOCKS overrides.  TEST INFRASTRUCTURE: tests/test_piece_plans.py holds the lines against its tables.
 //   one line per planner and configuration; on it the result without the override, then with it at 0 1 2 3 5 8 40 -1 (" | ")
 //   a list of pieces is printed as their sizes, runs of equal sizes as size x count
+// With the argument "handover": the phase hand-over between the pieces of the staged batch calls (piece_rows), one line per case.
 #include <cstdio>
+#include <cstring>
 #include <optional>
 #include <string>
 #include <vector>
@@ -37,8 +39,56 @@ template <class F> static void line(const std::string &head, F result)
     std::printf("%s\n", s.c_str());
 }
 
-int main()
+// Five blocks of nchan slots cut at block 2.  Slot i is of kind (i + shift) % 4: 0 keeps its satellite across the edge, 1 changes it
+// there, 2 has none (prn 0) on either side, 3 loses it there (prn 0 from the edge on).  Every carr_phase and every carried phase is a
+// value of its own, so a row that took the wrong one shows.  Returns the number of checks that failed.
+static int handover_case(int nchan, int shift)
 {
+    const int nblocks = 5, b0 = 2, nb = nblocks - b0;
+    std::vector<gpsiq_chan_t> ch((size_t) nblocks * nchan);
+    std::memset(ch.data(), 0, ch.size() * sizeof(gpsiq_chan_t));
+    double carr[GPSIQ_MAX_CHAN];
+    for (int i = 0; i < GPSIQ_MAX_CHAN; ++i) carr[i] = -7.5 - i;
+    for (int b = 0; b < nblocks; ++b)
+        for (int i = 0; i < nchan; ++i) {
+            gpsiq_chan_t &r = ch[(size_t) b * nchan + i];
+            const int kind = (i + shift) % 4;
+            r.prn = kind == 0 ? i + 1 : kind == 1 ? (b < b0 ? i + 1 : i + 17) : kind == 2 ? 0 : (b < b0 ? i + 1 : 0);
+            r.carr_phase = 1000.0 * b + i + 0.25;
+            r.f_carr = 10.0 * b + i;
+        }
+    const std::vector<gpsiq_chan_t> before = ch;
+    int bad = 0;
+    std::vector<gpsiq_chan_t> row;
+    // piece 0: the caller's rows as they lie, nothing copied
+    bad += piece_rows(ch.data(), 0, b0, nchan, carr, &row) != ch.data() || !row.empty();
+    // a later piece: a copy, its first row rewritten where the slot keeps its satellite, every other byte the caller's
+    const gpsiq_chan_t *rows = piece_rows(ch.data(), b0, nb, nchan, carr, &row);
+    bad += rows != row.data() || row.size() != (size_t) nb * nchan || rows == ch.data() + (size_t) b0 * nchan;
+    for (int i = 0; i < nchan; ++i) {
+        const int kind = (i + shift) % 4;
+        gpsiq_chan_t want = before[(size_t) b0 * nchan + i];
+        if (kind == 0) want.carr_phase = carr[i];                     // kinds 1, 2, 3: its own carr_phase, untouched
+        bad += std::memcmp(&rows[i], &want, sizeof want) != 0;
+        bad += kind == 0 && rows[i].carr_phase == before[(size_t) b0 * nchan + i].carr_phase;
+    }
+    bad += std::memcmp(rows + nchan, before.data() + (size_t) (b0 + 1) * nchan, (size_t) (nb - 1) * nchan * sizeof(gpsiq_chan_t)) != 0;
+    bad += std::memcmp(ch.data(), before.data(), ch.size() * sizeof(gpsiq_chan_t)) != 0;      // the caller's rows are read only
+    return bad;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && !std::strcmp(argv[1], "handover")) {
+        int bad = 0;
+        for (int nchan : {1, 3, GPSIQ_MAX_CHAN})
+            for (int shift = 0; shift < 4; ++shift) {
+                const int b = handover_case(nchan, shift);
+                std::printf("handover nchan=%d shift=%d: %s\n", nchan, shift, b ? "WRONG" : "ok");
+                bad += b;
+            }
+        return bad != 0;
+    }
     for (int nsamp : {260000, 1000000, 2500000, 33333})
         for (int ss : {1, 2}) {
             const size_t stride = ((size_t) 2 * nsamp * ss + 15) & ~(size_t) 15;

@@ -1,7 +1,8 @@
-"""FilterSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device context, on the CPU:
+"""FilterSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device context, and
+PieceRing::reserve (csrc/gpsiq_stage_batch.h), that of the staging ring its batch call works through its pieces with, on the CPU:
 tests/filter_own.cpp defines the HIP entry points csrc/gpsiq_own.h calls as counting fakes over malloc / free and is built with the
-address and undefined-behaviour sanitizers; no HIP runtime is linked.  It checks that gpsiq_filter's share of the set makes neither a
-stream nor a staging buffer, that the batch call's set completes on the attempt after a failure at any one of its sixteen resources
+address and undefined-behaviour sanitizers; no HIP runtime is linked.  It checks that gpsiq_filter's share is six resources, neither a
+stream nor a staging buffer among them, that what the batch call reserves (ring and set) completes on the attempt after a failure at any one of its sixteen resources
 with nothing made twice, that a grow step of the staging pairs which failed at any member is completed by a later, smaller request,
 and that nothing is released twice or left alive."""
 import os

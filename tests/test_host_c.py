@@ -159,9 +159,9 @@ def test_exact_mode_header_compiles_on_its_own(header):
     assert r.returncode == 0, r.stderr[-2000:]
 
 
-@pytest.mark.parametrize("header", ["gpsiq_own.h", "gpsiq_despread.h", "gpsiq_pack.h", "gpsiq_acquire.h", "gpsiq_follow.h"])
+@pytest.mark.parametrize("header", ["gpsiq_own.h", "gpsiq_despread.h", "gpsiq_pack.h", "gpsiq_acquire.h", "gpsiq_follow.h", "gpsiq_stage_batch.h"])
 def test_stage_header_compiles_on_its_own(header):
-    """The owning types and each stream stage's header are interfaces of their own (the context includes them, not the other way
+    """The owning types, each stream stage's header and the staged batch calls' are interfaces of their own (the context includes them, not the other way
     round): a translation unit of nothing but the include compiles, against the HIP runtime's host declarations alone."""
     csrc = os.path.join(ROOT, "multi-sdr-gps-sim_amd", "csrc")
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",

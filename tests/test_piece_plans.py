@@ -341,11 +341,27 @@ device nsamp=2500000 nchan=16 host_rows=1 reference=1 nblocks=1000000: 53 424 33
 """
 
 
-def test_piece_plans_are_the_tables(tmp_path):
+def build(tmp_path, *flags):
     exe = str(tmp_path / "piece_plans")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, "-o", exe,
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", *flags, "-I" + CSRC, "-o", exe,
                     os.path.join(ROOT, "tests", "piece_plans.cpp")], check=True)
-    got = subprocess.run([exe], capture_output=True, text=True, check=True, timeout=120).stdout.splitlines()
+    return exe
+
+
+def test_phase_hand_over_between_pieces(tmp_path):
+    """piece_rows (csrc/gpsiq_pieces.h), what the pieces of the staged batch calls hand each other on the host, with no HIP and under
+    ASan + UBSan: piece 0 uses the caller's rows as they lie; in a later piece a slot with prn > 0 equal to the row before takes the
+    carried phase, a slot whose prn changes at the edge (to another satellite, or to none) keeps its own carr_phase, prn == 0 is
+    untouched, and every row but the piece's first is byte-equal to the input -- for 1, 3 and GPSIQ_MAX_CHAN (16) channels, with each
+    kind of slot in every position."""
+    run = subprocess.run([build(tmp_path, "-fsanitize=address,undefined"), "handover"], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+    assert run.stdout.splitlines() == ["handover nchan=%d shift=%d: ok" % (n, s) for n in (1, 3, 16) for s in range(4)]
+
+
+def test_piece_plans_are_the_tables(tmp_path):
+    got = subprocess.run([build(tmp_path)], capture_output=True, text=True, check=True, timeout=120).stdout.splitlines()
     want = EXPECTED.splitlines()
     assert len(got) == len(want)
     for g, w in zip(got, want):
