@@ -709,6 +709,81 @@ int gpsiq_generate_batch_resampled(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int
                                    int out_sample_size, void *dst_host, uint64_t dst_capacity /* samples */, uint64_t *nout,
                                    uint64_t *clipped, double *carr_phase_out);
 
+/* ---- AGC: windowed device gain control, pulse blanker and requantiser -------------------------------------------------------------------
+ * The stage between the analogue side and a narrow quantiser.  gpsiq_set_level and the shifts of the filter and the mixer are fixed
+ * multipliers, right for the power the caller worked out beforehand; once gpsiq_mix adds a jammer or a pulsed interferer they are not.
+ * This stage measures: the gain is feed-forward, constant over a window of W samples, and a pure function of exact integer power sums
+ * of the windows before it; the blanker's threshold is absolute.  No sample-serial loop anywhere, integers only: a restatement in
+ * numpy (tests/_agc_ref.py) agrees with the device byte for byte.
+ *
+ * Input.  src is ONE contiguous span of nsamp complex samples as gpsiq_filter takes it: interleaved I,Q, int8 for GPSIQ_SC08 and int16
+ * for GPSIQ_SC16, elements as stored, base 4-byte aligned, device or page-locked memory.  dst receives exactly nsamp complex samples
+ * of out_sample_size, in any of the four combinations.
+ * Windows belong to the stream, not to the span.  The first W - state.fill samples of a span complete the window in progress;
+ * nwin = ceil((fill + nsamp) / W) windows are touched and next_fill = (fill + nsamp) % W (gpsiq_agc_span: host arithmetic, either
+ * result pointer may be NULL).  mults[i] is the multiplier of the i-th touched window.
+ * Blanker.  exceed(m) holds iff blank_thresh > 0 and (|I(m)| > blank_thresh or |Q(m)| > blank_thresh), elements as stored.  blank(m)
+ * holds iff m < state.hold, or exceed(e) holds for some e in [max(0, m - H), m], H = blank_hold.  Blanked samples are written as
+ * (0, 0), counted in *blanked (in samples), and take no part in the power or in *clipped.  hold_out = max(0, hold_in - nsamp,
+ * H - (nsamp - 1 - e_last)), the last term only where the span holds an exceeding sample, e_last the last one.
+ * Power.  For a window, sum is the sum of I^2 + Q^2 over its unblanked samples and cnt is 2 per unblanked sample.  When a window
+ * completes it enters the ring, which keeps the last M = navg.
+ * Gain rule (exactly what gpsiq_agc_mult returns).  The multiplier of a window is fixed at the window's start, from S, the sum of wsum,
+ * and n, the sum of wcnt, over the ring at that moment.  The ring does not change while a window is in progress, so a window continued
+ * in the next call gets the same multiplier again.  n == 0 (which includes nring == 0): mult0.  Otherwise m = floor(S * 2^16 / n),
+ * computed as ((S / n) << 16) + (((S % n) << 16) / n) -- the same value, inside 64 bits: S <= 2^53, n <= 2^23 --, r = max(isqrt(m), 1),
+ * the floor square root: the rms in 1/256 units; mult = min(max(floor((target_q8 << 16) / r), mult_min), mult_max).
+ * Output.  For I and Q alike y = floor((x * mult + 32768) / 65536) in 64 bits, the formula of the output level stage, and
+ * out = min(max(y, -qmax), qmax).  *clipped counts the elements of unblanked samples that the clamp changed.
+ * Ranges.  Those written at the members below; anything outside is GPSIQ_E_ARG, as is a state that cannot have come from a call with
+ * this window and navg (nring > navg, fill >= window, pcnt > 2 * fill, hold > blank_hold), a NULL cfg, a pointer that is not 4-byte
+ * aligned, and src and dst that overlap: there is no in-place form, the blanker reads input behind its output.  nsamp == 0 launches
+ * nothing and returns GPSIQ_OK with counts of 0 and the state unchanged.  Entries of wsum / wcnt from nring on are zeros, in and out.
+ * Stream order and return as gpsiq_filter's: all work is queued on hip_stream (a hipStream_t, NULL = the null stream) behind the
+ * caller's producer there; the call then waits, fetches counts, multipliers and state, and returns.  The same call twice gives the
+ * same bytes.  Bytes past 2 * nsamp * out_sample_size of dst are never written, bytes past the span never read; offsets are 64-bit.
+ * Continuation is part of the contract: a span processed in pieces, each called with the state the piece before returned, gives
+ * exactly what one call over the whole span gives -- the bytes, both counts, the concatenated multipliers (a window continued across
+ * a call repeats its multiplier as the next call's mults[0]) and the final state.
+ *
+ * gpsiq_agc_mult(cfg, sumsq, count) is the gain rule on the host, for S = sumsq <= 2^53 and n = count <= 2^23.
+ *
+ * gpsiq_generate_batch_agc is the piece loop of the staged batch calls with this stage in the filter's place: a piece is rendered at
+ * sample_size into one of two device staging buffers, taken through the stage on a side stream, and crosses to HOST memory (pageable
+ * or page-locked) while the next piece renders.  The state stays on the device from piece to piece; it comes back once, behind the
+ * last piece.  Output block b is nsamp samples of out_sample_size at dst_host + b * dst_block_stride.  Byte for byte, count for count,
+ * state for state and carr_phase_out bit for bit it equals gpsiq_agc -- given the same state, or a fresh one -- of what ONE
+ * gpsiq_generate_batch over the whole timeline writes, in both NCO models, with noise and level.  ch is host memory only.
+ * GPSIQ_AGC_PIECE_BLOCKS=n in the environment, read per call, sets the blocks per piece (default: about 32 MiB of rendered stream). */
+typedef struct gpsiq_agc_cfg {
+    int32_t  window;      /* W: samples per gain window; a multiple of 64, 64..65536 */
+    int32_t  navg;        /* M: complete windows the power is averaged over, 1..64 */
+    uint32_t target_q8;   /* wanted rms per component of the output, in 1/256 output units; 1 .. 2^23-1 */
+    uint32_t mult0;       /* Q16 multiplier while no window has completed, and for windows whose average holds no element */
+    uint32_t mult_min, mult_max;   /* 1 <= mult_min <= mult_max < 2^24, and mult0 inside them */
+    int32_t  blank_thresh;         /* 0: blanker off; else 1..32767, in input elements as stored */
+    int32_t  blank_hold;           /* H: samples blanked behind an exceeding one, 0..1024 */
+    int32_t  qmax;                 /* symmetric output clamp: 1..127 for an int8 dst, 1..32767 for int16 */
+} gpsiq_agc_cfg_t;
+
+typedef struct gpsiq_agc_state {   /* all zeros: a fresh stream */
+    uint64_t wsum[64];  uint32_t wcnt[64];   /* the last nring complete windows, oldest first: sum of squares, elements counted */
+    uint64_t psum;      uint32_t pcnt;       /* the window in progress */
+    uint32_t fill;                           /* samples of it already seen, 0..W-1 */
+    uint32_t nring;                          /* 0..M */
+    uint32_t hold;                           /* samples at the start of the next span that are blanked whatever they hold, 0..H */
+} gpsiq_agc_state_t;
+
+int gpsiq_agc(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const gpsiq_agc_cfg_t *cfg,
+              gpsiq_agc_state_t *state /* host, in and out; NULL: fresh and not returned */,
+              int out_sample_size, void *dst, void *hip_stream,
+              uint32_t *mults /* host [nwin], may be NULL */, uint64_t *clipped, uint64_t *blanked, float *kernel_ms /* each may be NULL */);
+int gpsiq_agc_mult(const gpsiq_agc_cfg_t *cfg, uint64_t sumsq, uint64_t count, uint32_t *mult);          /* host arithmetic: the gain rule */
+int gpsiq_agc_span(uint64_t nsamp, int window, uint32_t fill, uint64_t *nwin, uint32_t *next_fill);      /* host arithmetic */
+int gpsiq_generate_batch_agc(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp, double fs, int sample_size,
+                             const gpsiq_agc_cfg_t *cfg, gpsiq_agc_state_t *state, int out_sample_size,
+                             void *dst_host, size_t dst_block_stride, uint64_t *clipped, uint64_t *blanked, double *carr_phase_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -33,7 +33,8 @@ void *gpsiq_plumbing(const char *name);
  * csrc/gpsiq_follow.cpp).  "filter" and "generate_batch_filtered" are gpsiq_filter and gpsiq_generate_batch_filtered (ibid., "Filter";
  * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp).  "mix" and
  * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp).  "resample" and
- * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp). */
+ * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp).  "agc" and
+ * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -221,6 +222,14 @@ int gpsiq_mix_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
  * workgroup's threads for the generic one), out[3] the pieces of a batch call (0: not one; a batch call reports the plan of its first
  * piece). */
 int gpsiq_resample_last_plan(const gpsiq_ctx_t *ctx, long long out[4]);
+/* What the context's last gpsiq_agc / gpsiq_generate_batch_agc took (csrc/gpsiq_agc_plan.h): out[0] the grid of agc_measure, one workgroup
+ * per tile (-1: nothing was launched, or no call yet), out[1] the samples of a tile, out[2] the grid of agc_gains, out[3] the grid of
+ * agc_apply, out[4] the samples of one of its workgroups, out[5] the pieces of a batch call (0: not one; a batch call reports the plan
+ * of its first piece). */
+int gpsiq_agc_last_plan(const gpsiq_ctx_t *ctx, long long out[6]);
+/* The device time, in milliseconds, of the three launches of the context's last gpsiq_agc that launched anything: agc_measure, agc_gains,
+ * agc_apply (scripts/agc_rates.py). */
+int gpsiq_agc_last_ms(const gpsiq_ctx_t *ctx, float out[3]);
 
 #ifdef __cplusplus
 }

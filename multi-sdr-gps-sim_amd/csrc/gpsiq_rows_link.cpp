@@ -196,3 +196,23 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_resam
     return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, taps, log2_phases, ntaps, shift, interp, step, pos0, out_sample_size, dst_host, dst_capacity, nout,
              clipped, carr_phase_out);
 }
+
+// The gain control runs on the context's device (csrc/gpsiq_agc.cpp) and is exported here like the filter (include/gpsiq_rows.h,
+// "AGC"); gpsiq_agc_mult and gpsiq_agc_span, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_agc(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const gpsiq_agc_cfg_t *cfg,
+                                                                gpsiq_agc_state_t *state, int out_sample_size, void *dst, void *hip_stream, uint32_t *mults,
+                                                                uint64_t *clipped, uint64_t *blanked, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_agc)>("agc");
+    return f(ctx, nsamp, sample_size, src, cfg, state, out_sample_size, dst, hip_stream, mults, clipped, blanked, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_agc(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nblocks, int nchan, int nsamp,
+                                                                               double fs, int sample_size, const gpsiq_agc_cfg_t *cfg,
+                                                                               gpsiq_agc_state_t *state, int out_sample_size, void *dst_host,
+                                                                               size_t dst_block_stride, uint64_t *clipped, uint64_t *blanked,
+                                                                               double *carr_phase_out)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_agc)>("generate_batch_agc");
+    return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, cfg, state, out_sample_size, dst_host, dst_block_stride, clipped, blanked, carr_phase_out);
+}

@@ -1,4 +1,4 @@
-// gpsiq_stage_batch.cpp -- the piece loop of gpsiq_generate_batch_packed / _filtered / _mixed / _resampled (gpsiq_stage_batch.h says
+// gpsiq_stage_batch.cpp -- the piece loop of gpsiq_generate_batch_packed / _filtered / _mixed / _resampled / _agc (gpsiq_stage_batch.h says
 // what it does and what a stage gives it): the one place that holds pair reuse, the history's way from pair to pair, stream order,
 // the drain and the counter that is read only if it was written.  Host code: nothing here decides device code, so the file is not
 // one of the device sources behind gpsiq_kernels_id().
@@ -46,7 +46,7 @@ int gpsiq_stage_batch_run(gpsiq_ctx *c, const StageBatch &st, int rc, const gpsi
         if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "%s piece: %s", st.label, hipGetErrorString(e));
     }
     if (rc == GPSIQ_OK && nsamp) {                                    // the pieces' sum, behind the last piece's work
-        const hipError_t e = hipMemcpyAsync(st.h_count, st.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ss);
+        const hipError_t e = hipMemcpyAsync(st.h_count, st.d_count, sizeof(unsigned long long) * st.count_words, hipMemcpyDeviceToHost, ss);
         if (e != hipSuccess) rc = fail(GPSIQ_E_DEVICE, "%s count: %s", st.label, hipGetErrorString(e));
     }
     // nothing of the call may still read the staging or write dst when it returns, on any path

@@ -1,4 +1,4 @@
-// gpsiq_stage_batch.h -- the piece loop of the staged batch calls gpsiq_generate_batch_packed / _filtered / _mixed / _resampled
+// gpsiq_stage_batch.h -- the piece loop of the staged batch calls gpsiq_generate_batch_packed / _filtered / _mixed / _resampled / _agc
 // (include/gpsiq_rows.h) and the staging ring the device context holds for them (gpsiq_ctx.h: the member `ring`).  Host code.  The
 // loop is in gpsiq_stage_batch.cpp; the piece size (stage_piece_blocks) and the phase hand-over (piece_rows) are pure and in
 // gpsiq_pieces.h.  A stage's own share of such a call -- checks, plan, tables, kernels -- stays in gpsiq_<stage>.cpp.
@@ -56,6 +56,9 @@ struct StageBatch {
     int         piece;                 // blocks per piece
     const unsigned long long *d_count; // the stage's counter of clamped elements, zeroed by the stage before the first piece ...
     unsigned long long       *h_count; // ... and its page-locked twin, read once behind the last piece
+    // 64-bit words that come back from d_count to h_count behind the last piece.  The first is the counter; a stage with more to
+    // fetch (gpsiq_generate_batch_agc: a second counter and the state it kept on the device) lays it out behind that word
+    size_t      count_words = 1;
 };
 
 // a piece as the stage sees it: blocks [b0, b0 + nb) of the call, rendered back to back at span = d_render[pair] + lead

@@ -2,13 +2,14 @@
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
 // and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix, the
-// output count, the step and the tap table of a resampler.  Host code of libgpsiq_rows.so; nothing here touches a context or the
+// output count, the step and the tap table of a resampler, the gain rule and the windows of a gain control.  Host code of libgpsiq_rows.so; nothing here touches a context or the
 // device (the calls themselves: gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
 #include "gpsiq_spectrum_plan.h"
 #include "gpsiq_mix_geometry.h"
 #include "gpsiq_resample_plan.h"
+#include "gpsiq_agc_plan.h"
 
 #include <cmath>
 
@@ -350,6 +351,32 @@ int gpsiq_resample_design(uint64_t step, double bandwidth, int log2_phases, int 
         if (mag > kRsTapSum || q[big] > 32767) return fail(GPSIQ_E_RANGE, "row %d outside the resampler's range (sum |taps| %ld)", r, mag);
         for (int k = 0; k < ntaps; ++k) row[k] = (int16_t) q[k];
     }
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "AGC": the gain rule (agc_gain, gpsiq_agc_geometry.h -- the function the gains kernel evaluates) under the
+// ranges of the configuration it reads
+int gpsiq_agc_mult(const gpsiq_agc_cfg_t *cfg, uint64_t sumsq, uint64_t count, uint32_t *mult)
+{
+    if (!cfg || !mult) return fail(GPSIQ_E_ARG, "null argument");
+    if (cfg->target_q8 < 1 || cfg->target_q8 > kAgcMaxTarget) return fail(GPSIQ_E_ARG, "target_q8 %u outside 1..2^23-1", (unsigned) cfg->target_q8);
+    if (cfg->mult_min < 1 || cfg->mult_min > cfg->mult_max || cfg->mult_max > kAgcMaxMult || cfg->mult0 < cfg->mult_min || cfg->mult0 > cfg->mult_max)
+        return fail(GPSIQ_E_ARG, "multipliers: 1 <= mult_min %u <= mult0 %u <= mult_max %u < 2^24", (unsigned) cfg->mult_min, (unsigned) cfg->mult0, (unsigned) cfg->mult_max);
+    if (sumsq > kAgcMaxSum || count > kAgcMaxCount) return fail(GPSIQ_E_ARG, "sum %llu at most 2^53, count %llu at most 2^23", (unsigned long long) sumsq, (unsigned long long) count);
+    *mult = agc_gain(sumsq, count, cfg->target_q8, cfg->mult0, cfg->mult_min, cfg->mult_max);
+    return GPSIQ_OK;
+}
+
+// ibid.: the windows a span touches and the fill it leaves (agc_span, gpsiq_agc_plan.h)
+int gpsiq_agc_span(uint64_t nsamp, int window, uint32_t fill, uint64_t *nwin, uint32_t *next_fill)
+{
+    if (window < kAgcMinWindow || window > kAgcMaxWindow || window % 64 || fill >= (uint32_t) window || nsamp >= (UINT64_C(1) << 60))
+        return fail(GPSIQ_E_ARG, "window %d a multiple of 64 in %d..%d, fill %u below it, nsamp %llu below 2^60", window, kAgcMinWindow, kAgcMaxWindow, (unsigned) fill, (unsigned long long) nsamp);
+    uint64_t n = 0;
+    uint32_t next = 0;
+    agc_span(nsamp, (uint32_t) window, fill, &n, &next);
+    if (nwin) *nwin = n;
+    if (next_fill) *next_fill = next;
     return GPSIQ_OK;
 }
 

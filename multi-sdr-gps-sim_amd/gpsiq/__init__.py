@@ -194,6 +194,35 @@ _resample_design = _sig("gpsiq_resample_design", _i, _u64, _d, _i, _i, _i, _vp)
 _generate_batch_resampled = _sig("gpsiq_generate_batch_resampled", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _u64, _u64, _i, _vp, _u64,
                                  C.POINTER(_u64), C.POINTER(_u64), _vp)
 _resample_last_plan = _sig("gpsiq_resample_last_plan", _i, _vp, _vp)
+_agc = _sig("gpsiq_agc", _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_float))
+_agc_mult = _sig("gpsiq_agc_mult", _i, _vp, _u64, _u64, C.POINTER(C.c_uint32))
+_agc_span = _sig("gpsiq_agc_span", _i, _u64, _i, C.c_uint32, C.POINTER(_u64), C.POINTER(C.c_uint32))
+_generate_batch_agc = _sig("gpsiq_generate_batch_agc", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _vp, _sz, C.POINTER(_u64), C.POINTER(_u64), _vp)
+_agc_last_plan = _sig("gpsiq_agc_last_plan", _i, _vp, _vp)
+_agc_last_ms = _sig("gpsiq_agc_last_ms", _i, _vp, _vp)
+
+
+class AgcCfg(C.Structure):
+    """gpsiq_agc_cfg_t (include/gpsiq_rows.h, "AGC")."""
+    _fields_ = [("window", C.c_int32), ("navg", C.c_int32), ("target_q8", C.c_uint32), ("mult0", C.c_uint32), ("mult_min", C.c_uint32),
+                ("mult_max", C.c_uint32), ("blank_thresh", C.c_int32), ("blank_hold", C.c_int32), ("qmax", C.c_int32)]
+
+    def __init__(self, window=1024, navg=16, target_q8=256, mult0=65536, mult_min=1, mult_max=(1 << 24) - 1, blank_thresh=0, blank_hold=0, qmax=127):
+        super().__init__(window, navg, target_q8, mult0, mult_min, mult_max, blank_thresh, blank_hold, qmax)
+
+
+class AgcState(C.Structure):
+    """gpsiq_agc_state_t (ibid.): all zeros is a fresh stream."""
+    _fields_ = [("wsum", C.c_uint64 * 64), ("wcnt", C.c_uint32 * 64), ("psum", C.c_uint64), ("pcnt", C.c_uint32), ("fill", C.c_uint32),
+                ("nring", C.c_uint32), ("hold", C.c_uint32)]
+
+    def as_tuple(self):
+        return (tuple(self.wsum), tuple(self.wcnt), int(self.psum), int(self.pcnt), int(self.fill), int(self.nring), int(self.hold))
+
+    def copy(self):
+        other = AgcState()
+        C.memmove(C.byref(other), C.byref(self), C.sizeof(AgcState))
+        return other
 
 
 class NoiseSettings(C.Structure):
@@ -786,6 +815,25 @@ def resample_span(nsamp, pos0, step):
     return int(nout.value), int(nxt.value)
 
 
+def agc_mult(cfg, sumsq, count):
+    """gpsiq_agc_mult: the gain rule -- the Q16 multiplier of a window whose ring holds `sumsq` as its sum of squares over `count`
+    elements."""
+    mult = C.c_uint32(0)
+    _check(_agc_mult(C.byref(cfg) if cfg is not None else None, _u64_arg(sumsq, "sumsq"), _u64_arg(count, "count"), C.byref(mult)))
+    return int(mult.value)
+
+
+def agc_span(nsamp, window, fill=0):
+    """gpsiq_agc_span: (windows a span of nsamp samples touches when `fill` samples of the window in progress lie before it, the fill it
+    leaves)."""
+    nwin, nxt = _u64(0), C.c_uint32(0)
+    fill = int(fill)
+    if not 0 <= fill < 2 ** 32:
+        raise GpsiqError(-1, f"fill {fill} does not fit 32 unsigned bits")
+    _check(_agc_span(_u64_arg(nsamp, "nsamp"), int(window), fill, C.byref(nwin), C.byref(nxt)))
+    return int(nwin.value), int(nxt.value)
+
+
 def resample_step(fs_in, fs_out, ppb=0.0):
     """gpsiq_resample_step: the step from a stream at fs_in to a receiver at fs_out whose clock runs ppb parts per billion fast."""
     step = _u64(0)
@@ -1262,6 +1310,53 @@ class Context:
         out = (C.c_longlong * 4)()
         _check(_resample_last_plan(self._h, out))
         return {0: "generic", 1: "rows"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def agc(self, nsamp, sample_size, device_ptr, cfg, out_sample_size, dst_device_ptr, state=None, stream=None):
+        """gpsiq_agc: the nsamp complex samples at device_ptr through the blanker, the windowed gain and the clamp of `cfg` (AgcCfg) into
+        out_sample_size at dst_device_ptr.  state: an AgcState, updated in place (None: a fresh stream, nothing returned) -> (elements
+        the clamp changed, samples blanked, uint32 multipliers of the windows touched, kernel milliseconds)."""
+        fill = 0 if state is None else int(state.fill)
+        window = int(cfg.window) if cfg is not None else 0
+        nwin = (fill + int(nsamp) + window - 1) // window if window > 0 and int(nsamp) > 0 else 0
+        mults = np.zeros(max(nwin, 1), dtype=np.uint32)
+        clipped, blanked, ms = _u64(0), _u64(0), C.c_float(0.0)
+        _check(_agc(self._h, int(nsamp), int(sample_size), _vp(device_ptr), C.byref(cfg) if cfg is not None else None,
+                    C.byref(state) if state is not None else None, int(out_sample_size), _vp(dst_device_ptr), _vp(stream or 0), _p(mults),
+                    C.byref(clipped), C.byref(blanked), C.byref(ms)))
+        return int(clipped.value), int(blanked.value), mults[:nwin], float(ms.value)
+
+    def generate_batch_agc(self, desc, nsamp, fs, sample_size, cfg, out_sample_size, state=None, host_ptr=None, block_stride=None, carr_out=None):
+        """gpsiq_generate_batch_agc: the run-ahead call rendered at sample_size and taken through gpsiq_agc on the device, with blocks of
+        nsamp samples of out_sample_size in host memory; state as agc().  Returns (int8 / int16 [nblocks][2 * nsamp], elements the clamp
+        changed, samples blanked), the array None when host_ptr names the caller's buffer (pageable or page-locked; block_stride bytes
+        between blocks, default: back to back)."""
+        desc = np.ascontiguousarray(desc, dtype=CHAN_DTYPE)
+        nb, nc = desc.shape
+        rlen = 2 * int(nsamp) * int(out_sample_size)
+        stride = rlen if block_stride is None else int(block_stride)
+        co = None if carr_out is None else _p(carr_out)
+        clipped, blanked = _u64(0), _u64(0)
+        out = None if host_ptr is not None else np.zeros((nb, max(stride, 1)), dtype=np.uint8)
+        _check(_generate_batch_agc(self._h, _p(desc), nb, nc, int(nsamp), float(fs), int(sample_size), C.byref(cfg) if cfg is not None else None,
+                                   C.byref(state) if state is not None else None, int(out_sample_size), _vp(host_ptr) if out is None else _p(out),
+                                   stride, C.byref(clipped), C.byref(blanked), co))
+        if out is None:
+            return None, int(clipped.value), int(blanked.value)
+        return (np.ascontiguousarray(out[:, :rlen]).view(np.int8 if int(out_sample_size) == 1 else np.int16), int(clipped.value),
+                int(blanked.value))
+
+    def agc_last_plan(self):
+        """What the last agc() / generate_batch_agc() took: (grid of agc_measure or None, samples of a tile, grid of agc_gains, grid of
+        agc_apply, samples of one of its workgroups, pieces)."""
+        out = (C.c_longlong * 6)()
+        _check(_agc_last_plan(self._h, out))
+        return (None if out[0] < 0 else int(out[0])), int(out[1]), int(out[2]), int(out[3]), int(out[4]), int(out[5])
+
+    def agc_last_ms(self):
+        """Device milliseconds of the three launches of the last agc() that launched anything: (agc_measure, agc_gains, agc_apply)."""
+        out = (C.c_float * 3)()
+        _check(_agc_last_ms(self._h, out))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def pack_last_plan(self):
         """What the last pack() / unpack() / generate_batch_packed() took: (grid or None, units per block, tiles per block, pieces)."""

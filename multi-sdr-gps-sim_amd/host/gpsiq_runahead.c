@@ -16,7 +16,7 @@
  *   gpsiq_runahead <rinex> <2|3> <week> <sec> <position> <nblocks> <nchan> <fs> <1|2> <out.bin> [almanac.sem]
  *                  [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]]
  *                  [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]...
- *                  [--resample fs_out[,ppb]]
+ *                  [--resample fs_out[,ppb]] [--agc rms_out,qmax[,window,navg] [--blank thresh,hold]]
  *
  * start time: GPS <week> <sec>, or the reference's -t form "YYYY/MM/DD,hh:mm:ss" as <week> with "-" as <sec>
  * (gps-sim.c:104; date2gps, gps.c:315-337, 2295: no leap seconds applied, as there).
@@ -76,6 +76,13 @@
  * structure; the position runs on from call to call of the library, and every call starts from a history of zeros, as with --filter.
  * The samples written and the elements the clamp changed are printed.  Not with --pack, --filter, --tone, --acquire, --follow or
  * --spectrum.
+ * Gain control (optional, same place): --agc <rms_out>,<qmax>[,<window>,<navg>] writes the stream through gpsiq_generate_batch_agc
+ * (include/gpsiq_rows.h, "AGC") in the run's own sample size: a gain held over windows of <window> samples (a multiple of 64, default
+ * 1024) from the power of the <navg> windows before (default 16) that brings the stream to <rms_out> output steps per component, clamped
+ * to +-<qmax>; the multiplier is 65536 until the first window has completed.  --blank <thresh>,<hold> (only with --agc) zeroes every
+ * sample with an element above <thresh>, as stored, and the <hold> samples behind it, and keeps them out of the power.  The state runs on
+ * from call to call of the library.  The elements clipped, the samples blanked and the first and the last multiplier are printed.  With
+ * --cn0, --seed, --level and --spectrum; not with --pack, --filter, --tone or --resample.
  */
 #include <math.h>
 #include <stdint.h>
@@ -314,12 +321,15 @@ int main(int argc, char **argv)
     int ntone = 0;
     const char *resample_arg = NULL;
     int resample = 0;
+    const char *agc_arg = NULL, *blank_arg = NULL;
+    int agc = 0, blank = 0;
     for (;;) {                                                                                                   /* trailing flags */
         if (argc > 1 && strcmp(argv[argc - 1], "--acquire") == 0) { acquire = 1; argc -= 1; continue; }         /* the one without a value */
         if (!(argc > 3 && (strcmp(argv[argc - 2], "--cn0") == 0 || strcmp(argv[argc - 2], "--seed") == 0 || strcmp(argv[argc - 2], "--pack") == 0 ||
                         strcmp(argv[argc - 2], "--follow") == 0 || strcmp(argv[argc - 2], "--level") == 0 || strcmp(argv[argc - 2], "--qmax") == 0 ||
                         strcmp(argv[argc - 2], "--filter") == 0 || strcmp(argv[argc - 2], "--taps") == 0 || strcmp(argv[argc - 2], "--decim") == 0 ||
-                        strcmp(argv[argc - 2], "--spectrum") == 0 || strcmp(argv[argc - 2], "--tone") == 0 || strcmp(argv[argc - 2], "--resample") == 0))) break;
+                        strcmp(argv[argc - 2], "--spectrum") == 0 || strcmp(argv[argc - 2], "--tone") == 0 || strcmp(argv[argc - 2], "--resample") == 0 ||
+                        strcmp(argv[argc - 2], "--agc") == 0 || strcmp(argv[argc - 2], "--blank") == 0))) break;
         if (strcmp(argv[argc - 2], "--cn0") == 0) cn0 = atof(argv[argc - 1]);
         else if (strcmp(argv[argc - 2], "--pack") == 0) { pack = atoi(argv[argc - 1]); pack_given = 1; }
         else if (strcmp(argv[argc - 2], "--level") == 0) level_rms = atof(argv[argc - 1]);
@@ -330,6 +340,8 @@ int main(int argc, char **argv)
         else if (strcmp(argv[argc - 2], "--decim") == 0) { fdecim = atoi(argv[argc - 1]); fopts = 1; }
         else if (strcmp(argv[argc - 2], "--spectrum") == 0) { spec_nfft = atoi(argv[argc - 1]); spectrum = 1; }
         else if (strcmp(argv[argc - 2], "--resample") == 0) { resample_arg = argv[argc - 1]; ++resample; }
+        else if (strcmp(argv[argc - 2], "--agc") == 0) { agc_arg = argv[argc - 1]; ++agc; }
+        else if (strcmp(argv[argc - 2], "--blank") == 0) { blank_arg = argv[argc - 1]; ++blank; }
         else if (strcmp(argv[argc - 2], "--tone") == 0) { if (ntone <= MAX_TONES) tone_arg[ntone] = argv[argc - 1]; ++ntone; }
         else noise_seed = strtoull(argv[argc - 1], NULL, 0);
         argc -= 2;
@@ -364,8 +376,24 @@ int main(int argc, char **argv)
         resample_bad = (n != 1 && n != 2) || (n == 1 && strchr(resample_arg, ',')) || !(fs_arg > 0.0) ||
                        gpsiq_resample_step(fs_arg, rs_fs, rs_ppb, &rs_step) != GPSIQ_OK;
     }
-    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad || tone_bad || resample_bad) {
-        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]... [--resample fs_out[,ppb]]\n"
+    /* --agc: once, rms_out,qmax[,window,navg] inside the stage's ranges for this sample size; --blank thresh,hold only with it */
+    gpsiq_agc_cfg_t agc_cfg = {1024, 16, 0, 65536, 1, (1u << 24) - 1, 0, 0, 0};
+    double agc_rms = 0.0;
+    int agc_bad = agc > 1 || blank > 1 || (blank && !agc) || (agc && (pack_given || filter || fopts || ntone || resample));
+    if (agc == 1 && !agc_bad) {
+        char extra;
+        int q = 0, w = 1024, m = 16, t = 0, hold = 0;
+        const int short_form = sscanf(agc_arg, "%lf,%d%c", &agc_rms, &q, &extra) == 2;
+        const int long_form = !short_form && sscanf(agc_arg, "%lf,%d,%d,%d%c", &agc_rms, &q, &w, &m, &extra) == 4;
+        const int most = argc >= 10 && atoi(argv[9]) == 1 ? 127 : 32767;
+        agc_bad = (!short_form && !long_form) || !(agc_rms * 256.0 >= 1.0) || !(agc_rms * 256.0 < 8388607.5) || q < 1 || q > most || w < 64 || w > 65536 || w % 64 ||
+                  m < 1 || m > 64;
+        if (blank && !agc_bad) agc_bad = sscanf(blank_arg, "%d,%d%c", &t, &hold, &extra) != 2 || t < 1 || t > 32767 || hold < 0 || hold > 1024;
+        agc_cfg.window = w; agc_cfg.navg = m; agc_cfg.target_q8 = (uint32_t) floor(agc_rms * 256.0 + 0.5); agc_cfg.qmax = q;
+        agc_cfg.blank_thresh = t; agc_cfg.blank_hold = hold;
+    }
+    if ((argc != 11 && argc != 12) || pack_bad || acq_bad || follow_bad || filter_bad || spectrum_bad || tone_bad || resample_bad || agc_bad) {
+        fprintf(stderr, "usage: %s rinex 2|3 week sec xyz.bin|motion.csv|lat,lon,h nblocks nchan fs 1|2 out.bin [almanac.sem] [--cn0 dBHz] [--seed n] [--level rms] [--qmax n] [--pack 4|2] [--acquire [--follow seconds]] [--filter cutoff_hz [--taps n] [--decim d]] [--spectrum nfft] [--tone f_hz,js_db[,f1_hz,sweep_s]]... [--resample fs_out[,ppb]] [--agc rms_out,qmax[,window,navg] [--blank thresh,hold]]\n"
                         "       --pack needs --level, sample size 1 and --qmax <= 7 (4 bits) or <= 1 (2 bits)\n"
                         "       --acquire searches rendered elements (not with --pack) and needs fs >= 64 kHz\n"
                         "       --follow needs --acquire and a time in (0, 10] seconds inside the blocks before the first 30 s boundary\n"
@@ -375,7 +403,10 @@ int main(int argc, char **argv)
                         "       --tone (up to four) needs f,J/S or f0,J/S,f1,sweep: frequencies inside (-fs/2, fs/2), a sweep of 2 samples or more;\n"
                         "              not with --pack or --filter\n"
                         "       --resample needs a rate between fs/8 and 8 fs and, behind a comma, a clock offset in parts per billion; once, and\n"
-                        "              not with --pack, --filter, --tone, --acquire, --follow or --spectrum\n", argv[0]);
+                        "              not with --pack, --filter, --tone, --acquire, --follow or --spectrum\n"
+                        "       --agc needs an output rms in [1/256, 32768) steps, a clamp 1..127 (sample size 1) or 1..32767, and optionally a window\n"
+                        "             (a multiple of 64, 64..65536; default 1024) and the windows averaged (1..64; default 16); once, and not with\n"
+                        "             --pack, --filter, --tone or --resample.  --blank needs --agc, a threshold 1..32767 and a hold 0..1024\n", argv[0]);
         return 2;
     }
     if (pack && !qmax) qmax = pack_qmax;
@@ -466,6 +497,10 @@ int main(int argc, char **argv)
         if (gpsiq_resample_span((uint64_t) BLOCKS_PER_CALL * (uint64_t) nsamp, 0, rs_step, &rs_room, NULL) != GPSIQ_OK) return die("resample span");
         rs_room += 1;
     }
+    /* --agc: the state of the run */
+    gpsiq_agc_state_t agc_state;
+    memset(&agc_state, 0, sizeof agc_state);
+    uint64_t agc_clipped = 0, agc_blanked = 0;
     void *buf = gpsiq_host_alloc(resample ? (size_t) rs_room * 2 * (size_t) ss : blk_bytes * BLOCKS_PER_CALL);
     gpsiq_chan_t *desc = malloc(sizeof *desc * BLOCKS_PER_CALL * (size_t) nchan);
     FILE *fo = fopen(argv[10], "wb");
@@ -518,6 +553,12 @@ int main(int argc, char **argv)
                 if (fwrite(buf, (size_t) 2 * (size_t) ss, (size_t) nout, fo) != (size_t) nout) { fprintf(stderr, "short write\n"); return 1; }
                 have_carr = 1;
                 continue;
+            } else if (agc) {
+                uint64_t clipped = 0, blanked = 0;
+                if (gpsiq_generate_batch_agc(gq, desc, nb, nchan, nsamp, fs, ss, &agc_cfg, &agc_state, ss, buf, blk_bytes, &clipped, &blanked, carr) != GPSIQ_OK)
+                    return die("generate agc");
+                agc_clipped += clipped;
+                agc_blanked += blanked;
             } else if (ntone) {
                 if (!tones_set) {                                              /* once: J/S against a satellite of descriptor gain 1 */
                     const double unit = level_mult ? 250.0 * (double) level_mult / 65536.0 : 250.0;
@@ -577,6 +618,15 @@ int main(int argc, char **argv)
     if (resample)
         printf("resample: %g Hz to %g Hz at %g ppb, step %llu / 2^32, %llu samples written, %llu elements clipped\n", fs, rs_fs, rs_ppb,
                (unsigned long long) rs_step, (unsigned long long) rs_written, (unsigned long long) rs_clipped);
+    if (agc) {
+        uint64_t sum = 0, cnt = 0;
+        uint32_t first = 0, last = 0;
+        for (uint32_t r = 0; r < agc_state.nring; ++r) { sum += agc_state.wsum[r]; cnt += agc_state.wcnt[r]; }
+        if (gpsiq_agc_mult(&agc_cfg, 0, 0, &first) != GPSIQ_OK || gpsiq_agc_mult(&agc_cfg, sum, cnt, &last) != GPSIQ_OK) return die("agc multiplier");
+        printf("agc: rms %g, qmax %d, window %d, navg %d, %llu elements clipped, %llu samples blanked, multiplier %u at the first window, %u at the end\n", agc_rms,
+               (int) agc_cfg.qmax, (int) agc_cfg.window, (int) agc_cfg.navg, (unsigned long long) agc_clipped, (unsigned long long) agc_blanked, (unsigned) first,
+               (unsigned) last);
+    }
     if (ntone) printf("tones: %d, %llu elements clipped\n", ntone, (unsigned long long) tone_clipped);
     gpsiq_host_free(buf);
     gpsiq_destroy(gq);
