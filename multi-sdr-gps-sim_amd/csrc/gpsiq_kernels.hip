@@ -334,7 +334,8 @@ __global__ __launch_bounds__(kRowsThreads) void synth_rowsx(
 //   * LUT build: thread k owns LUT entry k of every channel, so sin/cos of k are formed
 //     once and each entry costs two f64 multiplies and two truncations;
 //   * window set-up in 32-bit chip arithmetic (a block never advances 2^32 chips);
-//   * a chunk whose rows all lie inside the block runs a check-free row loop.
+//   * a chunk whose rows all lie inside the block runs a check-free row loop; in the plain-add cores that loop takes four
+//     rows per trip and reads the next row's windows while a row is worked (gpsiq_tile_body.inc, "rows per loop trip").
 //   * H = 2 ("segh"): one window per HALF row (32 lanes), so a row may span up to 63 chips
 //     and the kernel works down to one chip per sample (1.023 Msps); lanes 32..63 read the
 //     second window of their row (two LDS addresses per wave read instead of one).

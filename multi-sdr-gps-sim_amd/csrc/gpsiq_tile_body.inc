@@ -145,15 +145,124 @@
     [[maybe_unused]] int32_t l_neg = 0;
     if constexpr (LEVEL && FAST) asm("v_mov_b32 %0, %1" : "=v"(l_neg) : "s"(-(int32_t) lqmax));
 
+    constexpr uint32_t kElem = FMT == GPSIQ_SC16 ? 4u : 2u;     // bytes of one stored sample
+
+    // this lane's noise at the row being worked (mod 2^32); steps its stream on to the next row
+    auto noise_row = [&](uint32_t &zi, uint32_t &zq) {
+        const uint32_t w = noise::xsh_rr(nx);
+        nx = nx * noise::kMul + noise::kInc;
+        zi = (uint32_t) noise::z(nz, w & 0xffffu);
+        zq = (uint32_t) noise::z(nz, w >> 16);
+    };
+    // what the plain-add core's sum becomes before the level stage or the store: the noise as one more term, the bias off
+    auto fast_word = [&](uint32_t sum, uint32_t zi, uint32_t zq) -> uint32_t {
+        if constexpr (NOISE && !LEVEL) {
+            if (FMT == GPSIQ_SC08)
+                // a 17th term in the 12-bit fields: I's spill bits (16..19) are cleared first, so its carry stays out of Q
+                sum = (sum & ~0xf0000u) + ((zi & 0xfffu) << 4) + (zq << 20);
+            else
+                sum += zi + (zq << 16);                           // |I + zI| <= 32767 (the host's choice of core): no borrow into Q
+        }
+        return LFMT == GPSIQ_SC16 ? sum ^ 0x8000u : sum;          // take the bias off again: (I & 0xffff) | Q << 16
+    };
+    // the level stage (LEVEL kernels) and the store of one sample at o; iq = (I & 0xffff) | Q << 16 as the int16 store keeps it
+    auto emit = [&](uint32_t iq, [[maybe_unused]] uint32_t zi, [[maybe_unused]] uint32_t zq, uint8_t *o, bool ok) {
+        if constexpr (LEVEL) {
+            // iq holds the noiseless sums as the int16 store would keep them.  Each comes out of the word sign-extended, the
+            // noise is added in 32 bits (nothing wraps), then scale, round, clamp: the product needs more than 32 bits
+            // (|A| < 2^19, mult < 2^24: v_mad_i64_i32), the quotient does not
+            const int32_t ai = (int32_t) (int16_t) iq + (int32_t) zi, aq = ((int32_t) iq >> 16) + (int32_t) zq;
+            const int32_t yi = (int32_t) (((int64_t) ai * (int64_t) (int32_t) lmult + 32768) >> 16);
+            const int32_t yq = (int32_t) (((int64_t) aq * (int64_t) (int32_t) lmult + 32768) >> 16);
+            // the clamp is one v_med3_i32 per component (written out: the compiler cannot know that -qmax <= qmax and emits
+            // min, compare and select; a VOP3 instruction reads one scalar register at most, so -qmax sits in a vector register)
+            uint32_t oi, oq;
+            if constexpr (!FAST) l_neg = -(int32_t) lqmax;
+            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oi) : "v"(yi), "v"(l_neg), "s"((int32_t) lqmax));
+            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oq) : "v"(yq), "v"(l_neg), "s"((int32_t) lqmax));
+            if (ok) {
+                if (FMT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(o) = (oi & 0xffffu) | (oq << 16);
+                else *reinterpret_cast<uint16_t *>(o) = (uint16_t) ((oi & 0xffu) | (oq << 8));
+            }
+        } else if (ok) {
+            if (FMT == GPSIQ_SC16)
+                *reinterpret_cast<uint32_t *>(o) = iq;                                        // gps.c:2842
+            else                                                                             // bytes 1 and 3, see the LUT build
+                *reinterpret_cast<uint16_t *>(o) = (uint16_t) __builtin_amdgcn_perm(iq, iq, 0x0c0c0301u);
+        }
+    };
+
+    // ---- kTrip rows per loop trip (the plain-add cores) ----
+    // One trip works rows r .. r + kTrip - 1 of a chunk off one window pointer and one store pointer: the rows' window reads and
+    // stores differ in their immediate offsets only.  Within a row the LDS traffic runs under arithmetic that does not wait for
+    // it: the gathers go out behind the address arithmetic, the NCO adds (which depend on nothing in flight) follow, and only
+    // then does the sum wait for the gathers, in their order.  A row's window words are dead once the sixteen shifts have read
+    // them, so the NEXT row's windows are read into them meanwhile (wv is carried from row to row and from trip to trip): half
+    // way down the NCO adds, which measured 0.2-0.3 % faster than right behind the shifts (twenty LDS instructions in one burst).
+    // A wave then covers its own LDS latency instead of leaving it to the other three of its SIMD.  The packed core has no
+    // registers for a second set of window words (128 VGPRs) and keeps one row per trip; the 16-channel noise and level
+    // kernels have none either (the noise stream and the level's operands take them: they would spill) and do the same.
+    constexpr int kTrip = FAST && !(NOISE && NCH > 12) ? 4 : 1;
+    static_assert(ROWS % kTrip == 0, "whole trips in a full chunk");
+    static_assert(NCH % 4 == 0, "window words are read four at a time");
+    typedef uint32_t win4 __attribute__((ext_vector_type(4)));
+    auto read_windows = [&](const uint32_t *w, uint32_t (&wv)[NCH]) {
+        const win4 *w4 = reinterpret_cast<const win4 *>(__builtin_assume_aligned(w, 16));
+#pragma unroll
+        for (int c = 0; c < NCH; c += 4) {
+            const win4 v = w4[c / 4];
+            wv[c] = v.x; wv[c + 1] = v.y; wv[c + 2] = v.z; wv[c + 3] = v.w;
+        }
+    };
+    // w_at: window of the trip's first row (on return: of the row that wv holds, w_step words on);  o: the first row's sample
+    [[maybe_unused]] auto trip_body = [&](const uint32_t *&w_at, uint32_t (&wv)[NCH], uint8_t *o, int w_step) {
+#pragma unroll
+        for (int j = 0; j < kTrip; ++j) {
+            uint32_t t[NCH], g[NCH];
+            [[maybe_unused]] uint32_t zi = 0, zq = 0;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) t[c] = wv[c] >> ((uint32_t) (Q[c] >> 56) & 31u);   // bit 0 = chip ^ nav bit of this lane
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                if (BOTH) {
+                    const uint32_t x = __builtin_amdgcn_alignbit(t[c], (uint32_t) (P[c] >> 32), 21u);
+                    g[c] = *reinterpret_cast<const uint32_t *>(lut_b + c * 4096 + (x & 0xffcu));
+                } else {
+                    const uint32_t x = (t[c] << 26) + (uint32_t) (P[c] >> 32);
+                    g[c] = *reinterpret_cast<const uint32_t *>(lut_b + c * 2048 + ((x >> 16) & 0x7fcu));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NOISE) noise_row(zi, zq);
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                if (c == NCH / 2) {
+                    // the next row's windows, half way down the adds.  The last row of the trip reads ahead for the next trip;
+                    // the last trip of a chunk has w_step == 0 and reads its own first row again, never past the chunk's windows
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j + 1 == kTrip) w_at += w_step;
+                    read_windows(j + 1 == kTrip ? w_at : w_at + (j + 1) * (H * NCH), wv);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                P[c] += dP[c];
+                Q[c] += dQ[c];
+                // one add per row and word, in place: left to itself the compiler rewrites the trip's four adds of a word so
+                // that several values of it are live at once, and the 16-channel kernels spill some 150 registers
+                asm("" : "+v"(P[c]), "+v"(Q[c]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            uint32_t sum = 0u;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) sum += g[c];
+            emit(fast_word(sum, zi, zq), zi, zq, o + (uint32_t) j * (64u * kElem), true);
+        }
+    };
+
     auto row_body = [&](int r, uint32_t n_chunk, bool check) {
         uint32_t iq;                                             // (I & 0xffff) | Q << 16, what the int16 store keeps
         [[maybe_unused]] uint32_t zi = 0, zq = 0;                // noise of this lane's sample, mod 2^32
-        if constexpr (NOISE) {
-            const uint32_t w = noise::xsh_rr(nx);
-            nx = nx * noise::kMul + noise::kInc;
-            zi = (uint32_t) noise::z(nz, w & 0xffffu);
-            zq = (uint32_t) noise::z(nz, w >> 16);
-        }
+        if constexpr (NOISE) noise_row(zi, zq);
         if (FAST) {
             uint32_t sum = 0u;                                    // int16: slot 0's entries carry a +0x8000 bias
 #pragma unroll
@@ -172,14 +281,7 @@
                 P[c] += dP[c];
                 Q[c] += dQ[c];
             }
-            if constexpr (NOISE && !LEVEL) {
-                if (FMT == GPSIQ_SC08)
-                    // a 17th term in the 12-bit fields: I's spill bits (16..19) are cleared first, so its carry stays out of Q
-                    sum = (sum & ~0xf0000u) + ((zi & 0xfffu) << 4) + (zq << 20);
-                else
-                    sum += zi + (zq << 16);                       // |I + zI| <= 32767 (the host's choice of core): no borrow into Q
-            }
-            iq = LFMT == GPSIQ_SC16 ? sum ^ 0x8000u : sum;        // take the bias off again: (I & 0xffff) | Q << 16
+            iq = fast_word(sum, zi, zq);
         } else {
             s16x2 acc0 = (s16x2) (0), acc1 = (s16x2) (0);
 #pragma unroll
@@ -201,33 +303,8 @@
             }
             iq = __builtin_bit_cast(uint32_t, acc0 + acc1);
         }
-        if constexpr (LEVEL) {
-            // iq holds the noiseless sums as the int16 store would keep them.  Each comes out of the word sign-extended, the
-            // noise is added in 32 bits (nothing wraps), then scale, round, clamp: the product needs more than 32 bits
-            // (|A| < 2^19, mult < 2^24: v_mad_i64_i32), the quotient does not
-            const int32_t ai = (int32_t) (int16_t) iq + (int32_t) zi, aq = ((int32_t) iq >> 16) + (int32_t) zq;
-            const int32_t yi = (int32_t) (((int64_t) ai * (int64_t) (int32_t) lmult + 32768) >> 16);
-            const int32_t yq = (int32_t) (((int64_t) aq * (int64_t) (int32_t) lmult + 32768) >> 16);
-            // the clamp is one v_med3_i32 per component (written out: the compiler cannot know that -qmax <= qmax and emits
-            // min, compare and select; a VOP3 instruction reads one scalar register at most, so -qmax sits in a vector register)
-            uint32_t oi, oq;
-            if constexpr (!FAST) l_neg = -(int32_t) lqmax;
-            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oi) : "v"(yi), "v"(l_neg), "s"((int32_t) lqmax));
-            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(oq) : "v"(yq), "v"(l_neg), "s"((int32_t) lqmax));
-            const uint32_t n = n_chunk + (uint32_t) lane + (uint32_t) r * 64u;
-            if (!check || n < (uint32_t) nsamp) {
-                if (FMT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(blk_dst + n * 4u) = (oi & 0xffffu) | (oq << 16);
-                else *reinterpret_cast<uint16_t *>(blk_dst + n * 2u) = (uint16_t) ((oi & 0xffu) | (oq << 8));
-            }
-            return;
-        }
         const uint32_t n = n_chunk + (uint32_t) lane + (uint32_t) r * 64u;
-        if (!check || n < (uint32_t) nsamp) {
-            if (FMT == GPSIQ_SC16)
-                *reinterpret_cast<uint32_t *>(blk_dst + n * 4u) = iq;                     // gps.c:2842
-            else                                                                         // bytes 1 and 3, see the LUT build
-                *reinterpret_cast<uint16_t *>(blk_dst + n * 2u) = (uint16_t) __builtin_amdgcn_perm(iq, iq, 0x0c0c0301u);
-        }
+        emit(iq, zi, zq, blk_dst + n * kElem, !check || n < (uint32_t) nsamp);
     };
 
     for (int row0 = 0; row0 < wave_rows; row0 += ROWS) {
@@ -293,8 +370,25 @@
         rows = rows < ROWS ? rows : ROWS;
         if (n_chunk + (uint32_t) rows * 64u <= (uint32_t) nsamp) {
             const int rows_s = __builtin_amdgcn_readfirstlane(rows);       // the trip count is wave-uniform: keep it scalar
+            int r = 0;
+            if constexpr (kTrip > 1) {
+                const int trips = rows_s / kTrip;
+                if (trips > 0) {
+                    const uint32_t *w_at = w_row;
+                    uint32_t wv[NCH];
+                    read_windows(w_at, wv);
+                    uint32_t o_off = (n_chunk + (uint32_t) lane) * kElem;
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int r = 0; r < rows_s; ++r) row_body(r, n_chunk, false);
+                    for (int t = trips; t > 0; --t) {
+                        trip_body(w_at, wv, blk_dst + o_off, t > 1 ? kTrip * (H * NCH) : 0);
+                        o_off += (uint32_t) kTrip * 64u * kElem;
+                    }
+                    r = trips * kTrip;
+                }
+            }
+            // a partial chunk's last rows, one per trip
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (; r < rows_s; ++r) row_body(r, n_chunk, false);
         } else {                                             // the block ends inside this chunk
             const int in_block = (int) (((uint32_t) nsamp - n_chunk + 63u) >> 6);
             rows = rows < in_block ? rows : in_block;

@@ -84,8 +84,10 @@ def main():
                     addr = re.search(r"//\s*([0-9A-Fa-f]+):", ln)
                     if t:
                         ins.append((int(addr.group(1), 16) if addr else None, t))
-                # innermost backward branch whose body holds the LDS gathers
+                # the innermost loops whose body holds the LDS gathers; of those the one with the most of them: the whole-trip loop
+                # (several rows per pass) where there is one, rather than the single-row loop of the remainder rows
                 best = None
+                backward = []
                 for i, (a, t) in enumerate(ins):
                     mm = re.match(r"s_cbranch_\w+\s+(\d+)", t) or re.match(r"s_branch\s+(\d+)", t)
                     if not mm or a is None:
@@ -94,9 +96,13 @@ def main():
                     j = next((q for q, (aa, _) in enumerate(ins) if aa == tgt), None)
                     if j is None or j > i:
                         continue
+                    backward.append((j, i))
+                for j, i in backward:
+                    if any((j2, i2) != (j, i) and j <= j2 and i2 <= i for j2, i2 in backward):
+                        continue                                # another loop inside: not innermost
                     seg = ins[j:i + 1]
                     gathers = sum(1 for _, x in seg if x.startswith("ds_read_b32"))
-                    if gathers >= 16 and (best is None or len(seg) < len(best)):
+                    if gathers >= 16 and (best is None or gathers > sum(1 for _, x in best if x.startswith("ds_read_b32"))):
                         best = seg
                 lines_out.append(f"== {name}")
                 if best is None:
@@ -114,9 +120,11 @@ def main():
                     lines_out.append(f"   {a:08x}  {t:<64s} {'' if c is None else f'{c:.1f}'}")
                 gathers = sum(1 for _, x in best if x.startswith("ds_read_b32"))
                 wide = sum(1 for _, x in best if x.startswith("ds_read_b128"))
-                lines_out.append(f"   -- one pass of the loop = one 64-sample row of 16 channels: {cls['VALU']} VALU ({cls['VALU'] / 16:.2f} per channel-row), "
-                                 f"{gathers} ds_read_b32 gathers + {wide} ds_read_b128, {cls['VMEM']} store(s), {cls['SALU/other']} scalar / wait / branch; "
-                                 f"VALU issue at the measured rates: {cyc:.1f} cycles per row = {cyc / 16:.2f} per channel-row")
+                rows = max(cls['VMEM'], 1)                      # one store per row
+                lines_out.append(f"   -- one pass of the loop = {rows} 64-sample row(s) of 16 channels: {cls['VALU']} VALU ({cls['VALU'] / rows:.2f} per row, "
+                                 f"{cls['VALU'] / rows / 16:.2f} per channel-row), {gathers} ds_read_b32 gathers + {wide} ds_read_b128, {cls['VMEM']} store(s), "
+                                 f"{cls['SALU/other']} scalar / wait / branch / scheduling mark; "
+                                 f"VALU issue at the measured rates: {cyc / rows:.1f} cycles per row = {cyc / rows / 16:.2f} per channel-row")
     hdr = [f"# row loop of the default kernels in the shipped libgpsiq.so (kernel id {kernels_id()}), llvm-objdump -d; right column: issue cycles of the",
            "# instruction's encoding class as measured on MI355X (profiles/r01_ubench_valu_encodings.txt: VOP2 on VGPRs 2.5, SGPR-operand / VOP3 /",
            "# SDWA / packed 4.3, v_lshl_add_u64 4.4).  Regenerate: python scripts/row_loop_listing.py <tag>", ""]
