@@ -784,6 +784,53 @@ int gpsiq_generate_batch_agc(gpsiq_ctx_t *ctx, const gpsiq_chan_t *ch, int nbloc
                              const gpsiq_agc_cfg_t *cfg, gpsiq_agc_state_t *state, int out_sample_size,
                              void *dst_host, size_t dst_block_stride, uint64_t *clipped, uint64_t *blanked, double *carr_phase_out);
 
+/* ---- Complex filter and notch: a complex-tap device FIR, and the host arithmetic that turns a spectrum into a notch ------------------
+ * gpsiq_filter has real taps, so its response is symmetric about 0 Hz: it cannot take a line out at +300 kHz and leave -300 kHz alone.
+ * gpsiq_cfilter is the same stage with taps h[k] = re[k] + j im[k] over x(m) = I(m) + j Q(m):
+ *   accI = sum over k < ntaps of re[k] * I(m_j - k) - im[k] * Q(m_j - k)
+ *   accQ = sum over k < ntaps of re[k] * Q(m_j - k) + im[k] * I(m_j - k)
+ * Everything else is gpsiq_filter's contract word for word (see "Filter"): the span, head and the zeros before it; the output count
+ * and next_phase (gpsiq_filter_span serves both calls); y, the round-half-up shift, the symmetric clamp and *clipped; 1 <= ntaps <= 512,
+ * 1 <= decim <= 16, 0 <= phase < decim, 0 <= shift <= 24, nsamp >= 0 and the four format pairs (GPSIQ_E_ARG); alignment and overlap
+ * refusals; memory kinds; stream order and the synchronous return; nsamp == 0 or nout == 0 launching nothing; exact continuation
+ * across pieces with head and next_phase.  The bound is sum over k of (|re[k]| + |im[k]|) <= 65535, else GPSIQ_E_RANGE: with it
+ * |accI|, |accQ| <= 65535 * 32768 < 2^31 for both input formats, so there is one accumulator width and no saturation rule.
+ * Two identities:  with every im[k] == 0 the call writes the bytes and the count of gpsiq_filter with taps = re;  with ntaps 1, re 0,
+ * im 1, shift 0 it writes (-Q, I) (an element -32768 of an int16 stream becomes +32768 and is clamped to 32767, and counted).
+ * GPSIQ_CFILTER_KERNEL=generic|mfma in the environment, read per call, forces a kernel where it can serve; the bytes and the count
+ * never depend on it.
+ *
+ * gpsiq_notch_find reads ONE group of a gpsiq_spectrum result, power[nfft].  The floor is the median of the nfft cells: the lower of
+ * the two middle ones, in integers.  A cell is over if power > ratio * floor (compared in long double).  A maximal run of over cells,
+ * cyclic in k, is one line (at least half the cells are at or below the floor, so no run closes on itself).  Its frequency is the
+ * power-weighted centroid of its cells, the run counted on from its first cell: bin k standing at (k < nfft/2 ? k : k - nfft) * fs/nfft and a run that wraps past bin nfft-1 continuing at nfft, nfft+1, ... before
+ * the result is brought back into [-fs/2, fs/2); its excess is 10 log10(peak cell / floor).  Lines come back strongest first (by peak
+ * cell, then by lower first bin), at most max_lines of them (1..8) in f_hz and excess_db; *nlines is what was found before that cap.
+ * GPSIQ_E_ARG: nfft not one of 64, 128, 256, 512; ratio <= 1 or not finite; fs <= 0; max_lines outside 1..8; a floor of 0; a null pointer.
+ *
+ * gpsiq_notch_design writes the taps of a linear-phase notch at nlines frequencies.  ntaps odd, 3..511, c = (ntaps-1)/2.  g is the
+ * Hamming-windowed sinc of gpsiq_filter_design at cutoff width_hz/2, normalised to sum 1 (unrounded).  The unrounded filter is
+ *   h[n] = delta[n - c] - sum over l of a_l * g[n] * e^(j w_l (n - c)),   w_l = 2 pi f_l / fs,
+ * where the a_l solve the nlines x nlines linear system that makes the unrounded response exactly 0 at every f_l (one line: a = 1), and
+ * taps = rint(2^shift * h), component by component.  GPSIQ_E_ARG: ntaps even or outside 3..511, nlines outside 1..8, |f_l| >= fs/2,
+ * width_hz outside (0, fs), two lines closer than width_hz (cyclically in fs), shift outside 8..14, a null pointer.  GPSIQ_E_RANGE:
+ * the rounded taps break the sum bound or a component leaves int16; the caller then lowers shift.
+ * Double arithmetic: its properties are contract, its bits are not.  With H the response of the integer taps over 2^shift:
+ *   1. taps[c + n] = conj(taps[c - n]): linear phase, a delay of c samples;
+ *   2. |H(f_l)| <= 0.7072 * ntaps / 2^shift: only rounding is left at a line, at most 0.5 per component and tap;
+ *   3. where |f - f_l| >= width_hz/2 + 3.3 fs/ntaps for every l:  | |H(f)| - 1 | <= (sum |a_l|) * g_stop + 0.7072 * ntaps / 2^shift,
+ *      g_stop the largest |G(f)| of the prototype g itself beyond that same distance from 0 Hz. */
+typedef struct { int16_t re, im; } gpsiq_ctap_t;
+
+int gpsiq_cfilter(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head /* may be NULL */,
+                  const gpsiq_ctap_t *taps /* host [ntaps] */, int ntaps, int shift, int decim, int phase,
+                  int out_sample_size, void *dst, void *hip_stream,
+                  int *nout, uint64_t *clipped, float *kernel_ms);           /* the last three may be NULL */
+int gpsiq_notch_find(const uint64_t *power /* [nfft], one group of gpsiq_spectrum */, int nfft, double fs, double ratio,
+                     int max_lines, double *f_hz, double *excess_db, int *nlines);                    /* host arithmetic */
+int gpsiq_notch_design(double fs, const double *f_hz, int nlines, double width_hz, int ntaps, int shift,
+                       gpsiq_ctap_t *taps);                                                            /* host arithmetic */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -6,7 +6,7 @@
 // stream stage keeps in the context is in that stage's header, included below; what the staged batch calls share (the staging ring
 // and the piece loop) is in gpsiq_stage_batch.h; HIP_TRY is in gpsiq_own.h.
 //
-// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample, agc):
+// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample, agc, cfilter):
 //   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
 //   gpsiq_<s>.h                 the stage's member of gpsiq_ctx (resources, reserve()), its kernels by type and their look-ups,
 //                               and `decltype(gpsiq_<s>) gpsiq_<s>_impl;`
@@ -41,6 +41,7 @@
 #include "gpsiq_mix.h"
 #include "gpsiq_resample.h"
 #include "gpsiq_agc.h"
+#include "gpsiq_cfilter.h"
 
 struct gpsiq_ctx {
     template <typename T> using DevBuf = gpsiq::DevBuf<T>;
@@ -175,7 +176,8 @@ struct gpsiq_ctx {
     } evd;
     // the stream stages, each in the header of its name: gpsiq_despread; gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed;
     // gpsiq_acquire; gpsiq_follow; gpsiq_filter / gpsiq_generate_batch_filtered; gpsiq_spectrum;
-    // gpsiq_mix / gpsiq_generate_batch_mixed; gpsiq_resample / gpsiq_generate_batch_resampled; gpsiq_agc / gpsiq_generate_batch_agc
+    // gpsiq_mix / gpsiq_generate_batch_mixed; gpsiq_resample / gpsiq_generate_batch_resampled; gpsiq_agc / gpsiq_generate_batch_agc;
+    // gpsiq_cfilter
     gpsiq::DespreadSet dsp;
     gpsiq::PackSet     pack;
     gpsiq::AcquireSet  acq;
@@ -185,6 +187,7 @@ struct gpsiq_ctx {
     gpsiq::MixSet      mix;
     gpsiq::ResampleSet rs;
     gpsiq::AgcSet      agc;
+    gpsiq::CfilterSet  cfilt;
     // the staging the five staged batch calls (_packed, _filtered, _mixed, _resampled, _agc) work through their pieces with: one ring for
     // all of them -- calls on a context are serial and every one ends with the ring's streams drained (gpsiq_stage_batch.h)
     gpsiq::PieceRing   ring;

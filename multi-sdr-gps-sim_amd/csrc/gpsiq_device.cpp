@@ -488,7 +488,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         GPSIQ_P(gpsiq_prn_code), GPSIQ_P(gpsiq_carrier_table), GPSIQ_P(gpsiq_generate_seeded), GPSIQ_P(gpsiq_noise_state), GPSIQ_P(gpsiq_noise_host),
         GPSIQ_P(gpsiq_despread_last_plan), GPSIQ_P(gpsiq_pack_last_plan), GPSIQ_P(gpsiq_acquire_last_plan), GPSIQ_P(gpsiq_follow_last_plan),
         GPSIQ_P(gpsiq_filter_last_plan), GPSIQ_P(gpsiq_spectrum_last_plan), GPSIQ_P(gpsiq_mix_last_plan),
-        GPSIQ_P(gpsiq_resample_last_plan), GPSIQ_P(gpsiq_agc_last_plan), GPSIQ_P(gpsiq_agc_last_ms),
+        GPSIQ_P(gpsiq_resample_last_plan), GPSIQ_P(gpsiq_agc_last_plan), GPSIQ_P(gpsiq_agc_last_ms), GPSIQ_P(gpsiq_cfilter_last_plan),
 #undef GPSIQ_P
         // the internals libgpsiq_rows.so runs on (gpsiq_rows_link.cpp): one pool, one quantiser, one error text per thread
         {"set_error", reinterpret_cast<void *>(&gpsiq::set_error)}, {"parallel_for", reinterpret_cast<void *>(&gpsiq::parallel_for)},
@@ -509,6 +509,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         {"generate_batch_resampled", reinterpret_cast<void *>(&gpsiq_generate_batch_resampled_impl)},    // (ibid., "Resample"; gpsiq_resample.cpp)
         {"agc", reinterpret_cast<void *>(&gpsiq_agc_impl)},                // gpsiq_agc and gpsiq_generate_batch_agc of libgpsiq_rows.so
         {"generate_batch_agc", reinterpret_cast<void *>(&gpsiq_generate_batch_agc_impl)},                // (ibid., "AGC"; gpsiq_agc.cpp)
+        {"cfilter", reinterpret_cast<void *>(&gpsiq_cfilter_impl)},        // gpsiq_cfilter of libgpsiq_rows.so (ibid., "Complex filter and notch"; gpsiq_cfilter.cpp)
     };
     if (!name) return nullptr;
     for (const auto &e : table)

@@ -34,7 +34,8 @@ void *gpsiq_plumbing(const char *name);
  * csrc/gpsiq_filter.cpp).  "spectrum" is gpsiq_spectrum (ibid., "Spectrum"; csrc/gpsiq_spectrum.cpp).  "mix" and
  * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp).  "resample" and
  * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp).  "agc" and
- * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp). */
+ * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp).  "cfilter" is
+ * gpsiq_cfilter (ibid., "Complex filter and notch"; csrc/gpsiq_cfilter.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -230,6 +231,10 @@ int gpsiq_agc_last_plan(const gpsiq_ctx_t *ctx, long long out[6]);
 /* The device time, in milliseconds, of the three launches of the context's last gpsiq_agc that launched anything: agc_measure, agc_gains,
  * agc_apply (scripts/agc_rates.py). */
 int gpsiq_agc_last_ms(const gpsiq_ctx_t *ctx, float out[3]);
+/* What the context's last gpsiq_cfilter took (csrc/gpsiq_cfilter_plan.h): out[0] the kernel (0 cfilter_generic, 1 filter_mfma with complex
+ * planes, 2 cfilter_mfma16; -1: nothing was launched, or no call yet), out[1] the grid, out[2] the outputs of a workgroup's run, out[3]
+ * the k-steps of a tile (0 for the generic kernel). */
+int gpsiq_cfilter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
 
 #ifdef __cplusplus
 }

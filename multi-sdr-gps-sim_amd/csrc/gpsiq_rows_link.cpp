@@ -216,3 +216,14 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_generate_batch_agc(g
     static const auto f = gpsiq::core<decltype(&gpsiq_generate_batch_agc)>("generate_batch_agc");
     return f(ctx, ch, nblocks, nchan, nsamp, fs, sample_size, cfg, state, out_sample_size, dst_host, dst_block_stride, clipped, blanked, carr_phase_out);
 }
+
+// The complex filter runs on the context's device (csrc/gpsiq_cfilter.cpp) and is exported here like the filter (include/gpsiq_rows.h,
+// "Complex filter and notch"); gpsiq_notch_find and gpsiq_notch_design, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_cfilter(gpsiq_ctx_t *ctx, int nsamp, int sample_size, const void *src, const void *head,
+                                                                    const gpsiq_ctap_t *taps, int ntaps, int shift, int decim, int phase,
+                                                                    int out_sample_size, void *dst, void *hip_stream, int *nout, uint64_t *clipped,
+                                                                    float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_cfilter)>("cfilter");
+    return f(ctx, nsamp, sample_size, src, head, taps, ntaps, shift, decim, phase, out_sample_size, dst, hip_stream, nout, clipped, kernel_ms);
+}

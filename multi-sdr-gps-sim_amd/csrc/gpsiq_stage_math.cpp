@@ -2,7 +2,8 @@
 // what a caller works out on the host before or after a call on the device -- a noise sigma for a C/N0, the level multiplier, the
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
 // and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix, the
-// output count, the step and the tap table of a resampler, the gain rule and the windows of a gain control.  Host code of libgpsiq_rows.so; nothing here touches a context or the
+// output count, the step and the tap table of a resampler, the gain rule and the windows of a gain control, the lines of a spectrum
+// and the taps of a notch.  Host code of libgpsiq_rows.so; nothing here touches a context or the
 // device (the calls themselves: gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
@@ -10,7 +11,9 @@
 #include "gpsiq_mix_geometry.h"
 #include "gpsiq_resample_plan.h"
 #include "gpsiq_agc_plan.h"
+#include "gpsiq_cfilter_geometry.h"
 
+#include <algorithm>
 #include <cmath>
 
 using namespace gpsiq;
@@ -377,6 +380,118 @@ int gpsiq_agc_span(uint64_t nsamp, int window, uint32_t fill, uint64_t *nwin, ui
     agc_span(nsamp, (uint32_t) window, fill, &n, &next);
     if (nwin) *nwin = n;
     if (next_fill) *next_fill = next;
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Complex filter and notch": the lines of one group of a spectrum.  The median leaves at least half the cells
+// at or below the floor and ratio > 1, so some cell is not over: the cyclic runs are walked from behind such a cell
+int gpsiq_notch_find(const uint64_t *power, int nfft, double fs, double ratio, int max_lines, double *f_hz, double *excess_db, int *nlines)
+{
+    if (!power || !f_hz || !excess_db || !nlines) return fail(GPSIQ_E_ARG, "null argument");
+    if (nfft < kSpecMinFft || nfft > kSpecMaxFft || (nfft & (nfft - 1))) return fail(GPSIQ_E_ARG, "nfft %d: 64, 128, 256 or 512", nfft);
+    if (!(ratio > 1.0) || !std::isfinite(ratio) || !(fs > 0.0) || !std::isfinite(fs)) return fail(GPSIQ_E_ARG, "ratio %g above 1, fs %g above 0", ratio, fs);
+    if (max_lines < 1 || max_lines > 8) return fail(GPSIQ_E_ARG, "max_lines %d outside 1..8", max_lines);
+    uint64_t sorted[kSpecMaxFft];
+    std::copy(power, power + nfft, sorted);
+    std::sort(sorted, sorted + nfft);
+    const uint64_t floor = sorted[nfft / 2 - 1];                       // the lower of the two middle cells
+    if (floor == 0) return fail(GPSIQ_E_ARG, "the median of the spectrum is 0: no floor to compare with");
+    const long double limit = (long double) ratio * (long double) floor;
+    const auto over = [&](int k) { return (long double) power[k] > limit; };
+    struct Line { uint64_t peak; int first; double f; };
+    Line lines[kSpecMaxFft / 2];
+    int found = 0, start = 0;
+    while (over(start)) ++start;                                       // (ends: see above)
+    for (int i = 1; i <= nfft;) {
+        const int k0 = (start + i) % nfft;
+        if (!over(k0)) { ++i; continue; }
+        long double sum = 0.0L, moment = 0.0L;
+        uint64_t peak = 0;
+        int len = 0;
+        for (; over((k0 + len) % nfft); ++len) {                       // stops at `start` at the latest
+            const uint64_t v = power[(k0 + len) % nfft];
+            sum += (long double) v;
+            moment += (long double) v * (long double) len;
+            if (v > peak) peak = v;
+        }
+        long double bin = (long double) (k0 < nfft / 2 ? k0 : k0 - nfft) + moment / sum;    // unwrapped from the run's first cell on
+        if (bin >= (long double) (nfft / 2)) bin -= (long double) nfft;
+        lines[found++] = {peak, k0, (double) (bin * (long double) fs / (long double) nfft)};
+        i += len;
+    }
+    std::sort(lines, lines + found, [](const Line &a, const Line &b) { return a.peak != b.peak ? a.peak > b.peak : a.first < b.first; });
+    for (int l = 0; l < found && l < max_lines; ++l) {
+        f_hz[l] = lines[l].f;
+        excess_db[l] = (double) (10.0L * std::log10((long double) lines[l].peak / (long double) floor));
+    }
+    *nlines = found;
+    return GPSIQ_OK;
+}
+
+// ibid.: a linear-phase notch at nlines frequencies.  g is gpsiq_filter_design's window and sinc, unrounded, at cutoff width_hz / 2 and
+// sum 1; its zero-phase response G0(w) = sum g[n] cos(w (n - c)) is real, and the unrounded filter's response is
+// e^(-j w c) (1 - sum_l a_l G0(w - w_l)): zero at every w_m where  sum_l a_l G0(w_m - w_l) = 1, a real symmetric system with a unit
+// diagonal.  Taps at distance d either side of the centre come from the same numbers, so taps[c + d] = conj(taps[c - d]) to the bit
+int gpsiq_notch_design(double fs, const double *f_hz, int nlines, double width_hz, int ntaps, int shift, gpsiq_ctap_t *taps)
+{
+    if (!taps || !f_hz) return fail(GPSIQ_E_ARG, "null argument");
+    if (ntaps < 3 || ntaps > kFiltMaxTaps - 1 || !(ntaps & 1)) return fail(GPSIQ_E_ARG, "ntaps %d: odd, 3..%d", ntaps, kFiltMaxTaps - 1);
+    if (shift < 8 || shift > 14) return fail(GPSIQ_E_ARG, "shift %d: 8..14", shift);
+    if (nlines < 1 || nlines > 8) return fail(GPSIQ_E_ARG, "nlines %d outside 1..8", nlines);
+    if (!(fs > 0.0) || !std::isfinite(fs) || !(width_hz > 0.0) || !(width_hz < fs)) return fail(GPSIQ_E_ARG, "width %g Hz outside (0, fs) at fs %g", width_hz, fs);
+    for (int l = 0; l < nlines; ++l) {
+        if (!(std::fabs(f_hz[l]) < fs / 2.0)) return fail(GPSIQ_E_ARG, "line %d at %g Hz outside (-fs / 2, fs / 2)", l, f_hz[l]);
+        for (int m = 0; m < l; ++m) {
+            const double d = std::fabs(f_hz[l] - f_hz[m]), cyc = d < fs - d ? d : fs - d;
+            if (cyc < width_hz) return fail(GPSIQ_E_ARG, "lines %d and %d are %g Hz apart, closer than the width %g", m, l, cyc, width_hz);
+        }
+    }
+    const double pi = 3.14159265358979323846, w = width_hz / fs;
+    const int mid = (ntaps - 1) / 2;
+    double g[kFiltMaxTaps / 2], sum = 0.0;                              // by the distance from the centre
+    for (int d = 0; d <= mid; ++d) {
+        const double x = w * (double) d, sinc = d ? std::sin(pi * x) / (pi * x) : 1.0;
+        g[d] = w * sinc * (0.54 - 0.46 * std::cos(2.0 * pi * (double) (mid - d) / (double) (ntaps - 1)));
+        sum += d ? 2.0 * g[d] : g[d];
+    }
+    for (int d = 0; d <= mid; ++d) g[d] /= sum;
+    const auto g0 = [&](double omega) { double r = g[0]; for (int d = 1; d <= mid; ++d) r += 2.0 * g[d] * std::cos(omega * (double) d); return r; };
+    double om[8], m[8][9];
+    for (int l = 0; l < nlines; ++l) om[l] = 2.0 * pi * f_hz[l] / fs;
+    for (int r = 0; r < nlines; ++r) {
+        for (int l = 0; l < nlines; ++l) m[r][l] = r == l ? 1.0 : g0(om[r] - om[l]);
+        m[r][nlines] = 1.0;
+    }
+    for (int col = 0; col < nlines; ++col) {                           // Gauss-Jordan with partial pivoting
+        int piv = col;
+        for (int r = col + 1; r < nlines; ++r) if (std::fabs(m[r][col]) > std::fabs(m[piv][col])) piv = r;
+        if (!(std::fabs(m[piv][col]) > 1e-9)) return fail(GPSIQ_E_ARG, "the lines' system is singular");
+        for (int k = 0; k <= nlines; ++k) std::swap(m[col][k], m[piv][k]);
+        for (int r = 0; r < nlines; ++r) {
+            if (r == col) continue;
+            const double f = m[r][col] / m[col][col];
+            for (int k = col; k <= nlines; ++k) m[r][k] -= f * m[col][k];
+        }
+    }
+    double a[8];
+    for (int l = 0; l < nlines; ++l) a[l] = m[l][nlines] / m[l][l];
+    const double scale = std::ldexp(1.0, shift);
+    long mag = 0;
+    long q[kFiltMaxTaps / 2][2];
+    for (int d = 0; d <= mid; ++d) {
+        double re = d ? 0.0 : 1.0, im = 0.0;
+        for (int l = 0; l < nlines; ++l) { re -= a[l] * g[d] * std::cos(om[l] * (double) d); im -= a[l] * g[d] * std::sin(om[l] * (double) d); }
+        q[d][0] = std::lrint(scale * re);
+        q[d][1] = d ? std::lrint(scale * im) : 0;
+        if (q[d][0] > 32767 || q[d][0] < -32767 || q[d][1] > 32767 || q[d][1] < -32767) return fail(GPSIQ_E_RANGE, "a tap leaves int16 at shift %d", shift);
+        mag += (d ? 2 : 1) * (std::labs(q[d][0]) + std::labs(q[d][1]));
+    }
+    if (mag > kCfiltTapSum) return fail(GPSIQ_E_RANGE, "sum |re| + |im| %ld above %ld at shift %d", mag, kCfiltTapSum, shift);
+    for (int d = 0; d <= mid; ++d) {
+        taps[mid + d].re = taps[mid - d].re = (int16_t) q[d][0];
+        taps[mid + d].im = (int16_t) q[d][1];
+        taps[mid - d].im = (int16_t) -q[d][1];
+    }
     return GPSIQ_OK;
 }
 

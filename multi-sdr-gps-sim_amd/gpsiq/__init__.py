@@ -200,6 +200,30 @@ _agc_span = _sig("gpsiq_agc_span", _i, _u64, _i, C.c_uint32, C.POINTER(_u64), C.
 _generate_batch_agc = _sig("gpsiq_generate_batch_agc", _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _vp, _sz, C.POINTER(_u64), C.POINTER(_u64), _vp)
 _agc_last_plan = _sig("gpsiq_agc_last_plan", _i, _vp, _vp)
 _agc_last_ms = _sig("gpsiq_agc_last_ms", _i, _vp, _vp)
+_cfilter = _sig("gpsiq_cfilter", _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_cfilter_last_plan = _sig("gpsiq_cfilter_last_plan", _i, _vp, _vp)
+_notch_find = _sig("gpsiq_notch_find", _i, _vp, _i, _d, _d, _i, _vp, _vp, C.POINTER(_i))
+_notch_design = _sig("gpsiq_notch_design", _i, _d, _vp, _i, _d, _i, _i, _vp)
+
+
+class CTap(C.Structure):
+    """gpsiq_ctap_t (include/gpsiq_rows.h, "Complex filter and notch"): one complex tap, re + j im."""
+    _fields_ = [("re", C.c_int16), ("im", C.c_int16)]
+
+
+def ctaps(taps):
+    """Complex taps as the int16 array [n, 2] (re, im) gpsiq_cfilter takes: from such an array, from a sequence of CTap, or from a ctypes
+    array of CTap."""
+    if isinstance(taps, C.Array) and getattr(taps, "_type_", None) is CTap:
+        return np.frombuffer(taps, dtype=np.int16).reshape(-1, 2).copy()
+    if not isinstance(taps, np.ndarray) and len(taps) and isinstance(taps[0], CTap):
+        return np.array([(t.re, t.im) for t in taps], dtype=np.int16).reshape(-1, 2)
+    a = np.asarray(taps)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise GpsiqError(-1, f"complex taps are [n, 2] (re, im), not an array of shape {a.shape}")
+    if a.size and (a.min() < -32768 or a.max() > 32767):
+        raise GpsiqError(-1, "a complex tap does not fit int16")
+    return np.ascontiguousarray(a, dtype=np.int16)
 
 
 class AgcCfg(C.Structure):
@@ -834,6 +858,27 @@ def agc_span(nsamp, window, fill=0):
     return int(nwin.value), int(nxt.value)
 
 
+def notch_find(power, fs, ratio=8.0, max_lines=8):
+    """gpsiq_notch_find: the lines of ONE group of a spectrum (uint64 [nfft]) -> (f_hz, excess_db, nlines): float arrays of the
+    min(nlines, max_lines) strongest lines, strongest first, and the number of lines found before that cap."""
+    power = np.ascontiguousarray(power, dtype=np.uint64)
+    if power.ndim != 1:
+        raise GpsiqError(-1, f"one group of a spectrum is a vector, not an array of shape {power.shape}")
+    f, ex, n = np.zeros(8, np.float64), np.zeros(8, np.float64), _i(0)
+    _check(_notch_find(_p(power), len(power), float(fs), float(ratio), int(max_lines), _p(f), _p(ex), C.byref(n)))
+    keep = min(int(n.value), int(max_lines))
+    return f[:keep].copy(), ex[:keep].copy(), int(n.value)
+
+
+def notch_design(fs, f_hz, width_hz, ntaps, shift=12):
+    """gpsiq_notch_design: int16 [ntaps, 2] (re, im) of a linear-phase notch at the frequencies f_hz (1..8 of them), each width_hz wide,
+    over 2^shift."""
+    f = np.ascontiguousarray(np.atleast_1d(f_hz), dtype=np.float64)
+    taps = np.zeros((max(int(ntaps), 1), 2), dtype=np.int16)
+    _check(_notch_design(float(fs), _p(f), len(f), float(width_hz), int(ntaps), int(shift), _p(taps)))
+    return taps
+
+
 def resample_step(fs_in, fs_out, ppb=0.0):
     """gpsiq_resample_step: the step from a stream at fs_in to a receiver at fs_out whose clock runs ppb parts per billion fast."""
     step = _u64(0)
@@ -1176,6 +1221,21 @@ class Context:
         _check(_filter(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(head_ptr or 0), _p(taps) if len(taps) else None, len(taps), int(shift),
                        int(decim), int(phase), int(out_sample_size), _vp(dst_device_ptr), _vp(stream or 0), C.byref(nout), C.byref(clipped), C.byref(ms)))
         return nout.value, int(clipped.value), float(ms.value)
+
+    def cfilter(self, nsamp, sample_size, device_ptr, taps, shift, decim, phase, out_sample_size, dst_device_ptr, head_ptr=None, stream=None):
+        """gpsiq_cfilter: gpsiq_filter with complex taps ([n, 2] int16 (re, im), or CTap: ctaps()) -> (outputs written, elements the clamp
+        changed, kernel milliseconds), as filter()."""
+        taps = ctaps(taps)
+        nout, clipped, ms = _i(0), C.c_uint64(0), C.c_float(0.0)
+        _check(_cfilter(self._h, int(nsamp), int(sample_size), _vp(device_ptr), _vp(head_ptr or 0), _p(taps) if len(taps) else None, len(taps), int(shift),
+                        int(decim), int(phase), int(out_sample_size), _vp(dst_device_ptr), _vp(stream or 0), C.byref(nout), C.byref(clipped), C.byref(ms)))
+        return nout.value, int(clipped.value), float(ms.value)
+
+    def cfilter_last_plan(self):
+        """What the last cfilter() took: (kernel name or None, grid, outputs of a workgroup's run, k-steps of a tile)."""
+        out = (C.c_long * 4)()
+        _check(_cfilter_last_plan(self._h, out))
+        return {0: "generic", 1: "mfma", 2: "mfma16"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def generate_batch_filtered(self, desc, nsamp, fs, sample_size, taps, shift, decim, out_sample_size, host_ptr=None, block_stride=None,
                                 carr_out=None):
