@@ -18,11 +18,12 @@
 #include "gpsiq_ctx.h"
 #include "gpsiq_acquire_geometry.h"
 #include "gpsiq_signal.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
 
-typedef int acq_i32x4 __attribute__((ext_vector_type(4)));
+using stream::i32x4;
 
 // +1 / -1 of replica sample n: chip ((n * code_step) >> 56) % 1023 of the satellite whose packed code is ext (bit set: -1)
 __device__ __forceinline__ int acq_code(const uint32_t *ext, uint64_t code_step, uint32_t n)
@@ -189,17 +190,17 @@ __global__ __launch_bounds__(kAcqWaves * 64) void acquire_mfma(
         const uint64_t h = (uint64_t) k * (uint64_t) hop;
         const int hr = (int) (h & 15);
         const uint8_t *a_ptr = tile_planes + (S0 + (h & ~UINT64_C(15))) * 16;
-        acq_i32x4 D[16];
+        i32x4 D[16];
 #pragma unroll
-        for (int a = 0; a < 16; ++a) D[a] = acq_i32x4{0, 0, 0, 0};
+        for (int a = 0; a < 16; ++a) D[a] = i32x4{0, 0, 0, 0};
         for (int t = 0; t < ksteps; ++t) {
-            const acq_i32x4 A = *reinterpret_cast<const acq_i32x4 *>(a_ptr + (uint64_t) t * (kAcqK * 16));
+            const i32x4 A = *reinterpret_cast<const i32x4 *>(a_ptr + (uint64_t) t * (kAcqK * 16));
             const int u0 = 4 * t + g - c;
 #pragma unroll
             for (int a = 0; a < 16; ++a) {
                 const int w = a + hr, u = u0 - (w >> 4);
                 const int unit = (u < -1 ? -1 : u > ulast ? ulast : u) + 1;       // 0 and ulast + 1: the zero units
-                const acq_i32x4 B = *reinterpret_cast<const acq_i32x4 *>(copies + (w & 15) * clen + unit * 16);
+                const i32x4 B = *reinterpret_cast<const i32x4 *>(copies + (w & 15) * clen + unit * 16);
                 D[a] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, D[a], 0, 0, 0);
             }
         }

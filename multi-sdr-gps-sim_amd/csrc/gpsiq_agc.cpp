@@ -17,8 +17,7 @@ namespace {
 int check_cfg(const gpsiq_agc_cfg_t *cfg, int sample_size, int out_sample_size)
 {
     if (!cfg) return fail(GPSIQ_E_ARG, "null configuration");
-    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
-    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (int rc = check_formats(sample_size, out_sample_size)) return rc;
     if (cfg->window < kAgcMinWindow || cfg->window > kAgcMaxWindow || cfg->window % 64) return fail(GPSIQ_E_ARG, "window %d: a multiple of 64 in %d..%d", (int) cfg->window, kAgcMinWindow, kAgcMaxWindow);
     if (cfg->navg < 1 || cfg->navg > kAgcMaxAvg) return fail(GPSIQ_E_ARG, "navg %d outside 1..%d", (int) cfg->navg, kAgcMaxAvg);
     if (cfg->target_q8 < 1 || cfg->target_q8 > kAgcMaxTarget) return fail(GPSIQ_E_ARG, "target_q8 %u outside 1..2^23-1", (unsigned) cfg->target_q8);
@@ -150,8 +149,7 @@ int gpsiq_generate_batch_agc_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int nb
     if (!c || (!ch && nblocks) || (!dst && nblocks && nsamp)) return fail(GPSIQ_E_ARG, "null argument");
     if (int rc = check_cfg(cfg, sample_size, out_sample_size)) return rc;
     if (int rc = check_state(cfg, state)) return rc;
-    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
-    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (int rc = check_batch_shape(nblocks, nchan, nsamp, fs)) return rc;
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, row_bytes = (size_t) 2 * (size_t) nsamp * (size_t) out_sample_size;
     if (dst_block_stride < row_bytes) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
     if (clipped) *clipped = 0;

@@ -313,7 +313,7 @@ __global__ __launch_bounds__(kAgcThreads) void agc_apply(const uint8_t *__restri
             }
         }
     }
-    // per wave, then per workgroup; one atomic of the workgroup if it clamped anything
+    // count_clipped's steps (gpsiq_stream.h), kept in place: calling the shared one changes this kernel's code object
     for (int off = 32; off >= 1; off >>= 1) clipped += __shfl_xor(clipped, off, 64);
     __shared__ unsigned long long part[kAgcThreads / 64];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = clipped;

@@ -3,7 +3,6 @@
 // (gpsiq_cfilter_kernels.hip holds the stage's kernels; an int8 input on the matrix path takes filter_mfma of gpsiq_filter_kernels.hip
 // with the complex planes), launch and count.  libgpsiq_rows.so exports the typed call and reaches this through the plumbing entry
 // "cfilter".  Host code: nothing here decides device code, so the file is not one of the device sources behind gpsiq_kernels_id().
-#include <cstdlib>
 #include <cstring>
 
 #include "gpsiq_ctx.h"
@@ -16,12 +15,7 @@ static_assert(sizeof(gpsiq_ctap_t) == 4, "gpsiq_ctap_t is two int16");
 
 namespace {
 
-int forced_kernel()
-{
-    const char *env = std::getenv("GPSIQ_CFILTER_KERNEL");
-    if (!env) return kCfiltAuto;
-    return !std::strcmp(env, "generic") ? kCfiltForceGeneric : !std::strcmp(env, "mfma") ? kCfiltForceMfma : kCfiltAuto;
-}
+static_assert(kCfiltAuto == 0 && kCfiltForceGeneric == 1 && kCfiltForceMfma == 2, "forced_kernel's values (gpsiq_stage_call.h)");
 
 void note_plan(gpsiq_ctx *c, const FilterPlan &p)
 {
@@ -33,14 +27,42 @@ void note_plan(gpsiq_ctx *c, const FilterPlan &p)
 // synchronised.
 int stage_coefficients(gpsiq_ctx *c, const int16_t *re_im, int ntaps, int decim, const FilterPlan &p, hipStream_t s)
 {
-    CfilterSet &k = c->cfilt;
+    FirSet &k = c->cfilt;
     std::memcpy(k.h_coef.get(), re_im, 4 * (size_t) ntaps);
-    size_t bytes = CfilterSet::kTapBytes;
+    size_t bytes = FirSet::kTapBytes;
     if (p.kernel != kCfiltGeneric) {
-        cfilter_build_planes(re_im, ntaps, decim, p.steps, reinterpret_cast<int8_t *>(k.h_coef.get() + CfilterSet::kTapBytes));
+        cfilter_build_planes(re_im, ntaps, decim, p.steps, reinterpret_cast<int8_t *>(k.h_coef.get() + FirSet::kTapBytes));
         bytes += (size_t) filter_mfma_plane_bytes(p.steps);
     }
     HIP_TRY(hipMemcpyAsync(k.d_coef.get(), k.h_coef.get(), bytes, hipMemcpyHostToDevice, s));
+    return GPSIQ_OK;
+}
+
+// the filter queued on s behind its coefficients (the counter is counted_call's to zero)
+int queue_cfilter(gpsiq_ctx *c, const FilterPlan &p, int nsamp, int sample_size, const uint8_t *src, const uint8_t *head, const int16_t *re_im, int ntaps,
+                  int shift, int decim, int phase, int out_sample_size, uint8_t *dst, hipStream_t s)
+{
+    FirSet &k = c->cfilt;
+    const uint8_t *planes = k.d_coef.get() + FirSet::kTapBytes;
+    if (p.kernel == kCfiltMfma) {
+        const FilterMfmaFn kernel = filter_mfma_kernel(out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no matrix filter kernel for %d-byte outputs", out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, planes, ntaps, shift, decim, phase, dst, p.nout, p.run, p.runs, p.steps,
+                           k.clip.d_count.get());
+    } else if (p.kernel == kCfiltMfma16) {
+        const CfilterMfma16Fn kernel = cfilter_mfma16_kernel(out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no int16 matrix filter kernel for %d-byte outputs", out_sample_size);
+        int32_t rc2[2];
+        cfilter_row_consts(re_im, ntaps, rc2);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, planes, ntaps, shift, decim, phase, dst, p.nout, p.run, p.runs, p.steps,
+                           (int) rc2[0], (int) rc2[1], k.clip.d_count.get());
+    } else {
+        const CfilterGenericFn kernel = cfilter_generic_kernel(sample_size, out_sample_size);
+        if (!kernel) return fail(GPSIQ_E_DEVICE, "no complex filter kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, reinterpret_cast<const uint32_t *>(k.d_coef.get()), ntaps, shift,
+                           decim, phase, dst, p.nout, p.run, p.runs, k.clip.d_count.get());
+    }
+    HIP_TRY(hipGetLastError());
     return GPSIQ_OK;
 }
 
@@ -50,8 +72,7 @@ int gpsiq_cfilter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *s
                        int decim, int phase, int out_sample_size, void *dst, void *hip_stream, int *nout, uint64_t *clipped, float *kernel_ms)
 {
     if (!c) return fail(GPSIQ_E_ARG, "null context");
-    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
-    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (int rc = check_formats(sample_size, out_sample_size)) return rc;
     if (ntaps < 1 || ntaps > kFiltMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kFiltMaxTaps);
     if (decim < 1 || decim > kFiltMaxDecim) return fail(GPSIQ_E_ARG, "decim %d outside 1..%d", decim, kFiltMaxDecim);
     if (shift < 0 || shift > kFiltMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kFiltMaxShift);
@@ -61,16 +82,8 @@ int gpsiq_cfilter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *s
     if (st.mag > kCfiltTapSum) return fail(GPSIQ_E_RANGE, "sum |re| + |im| %ld above %ld: the accumulator would not hold the sum", st.mag, kCfiltTapSum);
     if (phase < 0 || phase >= decim) return fail(GPSIQ_E_ARG, "phase %d outside [0, decim %d)", phase, decim);
     if (nsamp < 0) return fail(GPSIQ_E_ARG, "negative size");
-    const FilterPlan p = plan_cfilter(nsamp, sample_size, ntaps, decim, phase, st, forced_kernel());
-    if (!src && nsamp) return fail(GPSIQ_E_ARG, "null source");
-    if (!dst && p.nout) return fail(GPSIQ_E_ARG, "null destination");
-    if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
-    if ((uintptr_t) head & 3) return fail(GPSIQ_E_ARG, "head %p not 4-byte aligned", head);
-    if ((uintptr_t) dst & 3) return fail(GPSIQ_E_ARG, "destination %p not 4-byte aligned", dst);
-    const size_t src_len = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, head_len = head ? (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size : 0;
-    const size_t dst_len = (size_t) 2 * (size_t) p.nout * (size_t) out_sample_size;
-    if (overlap(dst, dst_len, src, src_len)) return fail(GPSIQ_E_ARG, "source [%p, +%zu) and destination [%p, +%zu) overlap", src, src_len, dst, dst_len);
-    if (overlap(dst, dst_len, head, head_len)) return fail(GPSIQ_E_ARG, "head [%p, +%zu) and destination [%p, +%zu) overlap", head, head_len, dst, dst_len);
+    const FilterPlan p = plan_cfilter(nsamp, sample_size, ntaps, decim, phase, st, forced_kernel("GPSIQ_CFILTER_KERNEL", "mfma"));
+    if (int rc = check_span(src, nsamp, sample_size, head, ntaps, dst, (uint64_t) p.nout, out_sample_size)) return rc;
     if (nout) *nout = p.nout;
     if (clipped) *clipped = 0;
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -78,39 +91,13 @@ int gpsiq_cfilter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *s
     if (!p.launch) return GPSIQ_OK;                                   // no output: nothing to write
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    CfilterSet &k = c->cfilt;
+    FirSet &k = c->cfilt;
     if (int rc = k.reserve()) return rc;
     if (int rc = stage_coefficients(c, re_im, ntaps, decim, p, s)) return rc;
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
-    HIP_TRY(hipEventRecord(k.t0.get(), s));
-    const uint8_t *s8 = static_cast<const uint8_t *>(src), *h8 = static_cast<const uint8_t *>(head);
-    const uint8_t *planes = k.d_coef.get() + CfilterSet::kTapBytes;
-    uint8_t *d8 = static_cast<uint8_t *>(dst);
-    if (p.kernel == kCfiltMfma) {
-        const FilterMfmaFn kernel = filter_mfma_kernel(out_sample_size);
-        if (!kernel) return fail(GPSIQ_E_DEVICE, "no matrix filter kernel for %d-byte outputs", out_sample_size);
-        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, s8, nsamp, h8, planes, ntaps, shift, decim, phase, d8, p.nout, p.run, p.runs, p.steps,
-                           k.d_count.get());
-    } else if (p.kernel == kCfiltMfma16) {
-        const CfilterMfma16Fn kernel = cfilter_mfma16_kernel(out_sample_size);
-        if (!kernel) return fail(GPSIQ_E_DEVICE, "no int16 matrix filter kernel for %d-byte outputs", out_sample_size);
-        int32_t rc2[2];
-        cfilter_row_consts(re_im, ntaps, rc2);
-        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, s8, nsamp, h8, planes, ntaps, shift, decim, phase, d8, p.nout, p.run, p.runs, p.steps,
-                           (int) rc2[0], (int) rc2[1], k.d_count.get());
-    } else {
-        const CfilterGenericFn kernel = cfilter_generic_kernel(sample_size, out_sample_size);
-        if (!kernel) return fail(GPSIQ_E_DEVICE, "no complex filter kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
-        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, s8, nsamp, h8, reinterpret_cast<const uint32_t *>(k.d_coef.get()), ntaps, shift,
-                           decim, phase, d8, p.nout, p.run, p.runs, k.d_count.get());
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(k.t1.get(), s));
-    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (clipped) *clipped = (uint64_t) k.h_count[0];
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
-    return GPSIQ_OK;
+    return counted_call(k.clip, s, [&] {
+        return queue_cfilter(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), re_im, ntaps, shift, decim, phase,
+                             out_sample_size, static_cast<uint8_t *>(dst), s);
+    }, clipped, kernel_ms);
 }
 
 extern "C" int gpsiq_cfilter_last_plan(const gpsiq_ctx_t *c, long out[4])

@@ -7,71 +7,24 @@
 //                              the taps (gpsiq_cfilter_geometry.h)
 // An int8 input on the matrix path is filter_mfma<OUT> of gpsiq_filter_kernels.hip itself, launched with the complex planes.
 // sum (|re[k]| + |im[k]|) <= 65535 (checked on the host) and |x| <= 32768 give |acc| <= 2^31 - 32768: one accumulator width, no
-// saturation inside the sum.  finish(), store_sample() and count_clipped() are gpsiq_filter_kernels.hip's, restated: that file's are
-// local to it, and its code objects do not move.
+// saturation inside the sum.  sample_at(), finish(), store_sample() and count_clipped() are gpsiq_stream.h's, as gpsiq_filter_kernels.hip's
+// are.
 // Every offset into src / dst is 64 bits wide.  Sample m of the span is read only for 0 <= m < nsamp, sample m < 0 from head (or as
 // zero); outputs j < nout are written and nothing else.  No workgroup waits for another; a workgroup strides over the runs.
 #include <hip/hip_runtime.h>
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_cfilter_geometry.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
 
-typedef int cfilt_i32x4 __attribute__((ext_vector_type(4)));
-
-// sample m of the stream as one dword: I in the low half, Q in the high half, each sign-extended to 16 bits
-template <int FMT>
-__device__ __forceinline__ uint32_t load_pair(const uint8_t *base, int64_t m)
-{
-    if (FMT == GPSIQ_SC16) return *reinterpret_cast<const uint32_t *>(base + (uint64_t) m * 4);
-    const uint32_t v = *reinterpret_cast<const uint16_t *>(base + (uint64_t) m * 2);
-    return ((uint32_t) (int32_t) (int8_t) (v & 0xffu) & 0xffffu) | ((uint32_t) (int32_t) (int8_t) (v >> 8) << 16);
-}
-
-// x(m) of the contract: the span, the head before it, zeros before that and where there is no head
-template <int FMT>
-__device__ __forceinline__ uint32_t sample_at(const uint8_t *src, const uint8_t *head, int64_t m, int nsamp, int ntaps)
-{
-    if (m >= 0) return m < (int64_t) nsamp ? load_pair<FMT>(src, m) : 0u;
-    return head && m >= -(int64_t) (ntaps - 1) ? load_pair<FMT>(head, (int64_t) (ntaps - 1) + m) : 0u;
-}
-
-// y = floor((acc + 2^(shift-1)) / 2^shift), clamped to +-QMAX; clipped counts the elements the clamp changed
-template <int OUT>
-__device__ __forceinline__ int finish(int acc, int shift, unsigned &clipped)
-{
-    constexpr int QMAX = OUT == GPSIQ_SC08 ? 127 : 32767;
-    const int64_t half = shift ? (int64_t) 1 << (shift - 1) : 0;
-    const int64_t y = ((int64_t) acc + half) >> shift;
-    const int64_t c = y < -QMAX ? -QMAX : y > QMAX ? QMAX : y;
-    clipped += c != y;
-    return (int) c;
-}
-
-template <int OUT>
-__device__ __forceinline__ void store_sample(uint8_t *dst, uint64_t j, int i, int q)
-{
-    if (OUT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(dst + j * 4) = ((uint32_t) i & 0xffffu) | ((uint32_t) q << 16);
-    else *reinterpret_cast<uint16_t *>(dst + j * 2) = (uint16_t) (((uint32_t) i & 0xffu) | (((uint32_t) q & 0xffu) << 8));
-}
-
-// per wave, then per workgroup; one atomic of the workgroup if it clamped anything.  Every thread of the workgroup arrives here.
-// (The four partial counts are the kernels' only static LDS: 32 bytes, so the dynamic region behind them stays 16-byte aligned.)
-__device__ __forceinline__ void count_clipped(unsigned long long clipped, unsigned long long *count)
-{
-    for (int off = 32; off >= 1; off >>= 1) clipped += __shfl_xor(clipped, off, 64);
-    __shared__ unsigned long long part[kFiltThreads / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-#pragma unroll
-        for (int k = 0; k < kFiltThreads / 64; ++k) sum += part[k];
-        if (sum) atomicAdd(count, sum);
-    }
-}
+using stream::i32x4;
+using stream::sample_at;
+using stream::finish;
+using stream::store_sample;
+using stream::count_clipped;
 
 // Arguments: span and its samples, head (may be null), device taps as dwords (re low, im high), ntaps, shift, decim, phase,
 // destination, outputs of the span, outputs of a run, runs of the launch (gpsiq_cfilter_plan.h), the counter (zeroed by the host).
@@ -111,7 +64,7 @@ __global__ __launch_bounds__(kFiltThreads) void cfilter_generic(const uint8_t *_
             store_sample<OUT>(dst, (uint64_t) (j0 + o), finish<OUT>(ai, shift, clipped), finish<OUT>(aq, shift, clipped));
         }
     }
-    count_clipped(clipped, count);
+    count_clipped<kFiltThreads>(clipped, count);
 }
 
 // Arguments as cfilter_generic's, with the digit planes in the taps' place, the k-steps of a tile behind the run, and the two row
@@ -140,7 +93,7 @@ __global__ __launch_bounds__(kFiltThreads) void cfilter_mfma16(const uint8_t *__
     uint8_t *win_lo = cfilt_lds + plane_bytes, *win_hi = win_lo + wbytes;
     const int wsamp = wbytes / 2;                                                                    // samples staged per run
     for (int i = tid; i < plane_bytes / 16; i += kFiltThreads)
-        reinterpret_cast<cfilt_i32x4 *>(cfilt_lds)[i] = reinterpret_cast<const cfilt_i32x4 *>(planes)[i];
+        reinterpret_cast<i32x4 *>(cfilt_lds)[i] = reinterpret_cast<const i32x4 *>(planes)[i];
     const int col = lane & 15, q = lane >> 4;
     unsigned clipped = 0;
     for (uint64_t r = blockIdx.x; r < runs; r += gridDim.x) {
@@ -158,12 +111,12 @@ __global__ __launch_bounds__(kFiltThreads) void cfilter_mfma16(const uint8_t *__
             const int b_off = 2 * decim * (kFiltTileOutputs * tile + kFiltColOutputs * col) + 16 * q;
             const uint8_t *lo_ptr = win_lo + b_off, *hi_ptr = win_hi + b_off;
             const uint8_t *a_ptr = cfilt_lds + lane * 16;
-            cfilt_i32x4 p00 = {0, 0, 0, 0}, pmid = {0, 0, 0, 0}, p11 = {0, 0, 0, 0};
+            i32x4 p00 = {0, 0, 0, 0}, pmid = {0, 0, 0, 0}, p11 = {0, 0, 0, 0};
             for (int t = 0; t < steps; ++t) {
-                const cfilt_i32x4 lo = *reinterpret_cast<const cfilt_i32x4 *>(lo_ptr + t * kFiltK);
-                const cfilt_i32x4 hi = *reinterpret_cast<const cfilt_i32x4 *>(hi_ptr + t * kFiltK);
-                const cfilt_i32x4 a0 = *reinterpret_cast<const cfilt_i32x4 *>(a_ptr + t * (kFiltK * 16));
-                const cfilt_i32x4 a1 = *reinterpret_cast<const cfilt_i32x4 *>(a_ptr + (steps + t) * (kFiltK * 16));
+                const i32x4 lo = *reinterpret_cast<const i32x4 *>(lo_ptr + t * kFiltK);
+                const i32x4 hi = *reinterpret_cast<const i32x4 *>(hi_ptr + t * kFiltK);
+                const i32x4 a0 = *reinterpret_cast<const i32x4 *>(a_ptr + t * (kFiltK * 16));
+                const i32x4 a1 = *reinterpret_cast<const i32x4 *>(a_ptr + (steps + t) * (kFiltK * 16));
                 p00 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, lo, p00, 0, 0, 0);
                 pmid = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, hi, pmid, 0, 0, 0);
                 pmid = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, lo, pmid, 0, 0, 0);
@@ -179,7 +132,7 @@ __global__ __launch_bounds__(kFiltThreads) void cfilter_mfma16(const uint8_t *__
             }
         }
     }
-    count_clipped(clipped, count);
+    count_clipped<kFiltThreads>(clipped, count);
 }
 
 }  // namespace

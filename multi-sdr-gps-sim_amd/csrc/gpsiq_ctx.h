@@ -4,7 +4,8 @@
 // on the device), and by the host side of every stream stage.  This header keeps the context itself, the first-use routines of the
 // chain and the device evaluation, what the translation units above use of each other, and the synthesis kernels by type.  What a
 // stream stage keeps in the context is in that stage's header, included below; what the staged batch calls share (the staging ring
-// and the piece loop) is in gpsiq_stage_batch.h; HIP_TRY is in gpsiq_own.h.
+// and the piece loop) is in gpsiq_stage_batch.h, what a stage's single call does around its kernel in gpsiq_stage_call.h; HIP_TRY
+// is in gpsiq_own.h.
 //
 // The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample, agc, cfilter):
 //   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
@@ -14,6 +15,10 @@
 //   gpsiq_<s>_plan.h            the plan, pure host arithmetic (pinned on the CPU by the tests)
 //   gpsiq_<s>_geometry.h        the constants plan and kernels share              } device sources: in the Makefile's DEVSRC,
 //   gpsiq_<s>_kernels.hip       the kernels and the table of those that exist     } behind gpsiq_kernels_id()
+//   gpsiq_stream.h              what the kernels of several stages do alike with a stream: sample in, sample out, round and clamp,
+//                               count (a device source too); a new stage's kernels take theirs from it
+//   gpsiq_stage_call.h          what the calls of several stages do alike around their kernel: the counter and its timed call
+//                               (ClipCount, counted_call), check_formats / check_span / check_batch_shape, forced_kernel
 //   gpsiq_device.cpp            one line of the gpsiq_plumbing() table: {"<s>", &gpsiq_<s>_impl}
 //   gpsiq_rows_link.cpp         the exported gpsiq_<s> of libgpsiq_rows.so: core<decltype(&gpsiq_<s>)>("<s>")
 //   gpsiq_stage_math.cpp        its helpers that are plain arithmetic (libgpsiq_rows.so)
@@ -32,6 +37,7 @@
 #include "gpsiq_own.h"
 #include "gpsiq_pieces.h"
 #include "gpsiq_stage_batch.h"
+#include "gpsiq_stage_call.h"
 #include "gpsiq_despread.h"
 #include "gpsiq_pack.h"
 #include "gpsiq_acquire.h"
@@ -182,12 +188,12 @@ struct gpsiq_ctx {
     gpsiq::PackSet     pack;
     gpsiq::AcquireSet  acq;
     gpsiq::FollowSet   fol;
-    gpsiq::FilterSet   filt;
+    gpsiq::FirSet      filt;
     gpsiq::SpectrumSet spec;
     gpsiq::MixSet      mix;
     gpsiq::ResampleSet rs;
     gpsiq::AgcSet      agc;
-    gpsiq::CfilterSet  cfilt;
+    gpsiq::FirSet      cfilt;               // (its own: nothing is shared between the two filters at run time)
     // the staging the five staged batch calls (_packed, _filtered, _mixed, _resampled, _agc) work through their pieces with: one ring for
     // all of them -- calls on a context are serial and every one ends with the ring's streams drained (gpsiq_stage_batch.h)
     gpsiq::PieceRing   ring;

@@ -19,8 +19,7 @@ struct TapStats { long mag = 0; int max_tap = 0; };
 // what both calls ask of the filter itself
 int check_taps(const int16_t *taps, int ntaps, int shift, int decim, int sample_size, int out_sample_size, TapStats *st)
 {
-    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
-    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (int rc = check_formats(sample_size, out_sample_size)) return rc;
     if (ntaps < 1 || ntaps > kFiltMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kFiltMaxTaps);
     if (decim < 1 || decim > kFiltMaxDecim) return fail(GPSIQ_E_ARG, "decim %d outside 1..%d", decim, kFiltMaxDecim);
     if (shift < 0 || shift > kFiltMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kFiltMaxShift);
@@ -34,12 +33,7 @@ int check_taps(const int16_t *taps, int ntaps, int shift, int decim, int sample_
     return GPSIQ_OK;
 }
 
-int forced_kernel()
-{
-    const char *env = std::getenv("GPSIQ_FILTER_KERNEL");
-    if (!env) return kFiltAuto;
-    return !std::strcmp(env, "generic") ? kFiltForceGeneric : !std::strcmp(env, "mfma") ? kFiltForceMfma : kFiltAuto;
-}
+static_assert(kFiltAuto == 0 && kFiltForceGeneric == 1 && kFiltForceMfma == 2, "forced_kernel's values (gpsiq_stage_call.h)");
 
 void note_plan(gpsiq_ctx *c, const FilterPlan &p, long pieces)
 {
@@ -47,31 +41,17 @@ void note_plan(gpsiq_ctx *c, const FilterPlan &p, long pieces)
 }
 
 // The coefficients of a call, page-locked, then queued for the device on s: the taps as dwords, and behind them the two digit planes
-// of the matrix kernel in fragment order (gpsiq_filter_geometry.h) -- lane l = (row i = l & 15, group g = l >> 4) of k-step t holds
-// bytes j = 0..15, k = 64 t + 16 g + j, of A(i, k) = T[2 jj decim + c + 2 (ntaps - 1) - k], i = 2 jj + c, T the taps zero-stuffed.
+// of the matrix kernel (filter_build_planes, gpsiq_filter_plan.h).
 // The caller has made sure nothing queued earlier still reads h_coef (every call ends synchronised).
 int stage_coefficients(gpsiq_ctx *c, const int16_t *taps, int ntaps, int decim, const FilterPlan &p, hipStream_t s)
 {
-    FilterSet &k = c->filt;
+    FirSet &k = c->filt;
     int32_t *t32 = reinterpret_cast<int32_t *>(k.h_coef.get());
     for (int i = 0; i < ntaps; ++i) t32[i] = taps[i];
-    size_t bytes = FilterSet::kTapBytes;
+    size_t bytes = FirSet::kTapBytes;
     if (p.kernel == kFiltMfma) {
-        int8_t *pl = reinterpret_cast<int8_t *>(k.h_coef.get() + FilterSet::kTapBytes);
-        const size_t plane = (size_t) p.steps * kFiltK * 16;
-        std::memset(pl, 0, 2 * plane);
-        for (int i = 0; i < 16; ++i) {
-            const int jj = i >> 1, comp = i & 1;
-            for (int tap = 0; tap < ntaps; ++tap) {
-                const int kk = 2 * jj * decim + comp + 2 * (ntaps - 1) - 2 * tap;      // the k at which this row meets taps[tap]
-                const int t = kk / kFiltK, g = (kk % kFiltK) / 16, j = kk % 16;
-                const size_t at = ((size_t) t * 64 + (size_t) (16 * g + i)) * 16 + (size_t) j;
-                const int d0 = ((taps[tap] + 128) & 255) - 128, d1 = (taps[tap] - d0) / 256;
-                pl[at] = (int8_t) d0;
-                pl[plane + at] = (int8_t) d1;
-            }
-        }
-        bytes += 2 * plane;
+        filter_build_planes(taps, ntaps, decim, p.steps, reinterpret_cast<int8_t *>(k.h_coef.get() + FirSet::kTapBytes));
+        bytes += (size_t) filter_mfma_plane_bytes(p.steps);
     }
     HIP_TRY(hipMemcpyAsync(k.d_coef.get(), k.h_coef.get(), bytes, hipMemcpyHostToDevice, s));
     return GPSIQ_OK;
@@ -81,17 +61,17 @@ int stage_coefficients(gpsiq_ctx *c, const int16_t *taps, int ntaps, int decim, 
 int queue_filter(gpsiq_ctx *c, const FilterPlan &p, int nsamp, int sample_size, const uint8_t *src, const uint8_t *head, int ntaps, int shift, int decim,
                  int phase, int out_sample_size, uint8_t *dst, hipStream_t s)
 {
-    FilterSet &k = c->filt;
+    FirSet &k = c->filt;
     if (p.kernel == kFiltMfma) {
         const FilterMfmaFn kernel = filter_mfma_kernel(out_sample_size);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no matrix filter kernel for %d-byte outputs", out_sample_size);
-        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const uint8_t *) (k.d_coef.get() + FilterSet::kTapBytes), ntaps,
-                           shift, decim, phase, dst, p.nout, p.run, p.runs, p.steps, k.d_count.get());
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const uint8_t *) (k.d_coef.get() + FirSet::kTapBytes), ntaps,
+                           shift, decim, phase, dst, p.nout, p.run, p.runs, p.steps, k.clip.d_count.get());
     } else {
         const FilterGenericFn kernel = filter_generic_kernel(sample_size, out_sample_size);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no filter kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
         hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, reinterpret_cast<const int32_t *>(k.d_coef.get()), ntaps, shift,
-                           decim, phase, dst, p.nout, p.run, p.runs, k.d_count.get());
+                           decim, phase, dst, p.nout, p.run, p.runs, k.clip.d_count.get());
     }
     HIP_TRY(hipGetLastError());
     return GPSIQ_OK;
@@ -107,16 +87,8 @@ int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *sr
     if (int rc = check_taps(taps, ntaps, shift, decim, sample_size, out_sample_size, &st)) return rc;
     if (phase < 0 || phase >= decim) return fail(GPSIQ_E_ARG, "phase %d outside [0, decim %d)", phase, decim);
     if (nsamp < 0) return fail(GPSIQ_E_ARG, "negative size");
-    const FilterPlan p = plan_filter(nsamp, sample_size, ntaps, decim, phase, st.max_tap, forced_kernel());
-    if (!src && nsamp) return fail(GPSIQ_E_ARG, "null source");
-    if (!dst && p.nout) return fail(GPSIQ_E_ARG, "null destination");
-    if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
-    if ((uintptr_t) head & 3) return fail(GPSIQ_E_ARG, "head %p not 4-byte aligned", head);
-    if ((uintptr_t) dst & 3) return fail(GPSIQ_E_ARG, "destination %p not 4-byte aligned", dst);
-    const size_t src_len = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, head_len = head ? (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size : 0;
-    const size_t dst_len = (size_t) 2 * (size_t) p.nout * (size_t) out_sample_size;
-    if (overlap(dst, dst_len, src, src_len)) return fail(GPSIQ_E_ARG, "source [%p, +%zu) and destination [%p, +%zu) overlap", src, src_len, dst, dst_len);
-    if (overlap(dst, dst_len, head, head_len)) return fail(GPSIQ_E_ARG, "head [%p, +%zu) and destination [%p, +%zu) overlap", head, head_len, dst, dst_len);
+    const FilterPlan p = plan_filter(nsamp, sample_size, ntaps, decim, phase, st.max_tap, forced_kernel("GPSIQ_FILTER_KERNEL", "mfma"));
+    if (int rc = check_span(src, nsamp, sample_size, head, ntaps, dst, (uint64_t) p.nout, out_sample_size)) return rc;
     if (nout) *nout = p.nout;
     if (clipped) *clipped = 0;
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -124,19 +96,13 @@ int gpsiq_filter_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *sr
     if (!p.launch) return GPSIQ_OK;                                   // no output: nothing to write
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    FilterSet &k = c->filt;
+    FirSet &k = c->filt;
     if (int rc = k.reserve()) return rc;
     if (int rc = stage_coefficients(c, taps, ntaps, decim, p, s)) return rc;
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
-    HIP_TRY(hipEventRecord(k.t0.get(), s));
-    if (int rc = queue_filter(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), ntaps, shift, decim, phase,
-                              out_sample_size, static_cast<uint8_t *>(dst), s)) return rc;
-    HIP_TRY(hipEventRecord(k.t1.get(), s));
-    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (clipped) *clipped = (uint64_t) k.h_count[0];
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
-    return GPSIQ_OK;
+    return counted_call(k.clip, s, [&] {
+        return queue_filter(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), ntaps, shift, decim, phase,
+                            out_sample_size, static_cast<uint8_t *>(dst), s);
+    }, clipped, kernel_ms);
 }
 
 // The pieces of gpsiq_stage_batch.h with the filter as the stage: a piece is rendered BEHIND a lead region of `hb` bytes whose last
@@ -150,8 +116,7 @@ int gpsiq_generate_batch_filtered_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, i
     if (!c || (!ch && nblocks) || (!dst && nblocks && nsamp)) return fail(GPSIQ_E_ARG, "null argument");
     TapStats st;
     if (int rc = check_taps(taps, ntaps, shift, decim, sample_size, out_sample_size, &st)) return rc;
-    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
-    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (int rc = check_batch_shape(nblocks, nchan, nsamp, fs)) return rc;
     if (nsamp % decim) return fail(GPSIQ_E_ARG, "nsamp %d is not a multiple of decim %d", nsamp, decim);
     const int nrow = nsamp / decim;                                   // outputs of a block
     const size_t blk_bytes = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, row_bytes = (size_t) 2 * (size_t) nrow * (size_t) out_sample_size;
@@ -161,18 +126,18 @@ int gpsiq_generate_batch_filtered_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, i
     const char *env = std::getenv("GPSIQ_FILTER_PIECE_BLOCKS");
     const int piece = filter_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
     const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
-    const int force = forced_kernel();
+    const int force = forced_kernel("GPSIQ_FILTER_KERNEL", "mfma");
     if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_filtered", ch, hb + blk_bytes * (size_t) piece + 4, row_bytes * (size_t) piece + 4)) return rc;     // (+4: never a request of no bytes)
-    FilterSet &k = c->filt;
+    FirSet &k = c->filt;
     if (int rc = k.reserve()) return rc;
-    const StageBatch stage = {"filtered batch", sample_size, hb, hist, piece, k.d_count.get(), k.h_count.get()};
+    const StageBatch stage = {"filtered batch", sample_size, hb, hist, piece, k.clip.d_count.get(), k.clip.h_count.get()};
     const FilterPlan whole = plan_filter(piece * nsamp, sample_size, ntaps, decim, 0, st.max_tap, force);
     note_plan(c, whole, (nblocks + piece - 1) / piece);
     const hipStream_t ss = c->ring.stage_stream.get();
     const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
         // one kernel for every piece (the choice does not look at the length), so one set of coefficients, queued once
         if (int rc = stage_coefficients(c, taps, ntaps, decim, whole, ss)) return rc;
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        HIP_TRY(hipMemsetAsync(k.clip.d_count.get(), 0, sizeof(unsigned long long), ss));
         if (hb) HIP_TRY(hipMemsetAsync(c->ring.d_render[0].get(), 0, hb, ss));       // the first block's history
         return GPSIQ_OK;
     }();

@@ -1,35 +1,35 @@
 // gpsiq_filter.h -- what the device context holds for gpsiq_filter / gpsiq_generate_batch_filtered (include/gpsiq_rows.h, "Filter") and
 // what their host side (gpsiq_filter.cpp) and their kernels (gpsiq_filter_kernels.hip, with gpsiq_filter_geometry.h) use of each
-// other.  The plan is in gpsiq_filter_plan.h.  Host code; gpsiq_ctx.h includes this header for the context's member `filt`.
+// other.  The plan is in gpsiq_filter_plan.h.  Host code; gpsiq_ctx.h includes this header for the context's members `filt`
+// and `cfilt` (gpsiq_cfilter.h has the complex filter's kernel types).
 #ifndef GPSIQ_FILTER_H
 #define GPSIQ_FILTER_H
 
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
+#include "gpsiq_stage_call.h"
 #include "gpsiq_filter_geometry.h"
 
 namespace gpsiq {
 
-// the coefficients of a call on the device and page-locked on their way there (the taps as dwords, then the matrix kernel's digit
-// planes: one size, the largest a call can ask for), the counter of clamped elements and its page-locked twin, and the two events a
-// kernel is timed with.  The batch call works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
-struct FilterSet {
+// What a FIR stage keeps in the context: gpsiq_filter's set (`filt`) and gpsiq_cfilter's (`cfilt`), one each.  The coefficients of
+// a call on the device and page-locked on their way there (the taps as dwords -- complex ones re below and im above -- then the
+// matrix kernels' digit planes: one size, the largest a call can ask for), and the counter of clamped elements with its timing events
+// (gpsiq_stage_call.h).  The batch call works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
+struct FirSet {
     static constexpr size_t kTapBytes = 4 * (size_t) kFiltMaxTaps;
     static constexpr size_t kCoefBytes = kTapBytes + (size_t) filter_mfma_plane_bytes(kFiltMaxSteps);
     DevBuf<uint8_t>               d_coef;    PinnedBuf<uint8_t>            h_coef;        // [kCoefBytes]
-    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    Event          t0, t1;
-    long           last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, outputs per run, pieces (gpsiq_filter_last_plan)
+    ClipCount      clip;
+    // the last call's plan: kernel, grid, outputs per run, then pieces (gpsiq_filter_last_plan) or k-steps (gpsiq_cfilter_last_plan)
+    long           last[4] = {-1, 0, 0, 0};
     int reserve();                                  // first use
 };
 
-inline int FilterSet::reserve()
+inline int FirSet::reserve()
 {
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
+    if (int rc = clip.reserve()) return rc;
     HIP_TRY(reserve_together(kCoefBytes, kCoefBytes, d_coef, h_coef));
-    HIP_TRY(d_count.reserve(1));
-    HIP_TRY(h_count.reserve(1));
     return GPSIQ_OK;
 }
 

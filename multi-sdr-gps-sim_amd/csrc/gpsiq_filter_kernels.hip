@@ -15,64 +15,16 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_filter_geometry.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
 
-typedef int filt_i32x4 __attribute__((ext_vector_type(4)));
-
-// sample m of the stream as one dword: I in the low half, Q in the high half, each sign-extended to 16 bits
-template <int FMT>
-__device__ __forceinline__ uint32_t load_pair(const uint8_t *base, int64_t m)
-{
-    if (FMT == GPSIQ_SC16) return *reinterpret_cast<const uint32_t *>(base + (uint64_t) m * 4);
-    const uint32_t v = *reinterpret_cast<const uint16_t *>(base + (uint64_t) m * 2);
-    return ((uint32_t) (int32_t) (int8_t) (v & 0xffu) & 0xffffu) | ((uint32_t) (int32_t) (int8_t) (v >> 8) << 16);
-}
-
-// x(m) of the contract: the span, the head before it, zeros before that and where there is no head
-template <int FMT>
-__device__ __forceinline__ uint32_t sample_at(const uint8_t *src, const uint8_t *head, int64_t m, int nsamp, int ntaps)
-{
-    if (m >= 0) return m < (int64_t) nsamp ? load_pair<FMT>(src, m) : 0u;
-    return head && m >= -(int64_t) (ntaps - 1) ? load_pair<FMT>(head, (int64_t) (ntaps - 1) + m) : 0u;
-}
-
-// y = floor((acc + 2^(shift-1)) / 2^shift), clamped to +-QMAX; clipped counts the elements the clamp changed
-template <int OUT>
-__device__ __forceinline__ int finish(int acc, int shift, unsigned &clipped)
-{
-    constexpr int QMAX = OUT == GPSIQ_SC08 ? 127 : 32767;
-    const int64_t half = shift ? (int64_t) 1 << (shift - 1) : 0;
-    const int64_t y = ((int64_t) acc + half) >> shift;
-    const int64_t c = y < -QMAX ? -QMAX : y > QMAX ? QMAX : y;
-    clipped += c != y;
-    return (int) c;
-}
-
-template <int OUT>
-__device__ __forceinline__ void store_sample(uint8_t *dst, uint64_t j, int i, int q)
-{
-    if (OUT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(dst + j * 4) = ((uint32_t) i & 0xffffu) | ((uint32_t) q << 16);
-    else *reinterpret_cast<uint16_t *>(dst + j * 2) = (uint16_t) (((uint32_t) i & 0xffu) | (((uint32_t) q & 0xffu) << 8));
-}
-
-// per wave, then per workgroup; one atomic of the workgroup if it clamped anything.  Integer addition: the order of arrival does not
-// matter.  Every thread of the workgroup arrives here.  (The four partial counts are the kernels' only static LDS: 32 bytes, so the
-// dynamic region behind them, which filter_mfma reads 16 bytes at a time, stays 16-byte aligned.)
-__device__ __forceinline__ void count_clipped(unsigned long long clipped, unsigned long long *count)
-{
-    for (int off = 32; off >= 1; off >>= 1) clipped += __shfl_xor(clipped, off, 64);
-    __shared__ unsigned long long part[kFiltThreads / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-#pragma unroll
-        for (int k = 0; k < kFiltThreads / 64; ++k) sum += part[k];
-        if (sum) atomicAdd(count, sum);
-    }
-}
+using stream::i32x4;
+using stream::sample_at;
+using stream::finish;
+using stream::store_sample;
+using stream::count_clipped;
 
 // Arguments: span and its samples, head (may be null), device taps as dwords, ntaps, shift, decim, phase, destination, outputs of the
 // span, outputs of a run, runs of the launch (gpsiq_filter_plan.h), the counter (zeroed by the host).
@@ -109,7 +61,7 @@ __global__ __launch_bounds__(kFiltThreads) void filter_generic(const uint8_t *__
             store_sample<OUT>(dst, (uint64_t) (j0 + o), finish<OUT>(ai, shift, clipped), finish<OUT>(aq, shift, clipped));
         }
     }
-    count_clipped(clipped, count);
+    count_clipped<kFiltThreads>(clipped, count);
 }
 
 // Arguments as filter_generic's, with the digit planes in the taps' place and the k-steps of a tile behind the run.
@@ -134,7 +86,7 @@ __global__ __launch_bounds__(kFiltThreads) void filter_mfma(const uint8_t *__res
     uint8_t *win = filt_lds + plane_bytes;
     const int wsamp = filter_mfma_window_bytes(run, decim, steps) / 2;                               // samples staged per run
     for (int i = tid; i < plane_bytes / 16; i += kFiltThreads)
-        reinterpret_cast<filt_i32x4 *>(filt_lds)[i] = reinterpret_cast<const filt_i32x4 *>(planes)[i];
+        reinterpret_cast<i32x4 *>(filt_lds)[i] = reinterpret_cast<const i32x4 *>(planes)[i];
     const int col = lane & 15, q = lane >> 4;
     unsigned clipped = 0;
     for (uint64_t r = blockIdx.x; r < runs; r += gridDim.x) {
@@ -153,11 +105,11 @@ __global__ __launch_bounds__(kFiltThreads) void filter_mfma(const uint8_t *__res
         for (int tile = wave; tile * kFiltTileOutputs < n; tile += kFiltThreads / 64) {
             const uint8_t *b_ptr = win + 2 * decim * (kFiltTileOutputs * tile + kFiltColOutputs * col) + 16 * q;
             const uint8_t *a_ptr = filt_lds + lane * 16;
-            filt_i32x4 d0 = {0, 0, 0, 0}, d1 = {0, 0, 0, 0};
+            i32x4 d0 = {0, 0, 0, 0}, d1 = {0, 0, 0, 0};
             for (int t = 0; t < steps; ++t) {
-                const filt_i32x4 b = *reinterpret_cast<const filt_i32x4 *>(b_ptr + t * kFiltK);
-                const filt_i32x4 a0 = *reinterpret_cast<const filt_i32x4 *>(a_ptr + t * (kFiltK * 16));
-                const filt_i32x4 a1 = *reinterpret_cast<const filt_i32x4 *>(a_ptr + (steps + t) * (kFiltK * 16));
+                const i32x4 b = *reinterpret_cast<const i32x4 *>(b_ptr + t * kFiltK);
+                const i32x4 a0 = *reinterpret_cast<const i32x4 *>(a_ptr + t * (kFiltK * 16));
+                const i32x4 a1 = *reinterpret_cast<const i32x4 *>(a_ptr + (steps + t) * (kFiltK * 16));
                 d0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b, d0, 0, 0, 0);
                 d1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b, d1, 0, 0, 0);
             }
@@ -171,7 +123,7 @@ __global__ __launch_bounds__(kFiltThreads) void filter_mfma(const uint8_t *__res
             }
         }
     }
-    count_clipped(clipped, count);
+    count_clipped<kFiltThreads>(clipped, count);
 }
 
 }  // namespace

@@ -1,13 +1,15 @@
 // gpsiq_filter_plan.h -- the output count, the kernel and the grid a gpsiq_filter call (include/gpsiq_rows.h, "Filter") takes.  Host
 // code only, and pure: no HIP, no environment (the GPSIQ_FILTER_KERNEL override is an argument, read per call by the caller; so is
 // GPSIQ_FILTER_PIECE_BLOCKS, for the piece size of gpsiq_generate_batch_filtered: stage_piece_blocks, gpsiq_pieces.h).
-// tests/filter_plan.cpp pins every plan on the CPU.
+// The matrix kernel's operand as the host builds it is here too (filter_build_planes).  tests/filter_plan.cpp pins every plan on the
+// CPU and multiplies the planes out against the direct sum.
 // Not a device source: the geometry the kernels are compiled for is gpsiq_filter_geometry.h.
 #ifndef GPSIQ_FILTER_PLAN_H
 #define GPSIQ_FILTER_PLAN_H
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "gpsiq_filter_geometry.h"
 #include "gpsiq_pieces.h"
@@ -66,6 +68,26 @@ inline FilterPlan plan_filter(int nsamp, int in_size, int ntaps, int decim, int 
     p.runs = ((uint64_t) p.nout + (uint64_t) p.run - 1) / (uint64_t) p.run;
     p.grid = p.runs < kFiltMaxGrid ? (unsigned) p.runs : kFiltMaxGrid;
     return p;
+}
+
+// The two digit planes of the matrix kernel in fragment order (gpsiq_filter_geometry.h): lane l = (row i = l & 15, group g = l >> 4) of
+// k-step t holds bytes j = 0..15, k = 64 t + 16 g + j, of A(i, k) = T[2 jj decim + c + 2 (ntaps - 1) - k], i = 2 jj + c, T the taps
+// zero-stuffed.  planes: [2][steps * 1024] bytes.  cfilter_build_planes (gpsiq_cfilter_plan.h) is its complex counterpart
+inline void filter_build_planes(const int16_t *taps, int ntaps, int decim, int steps, int8_t *planes)
+{
+    const size_t plane = (size_t) steps * kFiltK * 16;
+    std::memset(planes, 0, 2 * plane);
+    for (int i = 0; i < 16; ++i) {
+        const int jj = i >> 1, comp = i & 1;
+        for (int tap = 0; tap < ntaps; ++tap) {
+            const int kk = 2 * jj * decim + comp + 2 * (ntaps - 1) - 2 * tap;      // the k at which this row meets taps[tap]
+            const int t = kk / kFiltK, g = (kk % kFiltK) / 16, j = kk % 16;
+            const size_t at = ((size_t) t * 64 + (size_t) (16 * g + i)) * 16 + (size_t) j;
+            const int d0 = ((taps[tap] + 128) & 255) - 128, d1 = (taps[tap] - d0) / 256;
+            planes[at] = (int8_t) d0;
+            planes[plane + at] = (int8_t) d1;
+        }
+    }
 }
 
 // Blocks per piece of gpsiq_generate_batch_filtered: the one policy, stage_piece_blocks (gpsiq_pieces.h), under the call's name.  A

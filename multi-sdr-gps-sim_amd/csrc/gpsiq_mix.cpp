@@ -15,12 +15,7 @@ using namespace gpsiq;
 
 namespace {
 
-int forced_kernel()
-{
-    const char *env = std::getenv("GPSIQ_MIX_KERNEL");
-    if (!env) return kMixAuto;
-    return !std::strcmp(env, "generic") ? kMixForceGeneric : !std::strcmp(env, "rows") ? kMixForceRows : kMixAuto;
-}
+static_assert(kMixAuto == 0 && kMixForceGeneric == 1 && kMixForceRows == 2, "forced_kernel's values (gpsiq_stage_call.h)");
 
 // what both calls ask of the sum's end
 int check_output(int shift, int qmax, int out_sample_size)
@@ -77,11 +72,11 @@ int queue_mix(gpsiq_ctx *c, const MixPlan &p, const MixDevTerms &terms, uint64_t
         const MixRowsFn kernel = mix_rows_kernel(out_sample_size);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no row mix kernel for %d-byte outputs", out_sample_size);
         hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, terms, m0, nsamp, shift, qmax, dst, p.lead, p.units, (const uint32_t *) k.d_table.get(),
-                           k.d_count.get());
+                           k.clip.d_count.get());
     } else {
         const MixGenericFn kernel = mix_generic_kernel(out_sample_size);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no mix kernel for %d-byte outputs", out_sample_size);
-        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, terms, m0, nsamp, shift, qmax, dst, (const uint32_t *) k.d_table.get(), k.d_count.get());
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, terms, m0, nsamp, shift, qmax, dst, (const uint32_t *) k.d_table.get(), k.clip.d_count.get());
     }
     HIP_TRY(hipGetLastError());
     return GPSIQ_OK;
@@ -115,7 +110,7 @@ int gpsiq_mix_impl(gpsiq_ctx_t *c, int nsamp, uint64_t m0, const gpsiq_mix_term_
         if (overlap(dst, dst_len, t.src, len))
             return fail(GPSIQ_E_ARG, "term %d: source [%p, +%zu) and destination [%p, +%zu) overlap and are not the in-place case", k, t.src, len, dst, dst_len);
     }
-    const MixPlan p = plan_mix(nsamp, m0, out_sample_size, (uint64_t) (uintptr_t) dst, forced_kernel());
+    const MixPlan p = plan_mix(nsamp, m0, out_sample_size, (uint64_t) (uintptr_t) dst, forced_kernel("GPSIQ_MIX_KERNEL", "rows"));
     if (clipped) *clipped = 0;
     if (kernel_ms) *kernel_ms = 0.0f;
     MixPlan none;
@@ -126,15 +121,9 @@ int gpsiq_mix_impl(gpsiq_ctx_t *c, int nsamp, uint64_t m0, const gpsiq_mix_term_
     MixSet &k = c->mix;
     if (int rc = k.reserve()) return rc;
     if (int rc = stage_table(k, s)) return rc;
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
-    HIP_TRY(hipEventRecord(k.t0.get(), s));
-    if (int rc = queue_mix(c, p, dev, m0, nsamp, shift, qmax, out_sample_size, static_cast<uint8_t *>(dst), s)) return rc;
-    HIP_TRY(hipEventRecord(k.t1.get(), s));
-    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = counted_call(k.clip, s, [&] { return queue_mix(c, p, dev, m0, nsamp, shift, qmax, out_sample_size, static_cast<uint8_t *>(dst), s); },
+                              clipped, kernel_ms)) return rc;
     k.have_table = true;
-    if (clipped) *clipped = (uint64_t) k.h_count[0];
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
     note_plan(c, p, 0);
     return GPSIQ_OK;
 }
@@ -147,11 +136,10 @@ int gpsiq_generate_batch_mixed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int 
                                     uint64_t *clipped, double *carr_phase_out)
 {
     if (!c || (!ch && nblocks) || (!dst && nblocks && nsamp)) return fail(GPSIQ_E_ARG, "null argument");
-    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
+    if (int rc = check_formats(sample_size, sample_size)) return rc;       // (in place: one format)
     if (int rc = check_output(shift, qmax, sample_size)) return rc;
     if (ntones < 0 || ntones > kMixMaxTerms - 1 || (ntones && !tones)) return fail(GPSIQ_E_ARG, "ntones %d outside 0..%d, or null tones", ntones, kMixMaxTerms - 1);
-    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
-    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (int rc = check_batch_shape(nblocks, nchan, nsamp, fs)) return rc;
     MixDevTerms dev = {};
     dev.n = 1 + ntones;
     dev.t[0].gain = base_gain; dev.t[0].kind = GPSIQ_MIX_STREAM; dev.t[0].fmt = sample_size;
@@ -166,16 +154,16 @@ int gpsiq_generate_batch_mixed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int 
     const char *env = std::getenv("GPSIQ_MIX_PIECE_BLOCKS");
     const int piece = mix_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
     const int npieces = (nblocks + piece - 1) / piece;
-    const int force = forced_kernel();
+    const int force = forced_kernel("GPSIQ_MIX_KERNEL", "rows");
     if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_mixed", ch, blk_bytes * (size_t) piece + 16, 0)) return rc;       // (+16: never a request of no bytes)
     MixSet &k = c->mix;
     if (int rc = k.reserve()) return rc;
-    const StageBatch stage = {"mixed batch", sample_size, 0, 0, piece, k.d_count.get(), k.h_count.get()};
+    const StageBatch stage = {"mixed batch", sample_size, 0, 0, piece, k.clip.d_count.get(), k.clip.h_count.get()};
     note_plan(c, MixPlan(), npieces);
     const hipStream_t ss = c->ring.stage_stream.get();
     const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
         if (int rc = stage_table(k, ss)) return rc;
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        HIP_TRY(hipMemsetAsync(k.clip.d_count.get(), 0, sizeof(unsigned long long), ss));
         return GPSIQ_OK;
     }();
     double carr[GPSIQ_MAX_CHAN] = {};

@@ -6,29 +6,26 @@
 
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
+#include "gpsiq_stage_call.h"
 #include "gpsiq_mix_geometry.h"
 
 namespace gpsiq {
 
 // the carrier table as the kernels read it (512 dwords: cos below, sin above) on the device (have: it has arrived) and page-locked on
-// its way there, the counter of clamped elements and its page-locked twin, and the two events a kernel is timed with.  The batch call
-// works through its pieces with the context's staging ring (gpsiq_stage_batch.h), in place in the rendered pair
+// its way there, and the counter of clamped elements with its timing events (gpsiq_stage_call.h).  The batch call works through its
+// pieces with the context's staging ring (gpsiq_stage_batch.h), in place in the rendered pair
 struct MixSet {
     DevBuf<uint32_t>              d_table;   PinnedBuf<uint32_t>           h_table;       // [512]
     bool                          have_table = false;
-    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    Event          t0, t1;
+    ClipCount      clip;
     long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, units, pieces (gpsiq_mix_last_plan)
     int reserve();                                  // first use
 };
 
 inline int MixSet::reserve()
 {
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
+    if (int rc = clip.reserve()) return rc;
     HIP_TRY(reserve_together(512, 512, d_table, h_table));
-    HIP_TRY(d_count.reserve(1));
-    HIP_TRY(h_count.reserve(1));
     return GPSIQ_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_mix_geometry.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
@@ -95,28 +96,8 @@ __device__ __forceinline__ int finish(long long acc, int shift, int qmax, unsign
     return (int) c;
 }
 
-template <int OUT>
-__device__ __forceinline__ void store_sample(uint8_t *dst, uint64_t j, int i, int q)
-{
-    if (OUT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(dst + j * 4) = ((uint32_t) i & 0xffffu) | ((uint32_t) q << 16);
-    else *reinterpret_cast<uint16_t *>(dst + j * 2) = (uint16_t) (((uint32_t) i & 0xffu) | (((uint32_t) q & 0xffu) << 8));
-}
-
-// per wave, then per workgroup; one atomic of the workgroup if it clamped anything.  Integer addition: the order of arrival does not
-// matter.  Every thread of the workgroup arrives here.
-__device__ __forceinline__ void count_clipped(unsigned long long clipped, unsigned long long *count)
-{
-    for (int off = 32; off >= 1; off >>= 1) clipped += __shfl_xor(clipped, off, 64);
-    __shared__ unsigned long long part[kMixThreads / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-#pragma unroll
-        for (int k = 0; k < kMixThreads / 64; ++k) sum += part[k];
-        if (sum) atomicAdd(count, sum);
-    }
-}
+using stream::store_sample;
+using stream::count_clipped;
 
 // Arguments: the terms, m0, the samples, shift, qmax, the destination, the table as 512 dwords (cos in the low half, sin in the high
 // half), the counter (zeroed by the host).  Thread t of the launch takes samples t, t + gridDim.x * kMixThreads, ...
@@ -144,7 +125,7 @@ __global__ __launch_bounds__(kMixThreads) void mix_generic(const MixDevTerms ter
         }
         store_sample<OUT>(dst, n, finish(ai, shift, qmax, clipped), finish(aq, shift, qmax, clipped));
     }
-    count_clipped(clipped, count);
+    count_clipped<kMixThreads>(clipped, count);
 }
 
 // S whole samples of a source at p: dword loads where p is 4-byte aligned (always for int16; for int8 unless the delay is odd), as
@@ -270,7 +251,7 @@ __global__ __launch_bounds__(kMixThreads) void mix_rows(const MixDevTerms terms,
                 if (i >= lo && i < hi) store_sample<OUT>(dst, (uint64_t) (n0 + i), oi[i], oq[i]);
         }
     }
-    count_clipped(clipped, count);
+    count_clipped<kMixThreads>(clipped, count);
 }
 
 }  // namespace

@@ -46,7 +46,7 @@ static int queue_pack(gpsiq_ctx *c, const PackPlan &p, int nsamp, int sample_siz
 {
     const PackFn kernel = pack_kernel(sample_size, bits);
     if (!kernel) return fail(GPSIQ_E_DEVICE, "no pack kernel for %d-byte samples, %d bits", sample_size, bits);
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, src, src_stride, dst, dst_stride, nsamp, p.units, p.tiles, p.total, c->pack.d_count.get());
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, src, src_stride, dst, dst_stride, nsamp, p.units, p.tiles, p.total, c->pack.clip.d_count.get());
     HIP_TRY(hipGetLastError());
     return GPSIQ_OK;
 }
@@ -65,15 +65,9 @@ int gpsiq_pack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int sample_size, con
     hipStream_t s = (hipStream_t) hip_stream;
     PackSet &k = c->pack;
     if (int rc = k.reserve()) return rc;
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
-    HIP_TRY(hipEventRecord(k.t0.get(), s));
-    if (int rc = queue_pack(c, p, nsamp, sample_size, bits, static_cast<const uint8_t *>(src), src_stride, static_cast<uint8_t *>(dst), dst_stride, s)) return rc;
-    HIP_TRY(hipEventRecord(k.t1.get(), s));
-    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (clipped) *clipped = (uint64_t) k.h_count[0];
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
-    return GPSIQ_OK;
+    return counted_call(k.clip, s, [&] {
+        return queue_pack(c, p, nsamp, sample_size, bits, static_cast<const uint8_t *>(src), src_stride, static_cast<uint8_t *>(dst), dst_stride, s);
+    }, clipped, kernel_ms);
 }
 
 int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const void *src, size_t src_stride, int sample_size, void *dst, size_t dst_stride,
@@ -87,7 +81,7 @@ int gpsiq_unpack_impl(gpsiq_ctx_t *c, int nblocks, int nsamp, int bits, const vo
     if (!p.launch) return GPSIQ_OK;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    PackSet &k = c->pack;
+    ClipCount &k = c->pack.clip;                                      // (the two events of it: unpacking clamps nothing)
     if (int rc = k.reserve()) return rc;
     const UnpackFn kernel = unpack_kernel(bits, sample_size);
     if (!kernel) return fail(GPSIQ_E_DEVICE, "no unpack kernel for %d bits, %d-byte samples", bits, sample_size);
@@ -111,8 +105,7 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
 {
     if (!c || (!ch && nblocks) || (!dst && nblocks && nsamp)) return fail(GPSIQ_E_ARG, "null argument");
     if (bits != 4 && bits != 2) return fail(GPSIQ_E_ARG, "bad bits %d: 4 or 2", bits);
-    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
-    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (int rc = check_batch_shape(nblocks, nchan, nsamp, fs)) return rc;
     const size_t plen = packed_block_bytes(nsamp, bits), blk_bytes = block_bytes(nsamp, GPSIQ_SC08);
     if (dst_block_stride < plen) return fail(GPSIQ_E_ARG, "block stride %zu too small", dst_block_stride);
     const int qmax = bits == 4 ? 7 : 1;
@@ -126,10 +119,10 @@ int gpsiq_generate_batch_packed_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, int
     if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_packed", ch, raw + blk_bytes * (size_t) piece + 4, pstride * (size_t) piece + 4)) return rc;      // (+4: never a request of no bytes)
     PackSet &k = c->pack;
     if (int rc = k.reserve()) return rc;
-    const StageBatch st = {"packed batch", GPSIQ_SC08, raw, 0, piece, k.d_count.get(), k.h_count.get()};
+    const StageBatch st = {"packed batch", GPSIQ_SC08, raw, 0, piece, k.clip.d_count.get(), k.clip.h_count.get()};
     note_plan(c, plan_pack(piece, nsamp, GPSIQ_SC08, bits), (nblocks + piece - 1) / piece);
     const hipStream_t ss = c->ring.stage_stream.get();
-    const int rc0 = [&]() -> int { HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss)); return GPSIQ_OK; }();
+    const int rc0 = [&]() -> int { HIP_TRY(hipMemsetAsync(k.clip.d_count.get(), 0, sizeof(unsigned long long), ss)); return GPSIQ_OK; }();
     double carr[GPSIQ_MAX_CHAN] = {};
     uint64_t clamped = 0;
     const int rc = gpsiq_stage_batch_run(c, st, rc0, ch, nblocks, nchan, nsamp, fs, [&](const Piece &pc, PieceCopy *cp) -> int {

@@ -6,26 +6,17 @@
 
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
+#include "gpsiq_stage_call.h"
 
 namespace gpsiq {
 
-// the counter of clamped elements on the device and page-locked on its way back, and the two events a kernel is timed with.  The
-// batch call works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
+// the counter of clamped elements with its timing events (gpsiq_stage_call.h; gpsiq_unpack uses the events alone).  The batch call
+// works through its pieces with the context's staging ring (gpsiq_stage_batch.h)
 struct PackSet {
-    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    Event          t0, t1;
+    ClipCount      clip;
     long           last[4] = {-1, 0, 0, 0};         // the last call's plan: grid, units per block, tiles per block, pieces (gpsiq_pack_last_plan)
-    int reserve();                                  // first use
+    int reserve() { return clip.reserve(); }        // first use
 };
-
-inline int PackSet::reserve()
-{
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
-    HIP_TRY(d_count.reserve(1));
-    HIP_TRY(h_count.reserve(1));
-    return GPSIQ_OK;
-}
 
 // the pack / unpack kernels (gpsiq_pack_kernels.hip).  Arguments: source and its block stride, destination and its block stride,
 // samples per block, units per block, tiles per block, tiles of the launch (gpsiq_pack_plan.h); pack: the counter of clamped elements

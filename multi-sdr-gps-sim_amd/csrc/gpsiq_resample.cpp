@@ -17,8 +17,7 @@ namespace {
 // what both calls ask of the table, the step and the formats
 int check_table(const int16_t *taps, int log2_phases, int ntaps, int shift, int interp, uint64_t step, uint64_t pos0, int sample_size, int out_sample_size)
 {
-    if (sample_size != GPSIQ_SC08 && sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad sample size %d", sample_size);
-    if (out_sample_size != GPSIQ_SC08 && out_sample_size != GPSIQ_SC16) return fail(GPSIQ_E_ARG, "bad output sample size %d", out_sample_size);
+    if (int rc = check_formats(sample_size, out_sample_size)) return rc;
     if (log2_phases < 0 || log2_phases > kRsMaxLog2Phases) return fail(GPSIQ_E_ARG, "log2_phases %d outside 0..%d", log2_phases, kRsMaxLog2Phases);
     if (ntaps < 1 || ntaps > kRsMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kRsMaxTaps);
     const int rows = (1 << log2_phases) + 1;
@@ -36,12 +35,7 @@ int check_table(const int16_t *taps, int log2_phases, int ntaps, int shift, int 
     return GPSIQ_OK;
 }
 
-int forced_kernel()
-{
-    const char *env = std::getenv("GPSIQ_RESAMPLE_KERNEL");
-    if (!env) return kRsAuto;
-    return !std::strcmp(env, "generic") ? kRsForceGeneric : !std::strcmp(env, "rows") ? kRsForceRows : kRsAuto;
-}
+static_assert(kRsAuto == 0 && kRsForceGeneric == 1 && kRsForceRows == 2, "forced_kernel's values (gpsiq_stage_call.h)");
 
 void note_plan(gpsiq_ctx *c, const ResamplePlan &p, long long pieces)
 {
@@ -68,12 +62,12 @@ int queue_resample(gpsiq_ctx *c, const ResamplePlan &p, int nsamp, int sample_si
         const ResampleRowsFn kernel = resample_rows_kernel(sample_size, out_sample_size, p.pad);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no row resampler kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
         hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const int16_t *) k.d_taps.get(), log2_phases, ntaps, shift, interp,
-                           step, pos0, dst, p.nout, p.run, p.runs, k.d_count.get());
+                           step, pos0, dst, p.nout, p.run, p.runs, k.clip.d_count.get());
     } else {
         const ResampleGenericFn kernel = resample_generic_kernel(sample_size, out_sample_size);
         if (!kernel) return fail(GPSIQ_E_DEVICE, "no resampler kernel for %d-byte samples to %d-byte outputs", sample_size, out_sample_size);
         hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds, s, src, nsamp, head, (const int16_t *) k.d_taps.get(), log2_phases, ntaps, shift, interp,
-                           step, pos0, dst, p.nout, p.runs, k.d_count.get());
+                           step, pos0, dst, p.nout, p.runs, k.clip.d_count.get());
     }
     HIP_TRY(hipGetLastError());
     return GPSIQ_OK;
@@ -88,16 +82,8 @@ int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *
     if (!c) return fail(GPSIQ_E_ARG, "null context");
     if (int rc = check_table(taps, log2_phases, ntaps, shift, interp, step, pos0, sample_size, out_sample_size)) return rc;
     if (nsamp < 0) return fail(GPSIQ_E_ARG, "negative size");
-    const ResamplePlan p = plan_resample((uint64_t) nsamp, log2_phases, ntaps, step, pos0, forced_kernel());
-    if (!src && nsamp) return fail(GPSIQ_E_ARG, "null source");
-    if (!dst && p.nout) return fail(GPSIQ_E_ARG, "null destination");
-    if ((uintptr_t) src & 3) return fail(GPSIQ_E_ARG, "source %p not 4-byte aligned", src);
-    if ((uintptr_t) head & 3) return fail(GPSIQ_E_ARG, "head %p not 4-byte aligned", head);
-    if ((uintptr_t) dst & 3) return fail(GPSIQ_E_ARG, "destination %p not 4-byte aligned", dst);
-    const size_t src_len = (size_t) 2 * (size_t) nsamp * (size_t) sample_size, head_len = head ? (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size : 0;
-    const size_t dst_len = (size_t) 2 * (size_t) p.nout * (size_t) out_sample_size;
-    if (overlap(dst, dst_len, src, src_len)) return fail(GPSIQ_E_ARG, "source [%p, +%zu) and destination [%p, +%zu) overlap", src, src_len, dst, dst_len);
-    if (overlap(dst, dst_len, head, head_len)) return fail(GPSIQ_E_ARG, "head [%p, +%zu) and destination [%p, +%zu) overlap", head, head_len, dst, dst_len);
+    const ResamplePlan p = plan_resample((uint64_t) nsamp, log2_phases, ntaps, step, pos0, forced_kernel("GPSIQ_RESAMPLE_KERNEL", "rows"));
+    if (int rc = check_span(src, nsamp, sample_size, head, ntaps, dst, p.nout, out_sample_size)) return rc;
     if (nout) *nout = p.nout;
     if (next_pos) *next_pos = p.next_pos;
     if (clipped) *clipped = 0;
@@ -109,16 +95,10 @@ int gpsiq_resample_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *
     ResampleSet &k = c->rs;
     if (int rc = k.reserve()) return rc;
     if (int rc = stage_table(c, taps, log2_phases, ntaps, s)) return rc;
-    HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), s));       // the workgroups add into it: zeroed per call
-    HIP_TRY(hipEventRecord(k.t0.get(), s));
-    if (int rc = queue_resample(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), log2_phases, ntaps, shift,
-                                interp, step, pos0, out_sample_size, static_cast<uint8_t *>(dst), s)) return rc;
-    HIP_TRY(hipEventRecord(k.t1.get(), s));
-    HIP_TRY(hipMemcpyAsync(k.h_count.get(), k.d_count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (clipped) *clipped = (uint64_t) k.h_count[0];
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, k.t0.get(), k.t1.get()));
-    return GPSIQ_OK;
+    return counted_call(k.clip, s, [&] {
+        return queue_resample(c, p, nsamp, sample_size, static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(head), log2_phases, ntaps, shift,
+                              interp, step, pos0, out_sample_size, static_cast<uint8_t *>(dst), s);
+    }, clipped, kernel_ms);
 }
 
 // The pieces of gpsiq_stage_batch.h with the resampler as the stage: lead region and history as the filtered call's
@@ -131,8 +111,7 @@ int gpsiq_generate_batch_resampled_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, 
 {
     if (!c || (!ch && nblocks)) return fail(GPSIQ_E_ARG, "null argument");
     if (int rc = check_table(taps, log2_phases, ntaps, shift, interp, step, pos0, sample_size, out_sample_size)) return rc;
-    if (nblocks < 0 || nchan < 1 || nchan > GPSIQ_MAX_CHAN) return fail(GPSIQ_E_ARG, "bad nblocks %d / nchan %d", nblocks, nchan);
-    if (nsamp < 0 || !(fs > 0.0)) return fail(GPSIQ_E_ARG, "bad nsamp %d / fs %g", nsamp, fs);
+    if (int rc = check_batch_shape(nblocks, nchan, nsamp, fs)) return rc;
     uint64_t total = 0, end_pos = 0;
     resample_span((uint64_t) nblocks * (uint64_t) nsamp, pos0, step, &total, &end_pos);
     if (dst_capacity < total) return fail(GPSIQ_E_ARG, "room for %llu samples, the call writes %llu", (unsigned long long) dst_capacity, (unsigned long long) total);
@@ -144,17 +123,17 @@ int gpsiq_generate_batch_resampled_impl(gpsiq_ctx_t *c, const gpsiq_chan_t *ch, 
     const char *env = std::getenv("GPSIQ_RESAMPLE_PIECE_BLOCKS");
     const int piece = resample_piece_blocks(nblocks, nsamp, blk_bytes, env ? std::atol(env) : 0);
     const size_t hist = (size_t) 2 * (size_t) (ntaps - 1) * (size_t) sample_size, hb = (hist + 15) & ~(size_t) 15;
-    const int force = forced_kernel();
+    const int force = forced_kernel("GPSIQ_RESAMPLE_KERNEL", "rows");
     const size_t piece_out = (size_t) resample_piece_outputs((uint64_t) piece * (uint64_t) nsamp, step) * out_sample_bytes;
     if (int rc = gpsiq_stage_batch_begin(c, "gpsiq_generate_batch_resampled", ch, hb + blk_bytes * (size_t) piece + 4, piece_out + 4)) return rc;     // (+4: never a request of no bytes)
     ResampleSet &k = c->rs;
     if (int rc = k.reserve()) return rc;
-    const StageBatch stage = {"resampled batch", sample_size, hb, hist, piece, k.d_count.get(), k.h_count.get()};
+    const StageBatch stage = {"resampled batch", sample_size, hb, hist, piece, k.clip.d_count.get(), k.clip.h_count.get()};
     note_plan(c, plan_resample((uint64_t) piece * (uint64_t) nsamp, log2_phases, ntaps, step, pos0, force), (nblocks + piece - 1) / piece);
     const hipStream_t ss = c->ring.stage_stream.get();
     const int rc0 = !nsamp ? GPSIQ_OK : [&]() -> int {
         if (int rc = stage_table(c, taps, log2_phases, ntaps, ss)) return rc;
-        HIP_TRY(hipMemsetAsync(k.d_count.get(), 0, sizeof(unsigned long long), ss));
+        HIP_TRY(hipMemsetAsync(k.clip.d_count.get(), 0, sizeof(unsigned long long), ss));
         if (hb) HIP_TRY(hipMemsetAsync(c->ring.d_render[0].get(), 0, hb, ss));       // the first block's history
         return GPSIQ_OK;
     }();

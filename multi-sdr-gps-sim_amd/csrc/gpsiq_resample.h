@@ -7,29 +7,26 @@
 
 #include "gpsiq_internal.h"
 #include "gpsiq_own.h"
+#include "gpsiq_stage_call.h"
 #include "gpsiq_resample_geometry.h"
 
 namespace gpsiq {
 
-// the tap table of a call on the device and page-locked on its way there (one size, the largest a call can ask for), the counter of
-// clamped elements and its page-locked twin, and the two events a kernel is timed with.  The batch call works through its pieces
-// with the context's staging ring (gpsiq_stage_batch.h)
+// the tap table of a call on the device and page-locked on its way there (one size, the largest a call can ask for), and the counter
+// of clamped elements with its timing events (gpsiq_stage_call.h).  The batch call works through its pieces with the context's
+// staging ring (gpsiq_stage_batch.h)
 struct ResampleSet {
     static constexpr size_t kTableEntries = (size_t) kRsMaxTable;
     DevBuf<int16_t>               d_taps;    PinnedBuf<int16_t>            h_taps;        // [kTableEntries]
-    DevBuf<unsigned long long>    d_count;   PinnedBuf<unsigned long long> h_count;       // [1]
-    Event          t0, t1;
+    ClipCount      clip;
     long long      last[4] = {-1, 0, 0, 0};         // the last call's plan: kernel, grid, outputs per unit, pieces (gpsiq_resample_last_plan)
     int reserve();                                  // first use
 };
 
 inline int ResampleSet::reserve()
 {
-    HIP_TRY(t0.ensure(hipEventDefault));
-    HIP_TRY(t1.ensure(hipEventDefault));
+    if (int rc = clip.reserve()) return rc;
     HIP_TRY(reserve_together(kTableEntries, kTableEntries, d_taps, h_taps));
-    HIP_TRY(d_count.reserve(1));
-    HIP_TRY(h_count.reserve(1));
     return GPSIQ_OK;
 }
 

@@ -9,7 +9,8 @@
 // One accumulator width, no saturation inside a sum: every row has sum |taps| <= 65535 (checked on the host, GPSIQ_E_RANGE) and
 // |x| <= 32768, so |a0|, |a1| <= 65535 * 32768 < 2^31.  With interp both rows are accumulated and combined in 64 bits,
 // (256 - mu) a0 + mu a1 + 2^(shift + 7) >> shift + 8; without, a0 is rounded by shift as the filter rounds.  Symmetric clamp, one flag
-// per element the clamp changed.
+// per element the clamp changed.  x(m), the store of a sample and the count are gpsiq_stream.h's (sample_at, store_sample,
+// count_clipped); the rounding is this stage's own arithmetic and stays here (rs_finish).
 // Every offset into src / dst is 64 bits wide, and so is j: a span of 2^31 - 1 samples at step 2^29 has 2^34 outputs.  p_j itself
 // stays below nsamp * 2^32 < 2^63 for every output that exists.  Sample m of the span is read only for 0 <= m < nsamp, sample m < 0
 // from head (or as zero); outputs j < nout are written and nothing else.  No workgroup waits for another; a workgroup strides over
@@ -18,26 +19,14 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_resample_geometry.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
 
-// sample m of the stream as one dword: I in the low half, Q in the high half, each sign-extended to 16 bits
-template <int FMT>
-__device__ __forceinline__ uint32_t rs_load_pair(const uint8_t *base, int64_t m)
-{
-    if (FMT == GPSIQ_SC16) return *reinterpret_cast<const uint32_t *>(base + (uint64_t) m * 4);
-    const uint32_t v = *reinterpret_cast<const uint16_t *>(base + (uint64_t) m * 2);
-    return ((uint32_t) (int32_t) (int8_t) (v & 0xffu) & 0xffffu) | ((uint32_t) (int32_t) (int8_t) (v >> 8) << 16);
-}
-
-// x(m) of the contract: the span, the head before it, zeros before that and where there is no head
-template <int FMT>
-__device__ __forceinline__ uint32_t rs_sample_at(const uint8_t *src, const uint8_t *head, int64_t m, int nsamp, int ntaps)
-{
-    if (m >= 0) return m < (int64_t) nsamp ? rs_load_pair<FMT>(src, m) : 0u;
-    return head && m >= -(int64_t) (ntaps - 1) ? rs_load_pair<FMT>(head, (int64_t) (ntaps - 1) + m) : 0u;
-}
+using stream::sample_at;
+using stream::store_sample;
+using stream::count_clipped;
 
 // the contract's y of one element from its row sums, clamped to +-QMAX; clipped counts the elements the clamp changed
 template <int OUT>
@@ -50,29 +39,6 @@ __device__ __forceinline__ int rs_finish(int a0, int a1, int mu, int shift, int 
     const int64_t c = y < -QMAX ? -QMAX : y > QMAX ? QMAX : y;
     clipped += c != y;
     return (int) c;
-}
-
-template <int OUT>
-__device__ __forceinline__ void rs_store_sample(uint8_t *dst, uint64_t j, int i, int q)
-{
-    if (OUT == GPSIQ_SC16) *reinterpret_cast<uint32_t *>(dst + j * 4) = ((uint32_t) i & 0xffffu) | ((uint32_t) q << 16);
-    else *reinterpret_cast<uint16_t *>(dst + j * 2) = (uint16_t) (((uint32_t) i & 0xffu) | (((uint32_t) q & 0xffu) << 8));
-}
-
-// per wave, then per workgroup; one atomic of the workgroup if it clamped anything.  Integer addition: the order of arrival does not
-// matter.  Every thread of the workgroup arrives here.
-__device__ __forceinline__ void rs_count_clipped(unsigned long long clipped, unsigned long long *count)
-{
-    for (int off = 32; off >= 1; off >>= 1) clipped += __shfl_xor(clipped, off, 64);
-    __shared__ unsigned long long part[kRsThreads / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-#pragma unroll
-        for (int k = 0; k < kRsThreads / 64; ++k) sum += part[k];
-        if (sum) atomicAdd(count, sum);
-    }
 }
 
 // the tap table of a call into LDS, rows of resample_tap_stride(ntaps) dwords (gpsiq_resample_geometry.h); the caller synchronises
@@ -126,14 +92,14 @@ __global__ __launch_bounds__(kRsThreads) void resample_generic(const uint8_t *__
         const uint32_t *t0 = tap + q * ts, *t1 = t0 + (interp ? ts : 0);
         int a0i = 0, a0q = 0, a1i = 0, a1q = 0;
         for (int k = 0; k < ntaps; ++k) {
-            const uint32_t v = rs_sample_at<IN>(src, head, m - k, nsamp, ntaps);
+            const uint32_t v = sample_at<IN>(src, head, m - k, nsamp, ntaps);
             const int sh = (k & 1) << 4;
             rs_mac((int) (int16_t) (t0[k >> 1] >> sh), v, a0i, a0q);
             if (interp) rs_mac((int) (int16_t) (t1[k >> 1] >> sh), v, a1i, a1q);
         }
-        rs_store_sample<OUT>(dst, j, rs_finish<OUT>(a0i, a1i, mu, shift, interp, clipped), rs_finish<OUT>(a0q, a1q, mu, shift, interp, clipped));
+        store_sample<OUT>(dst, j, rs_finish<OUT>(a0i, a1i, mu, shift, interp, clipped), rs_finish<OUT>(a0q, a1q, mu, shift, interp, clipped));
     }
-    rs_count_clipped(clipped, count);
+    count_clipped<kRsThreads>(clipped, count);
 }
 
 // where sample i of a run's window lies (gpsiq_resample_geometry.h)
@@ -186,7 +152,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_rows(const uint8_t *__res
         const int64_t m_lo = m_first - (ntaps - 1);                                                  // the window's first sample
         const int wlen = (int) (m_last - m_lo) + 1;                                                  // its last: m_last < nsamp
         __syncthreads();                                                                             // the run before has read its window
-        for (int i = tid; i < wlen; i += kRsThreads) win[rs_widx<PAD>(i)] = rs_sample_at<IN>(src, head, m_lo + i, nsamp, ntaps);
+        for (int i = tid; i < wlen; i += kRsThreads) win[rs_widx<PAD>(i)] = sample_at<IN>(src, head, m_lo + i, nsamp, ntaps);
         __syncthreads();
         for (int o = tid; o < n; o += kRsThreads) {
             const uint64_t p = pos0 + (j0 + (uint64_t) o) * step;
@@ -196,11 +162,11 @@ __global__ __launch_bounds__(kRsThreads) void resample_rows(const uint8_t *__res
             int a0i = 0, a0q = 0, a1i = 0, a1q = 0;
             if (interp) rs_sums<PAD, true>(win, base, tap + q * ts, ts, ntaps, a0i, a0q, a1i, a1q);
             else rs_sums<PAD, false>(win, base, tap + q * ts, ts, ntaps, a0i, a0q, a1i, a1q);
-            rs_store_sample<OUT>(dst, j0 + (uint64_t) o, rs_finish<OUT>(a0i, a1i, mu, shift, interp, clipped),
-                                 rs_finish<OUT>(a0q, a1q, mu, shift, interp, clipped));
+            store_sample<OUT>(dst, j0 + (uint64_t) o, rs_finish<OUT>(a0i, a1i, mu, shift, interp, clipped),
+                              rs_finish<OUT>(a0q, a1q, mu, shift, interp, clipped));
         }
     }
-    rs_count_clipped(clipped, count);
+    count_clipped<kRsThreads>(clipped, count);
 }
 
 }  // namespace

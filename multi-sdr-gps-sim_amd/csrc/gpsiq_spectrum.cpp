@@ -3,7 +3,6 @@
 // look-up (gpsiq_spectrum_kernels.hip holds the kernels and the table of those that exist), launch and copy-back.  libgpsiq_rows.so
 // exports the typed call and reaches this through the plumbing entry "spectrum".
 // Host code: nothing here decides device code, so the file is not one of the device sources behind gpsiq_kernels_id().
-#include <cstdlib>
 #include <cstring>
 
 #include "gpsiq_ctx.h"
@@ -15,12 +14,7 @@ using namespace gpsiq;
 
 namespace {
 
-int forced_kernel()
-{
-    const char *env = std::getenv("GPSIQ_SPECTRUM_KERNEL");
-    if (!env) return kSpecAuto;
-    return !std::strcmp(env, "generic") ? kSpecForceGeneric : !std::strcmp(env, "mfma") ? kSpecForceMfma : kSpecAuto;
-}
+static_assert(kSpecAuto == 0 && kSpecForceGeneric == 1 && kSpecForceMfma == 2, "forced_kernel's values (gpsiq_stage_call.h)");
 
 // the coefficient of byte e = 2 n + c of a segment in X_comp[k]: Xi = I c + Q s, Xq = Q c - I s at idx = (k n T) mod 512
 inline int twiddle(int k, int comp, int e, int T)
@@ -88,7 +82,7 @@ int gpsiq_spectrum_impl(gpsiq_ctx_t *c, int nsamp, int sample_size, const void *
     if (!spectrum_fits(sample_size, nfft, window, navg, shift))
         return fail(GPSIQ_E_RANGE, "navg %d at shift %d: the sum of a group could pass 2^64 - 1 (gpsiq_spectrum_min_shift gives %d)", navg, shift,
                     spectrum_min_shift(sample_size, nfft, window, navg));
-    const SpectrumPlan p = plan_spectrum(nsamp, sample_size, nfft, hop, navg, forced_kernel());
+    const SpectrumPlan p = plan_spectrum(nsamp, sample_size, nfft, hop, navg, forced_kernel("GPSIQ_SPECTRUM_KERNEL", "mfma"));
     if (ngroups) *ngroups = p.ngroups;
     if (kernel_ms) *kernel_ms = 0.0f;
     SpectrumSet &k = c->spec;

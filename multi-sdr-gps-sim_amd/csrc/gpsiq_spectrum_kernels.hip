@@ -13,11 +13,13 @@
 
 #include "gpsiq_ctx.h"
 #include "gpsiq_spectrum_geometry.h"
+#include "gpsiq_stream.h"
 
 namespace gpsiq {
 namespace {
 
-typedef int spec_i32x4 __attribute__((ext_vector_type(4)));
+using stream::i32x4;
+using stream::load_pair;
 
 // Yi'^2 + Yq'^2: the shift is arithmetic and floors; |Y'| <= Ys < 2^32 by the host's bound, so each square fits uint64 and so does their sum
 __device__ __forceinline__ unsigned long long cell(long long yi, long long yq, int shift)
@@ -26,15 +28,6 @@ __device__ __forceinline__ unsigned long long cell(long long yi, long long yq, i
     yq >>= shift;
     const unsigned long long ai = (unsigned long long) (yi < 0 ? -yi : yi), aq = (unsigned long long) (yq < 0 ? -yq : yq);
     return ai * ai + aq * aq;
-}
-
-// sample m of the stream as one dword: I in the low half, Q in the high half, each sign-extended to 16 bits
-template <int FMT>
-__device__ __forceinline__ uint32_t spec_pair(const uint8_t *base, uint64_t m)
-{
-    if (FMT == GPSIQ_SC16) return *reinterpret_cast<const uint32_t *>(base + m * 4);
-    const uint32_t v = *reinterpret_cast<const uint16_t *>(base + m * 2);
-    return ((uint32_t) (int32_t) (int8_t) (v & 0xffu) & 0xffffu) | ((uint32_t) (int32_t) (int8_t) (v >> 8) << 16);
 }
 
 // Arguments: the span, the table as 512 dwords (cos in the low half, sin in the high half), nfft, hop, window, shift, navg, the units
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(kSpecThreads) void spectrum_generic(const uint8_t *
         unsigned long long sum[2] = {0, 0};
         for (uint64_t s = s0; s < s1; ++s) {
             __syncthreads();                                               // the segment before has been read, its bins' neighbours too
-            for (int i = tid; i < nfft; i += nthr) win[i] = spec_pair<FMT>(src, s * (uint64_t) hop + (uint64_t) i);
+            for (int i = tid; i < nfft; i += nthr) win[i] = load_pair<FMT>(src, (int64_t) (s * (uint64_t) hop + (uint64_t) i));
             __syncthreads();
             long long xi[2] = {0, 0}, xq[2] = {0, 0};
             for (int b = 0; b < bins; ++b) {
@@ -145,19 +138,19 @@ __global__ __launch_bounds__(kSpecThreads) void spectrum_mfma(const uint8_t *__r
         const int nseg = here < (uint64_t) cols ? (int) here : cols;       // segments of this pass
         const int ntile = (nseg + kSpecTileCols - 1) / kSpecTileCols;
         for (int rt = wave; rt < row_tiles; rt += kSpecThreads / 64) {
-            spec_i32x4 d0[kSpecMaxColTiles], d1[kSpecMaxColTiles];
+            i32x4 d0[kSpecMaxColTiles], d1[kSpecMaxColTiles];
 #pragma unroll
-            for (int c = 0; c < kSpecMaxColTiles; ++c) { d0[c] = spec_i32x4{0, 0, 0, 0}; d1[c] = spec_i32x4{0, 0, 0, 0}; }
+            for (int c = 0; c < kSpecMaxColTiles; ++c) { d0[c] = i32x4{0, 0, 0, 0}; d1[c] = i32x4{0, 0, 0, 0}; }
             const uint8_t *a_ptr = planes + (size_t) rt * (size_t) ksteps * (kSpecK * 16) + (size_t) lane * 16;
             for (int t = 0; t < ksteps; ++t) {
-                const spec_i32x4 a0 = *reinterpret_cast<const spec_i32x4 *>(a_ptr + (size_t) t * (kSpecK * 16));
-                const spec_i32x4 a1 = *reinterpret_cast<const spec_i32x4 *>(a_ptr + plane_bytes + (size_t) t * (kSpecK * 16));
+                const i32x4 a0 = *reinterpret_cast<const i32x4 *>(a_ptr + (size_t) t * (kSpecK * 16));
+                const i32x4 a1 = *reinterpret_cast<const i32x4 *>(a_ptr + plane_bytes + (size_t) t * (kSpecK * 16));
                 const int ch = (kSpecK * t) / chunk_bytes;
                 const uint8_t *b_ptr = win + (col + ch) * stride + (kSpecK * t - ch * chunk_bytes) + 16 * q;
 #pragma unroll
                 for (int c = 0; c < kSpecMaxColTiles; ++c) {
                     if (c < ntile) {
-                        const spec_i32x4 b = *reinterpret_cast<const spec_i32x4 *>(b_ptr + c * kSpecTileCols * stride);
+                        const i32x4 b = *reinterpret_cast<const i32x4 *>(b_ptr + c * kSpecTileCols * stride);
                         d0[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b, d0[c], 0, 0, 0);
                         d1[c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b, d1[c], 0, 0, 0);
                     }

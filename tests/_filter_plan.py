@@ -1,4 +1,4 @@
-"""The planner of the filter calls: tests/filter_plan.cpp (csrc/gpsiq_filter_plan.h, the header the calls themselves plan with)
+"""The planner and the operand builder of the filter calls: tests/filter_plan.cpp (csrc/gpsiq_filter_plan.h, the header the calls themselves plan with)
 compiled once per process with the host compiler, plain and with -fsanitize=address,undefined.  TEST INFRASTRUCTURE."""
 import atexit
 import collections
@@ -33,7 +33,8 @@ def executable(sanitize=False):
 
 def ask(requests, sanitize=False):
     """requests: tuples ("plan", nsamp, in_size, ntaps, decim, phase, max_tap, force) | ("piece", nblocks, nsamp, src_block_bytes,
-    override) | ("limits",) -> Plan / Nothing / int / Limits per request; one process for all"""
+    override) | ("planes", ntaps, decim, seed, kind) | ("limits",) -> Plan / Nothing / int / True / Limits per request; one process
+    for all"""
     text = "".join(" ".join(str(int(v)) if i else v for i, v in enumerate(r)) + "\n" for r in requests)
     r = subprocess.run([executable(sanitize)], input=text, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
@@ -45,6 +46,8 @@ def ask(requests, sanitize=False):
         kv = dict(w.split("=") for w in words if "=" in w)
         if words[0] == "nothing":
             out.append(Nothing(int(kv["nout"]), int(kv["next"])))
+        elif words[0] == "planes":
+            out.append(words[1] == "ok")
         elif "kernel" in kv:
             out.append(Plan(*(int(kv[k]) for k in Plan._fields)))
         elif "piece" in kv:

@@ -1,4 +1,4 @@
-// filter_own.cpp -- FilterSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device
+// filter_own.cpp -- FirSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device
 // context, and with it PieceRing::reserve (csrc/gpsiq_stage_batch.h), the staging ring the filtered batch call works through its
 // pieces with, on the CPU, in the manner of tests/own_types.cpp.  `Both` below is what that call reserves: its sixteen resources.
 // TEST INFRASTRUCTURE: tests/test_filter_own.py builds this file with the address and undefined-behaviour sanitizers and runs it.
@@ -73,12 +73,12 @@ int fail(int code, const char *fmt, ...)
 }
 }
 
-using gpsiq::FilterSet;
+using gpsiq::FirSet;
 using gpsiq::PieceRing;
 
 // what gpsiq_generate_batch_filtered reserves, in its order: the ring, then the filter's own
 struct Both {
-    PieceRing r; FilterSet f;
+    PieceRing r; FirSet f;
     int reserve(size_t render, size_t out) { if (int rc = r.reserve(render, out)) return rc; return f.reserve(); }
 };
 
@@ -87,19 +87,19 @@ static bool room(const B &b, size_t n) { return b.get() != nullptr && b.cap() >=
 
 static bool whole(const Both &b, size_t n)
 {
-    const FilterSet &f = b.f;
+    const FirSet &f = b.f;
     const PieceRing &r = b.r;
-    return room(f.d_coef, FilterSet::kCoefBytes) && room(f.h_coef, FilterSet::kCoefBytes) && room(f.d_count, 1) && room(f.h_count, 1) &&
+    return room(f.d_coef, FirSet::kCoefBytes) && room(f.h_coef, FirSet::kCoefBytes) && room(f.clip.d_count, 1) && room(f.clip.h_count, 1) &&
            room(r.d_render[0], n) && room(r.d_render[1], n) && room(r.d_out[0], n) && room(r.d_out[1], n) && r.stage_stream.get() && r.copy_stream.get() &&
-           f.t0.get() && f.t1.get() && r.staged[0].get() && r.staged[1].get() && r.copied[0].get() && r.copied[1].get();
+           f.clip.t0.get() && f.clip.t1.get() && r.staged[0].get() && r.staged[1].get() && r.copied[0].get() && r.copied[1].get();
 }
 
 int main()
 {
     // gpsiq_filter: coefficients, counter and the two timing events alone -- no stream, no staging
     {
-        FilterSet f;
-        CHECK(f.reserve() == GPSIQ_OK && g_created == 6 && room(f.d_coef, FilterSet::kCoefBytes) && room(f.h_count, 1));
+        FirSet f;
+        CHECK(f.reserve() == GPSIQ_OK && g_created == 6 && room(f.d_coef, FirSet::kCoefBytes) && room(f.clip.h_count, 1));
         const long before = g_calls;
         CHECK(f.reserve() == GPSIQ_OK && g_calls == before);
     }

@@ -342,7 +342,7 @@ int main()
         CHECK(f.d_epochs.cap() == base + 64);
         CHECK(p.d_render[0].cap() == base + 256 && p.d_render[1].cap() == base + 256 && p.d_out[0].cap() == base + 256 && p.d_out[1].cap() == base + 256);
         PackSet q;                                                                   // the packer's own: the counter and its timing events
-        CHECK(q.reserve() == GPSIQ_OK && room(q.d_count, 1) && room(q.h_count, 1) && q.t0.get() && q.t1.get());
+        CHECK(q.reserve() == GPSIQ_OK && room(q.clip.d_count, 1) && room(q.clip.h_count, 1) && q.clip.t0.get() && q.clip.t1.get());
         PieceRing m;                                                                 // a stage that works in place: no output pair
         CHECK(m.reserve(100, 0) == GPSIQ_OK && room(m.d_render[0], 100) && room(m.d_render[1], 100) && !m.d_out[0].get() && !m.d_out[1].get());
         AcquireSet g;                                                                // the generic kernel without correlations: neither buffer made

@@ -1,4 +1,4 @@
-"""FilterSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device context, and
+"""FirSet::reserve (csrc/gpsiq_filter.h), the first-use routine of the filter stage's member of the device context, and
 PieceRing::reserve (csrc/gpsiq_stage_batch.h), that of the staging ring its batch call works through its pieces with, on the CPU:
 tests/filter_own.cpp defines the HIP entry points csrc/gpsiq_own.h calls as counting fakes over malloc / free and is built with the
 address and undefined-behaviour sanitizers; no HIP runtime is linked.  It checks that gpsiq_filter's share is six resources, neither a

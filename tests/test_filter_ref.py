@@ -1,6 +1,6 @@
 """The filter stage on the CPU: tests/_filter_ref.py (the numpy restatement the GPU tests compare every byte with) against a second,
 scalar statement of the contract of include/gpsiq_rows.h ("Filter"), continuation in pieces, the library's gpsiq_filter_span and
-gpsiq_filter_design, the planner of the calls (tests/filter_plan.cpp, also under ASan + UBSan), the refusals that need no device and
+gpsiq_filter_design, the planner and the matrix operand of the calls (tests/filter_plan.cpp, also under ASan + UBSan), the refusals that need no device and
 the argument checks of gpsiq_runahead --filter."""
 import ctypes as C
 import os
@@ -188,6 +188,15 @@ def test_pieces_tile_the_call_and_the_override_is_honoured(sanitize):
     got = fp.ask([("piece", 0, 4096, 8192, 0), ("piece", 7, 4096, 8192, 0), ("piece", 7, 4096, 8192, 3), ("piece", 7, 4096, 8192, 99),
                   ("piece", 4130, 260000, 520000, 0), ("piece", 100, INT_MAX, 2 * INT_MAX, 50), ("piece", 5000, 1 << 20, 1 << 21, 4000)], sanitize)
     assert got == [0, 7, 3, 7, 65, 1, 2047]                          # 32 MiB of source; a piece's samples fit an int whatever was asked
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan+ubsan"])
+def test_planes_times_window_is_the_direct_sum(sanitize):
+    """filter_build_planes (csrc/gpsiq_filter_plan.h), the operand gpsiq_filter stages for filter_mfma: one tile column multiplied out
+    in the kernel's arithmetic against the direct real sum, inside the program."""
+    shapes = [(1, 1), (2, 1), (16, 1), (17, 3), (33, 1), (33, 16), (129, 4), (257, 2), (512, 1), (512, 16), (25, 7)]
+    reqs = [("planes", ntaps, decim, seed, kind) for ntaps, decim in shapes for seed in (0, 1, 2) for kind in (0, 1)]
+    assert all(fp.ask(reqs, sanitize))
 
 
 # ---- gpsiq_runahead --filter: the checks that need no device -------------------------------------------------------------------------
