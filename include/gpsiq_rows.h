@@ -831,6 +831,63 @@ int gpsiq_notch_find(const uint64_t *power /* [nfft], one group of gpsiq_spectru
 int gpsiq_notch_design(double fs, const double *f_hz, int nlines, double width_hz, int ntaps, int shift,
                        gpsiq_ctap_t *taps);                                                            /* host arithmetic */
 
+/* ---- Array: covariance, weights and a combiner for several elements -------------------------------------------------------------------
+ * Everything above reads ONE stream, and the notch can only take a narrowband line out.  Against a swept or broadband jammer a receiver
+ * works in space: several antenna elements, the sample covariance of their streams, weights that put a null on the jammer, a combiner.
+ * An element is the same timeline rendered with every channel's carr_phase advanced by the element's geometric phase (gpsiq_generate_batch
+ * reads carr_phase where a slot is seeded or re-allocated, include/gpsiq.h) and with a noise seed of its own; a jammer from a direction is
+ * a gpsiq_mix term whose phase0 differs per element.  nelem streams x_e(n) = I_e(n) + j Q_e(n), all of one sample_size, 1 <= nelem <=
+ * GPSIQ_ARRAY_MAX_ELEM, given as a HOST array src[nelem] of stream pointers; every stream lies in device memory or in page-locked
+ * memory from gpsiq_host_alloc, non-null where nsamp > 0 and 4-byte aligned; nsamp >= 0.  Anything else is GPSIQ_E_ARG.
+ *
+ * gpsiq_array_cov writes the exact covariance  R[a][b] = sum over n < nsamp of x_a(n) * conj(x_b(n))  to cov[a][b][0..1] (host, int64):
+ *   Re R[a][b] = sum (Ia Ib + Qa Qb)        Im R[a][b] = sum (Qa Ib - Ia Qb)
+ * The full matrix is written: the diagonal's imaginary part is exactly 0 and R[b][a] is the conjugate of R[a][b].  The sums cannot wrap:
+ * one int16 term is at most 2 * 32768^2 = 2^31 in magnitude and nsamp < 2^31, so |R| < 2^62 (an int8 term is at most 2^15).  Everything
+ * on the device is integers, and integer addition makes the order the workgroups' atomics arrive in irrelevant: the same call twice
+ * gives the same numbers, whichever kernel serves.  nsamp == 0 launches nothing and writes zeros.  Stream order and return are
+ * gpsiq_spectrum's: the call is queued on hip_stream behind the caller's work there, and returns synchronously.
+ * GPSIQ_ARRAY_KERNEL=generic|mfma in the environment, read per call, forces a kernel where it can serve (the matrix kernel serves int8
+ * input); the numbers never depend on it.
+ *
+ * gpsiq_array_combine is the beamformer  y(n) = sum over e of w_e * x_e(n),  w_e = re_e + j im_e:
+ *   accI = sum over e of re_e * I_e(n) - im_e * Q_e(n)
+ *   accQ = sum over e of re_e * Q_e(n) + im_e * I_e(n)
+ * and each component goes through gpsiq_cfilter's finish: y = floor((acc + 2^(shift-1)) / 2^shift) (shift 0: acc), clamped to +-127 /
+ * +-32767 of out_sample_size, *clipped the elements the clamp changed; 0 <= shift <= 24 and the four format pairs, else GPSIQ_E_ARG.
+ * The bound is gpsiq_cfilter's: sum over e of (|re_e| + |im_e|) <= 65535, else GPSIQ_E_RANGE; with it |acc| <= 65535 * 32768 < 2^31 for
+ * both input formats.  dst holds nsamp samples, 4-byte aligned, device or page-locked memory, and must not overlap any source
+ * (GPSIQ_E_ARG).  nsamp == 0 launches nothing.  Stream order and return as above.  The operation is pointwise: a span combined in
+ * pieces, each piece's sources and dst advanced alike, gives the bytes of one call and its counts add up to that call's count.
+ * The two calls are tied by an identity: with shift 0 and nothing clamped,  sum |y(n)|^2 = sum over a, b of w_a conj(w_b) R[a][b]  exactly.
+ *
+ * gpsiq_array_steer: pos[e][0..2] is element e's position east, north, up in wavelengths; phase_cycles[e] = frac(pos_e . u) in [0, 1),
+ * u = (cos el sin az, cos el cos az, sin el): the phase advance of a plane wave from that direction at the element.  GPSIQ_E_ARG: a
+ * null pointer, nelem outside 1..8, a non-finite input.
+ *
+ * gpsiq_array_weights turns a covariance into the combiner's weights.  Rn = cov / nsamp + loading * (trace(cov / nsamp) / nelem) * I;
+ * c = e_0 (steer_cycles NULL: power inversion, element 0 the reference) or c_e = exp(j 2 pi steer_cycles[e]) (minimum variance towards a
+ * steering vector);  v = Rn^-1 c / (c^H Rn^-1 c), solved in long double through a Hermitian (Cholesky) factorisation written here;
+ * w_e = rint(2^shift * conj(v_e)), component by component, so that the combiner's y = v^H x * 2^shift before its own shift.
+ * GPSIQ_E_ARG: a null pointer, nelem outside 1..8, nsamp == 0, loading negative or not finite, a non-finite steering phase, shift outside
+ * 0..24, a matrix that is not positive definite after loading.  GPSIQ_E_RANGE: a component leaves int16 or the rounded weights break the
+ * sum bound; the caller then lowers shift.  Only the lower triangle of cov is read.
+ * Long double arithmetic: its properties are contract, its bits are not.
+ *   1. before rounding, v is the solution of Rn v = c / (c^H Rn^-1 c) to the accuracy the condition number of Rn leaves;
+ *   2. | sum over e of w_e c_e - 2^shift | <= nelem / sqrt 2: only rounding is left in the constraint, at most 0.5 per component;
+ *   3. v^H Rn v = 1 / (c^H Rn^-1 c) <= Rn[0][0] for power inversion (e_0 itself satisfies the constraint), and for Rn = s^2 I + J a a^H
+ *      with a_0 of modulus 1 the residual jammer power J |v^H a|^2 is below s^2. */
+#define GPSIQ_ARRAY_MAX_ELEM 8
+
+int gpsiq_array_cov(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* host [nelem] stream pointers */, int nsamp, int sample_size,
+                    void *hip_stream, int64_t *cov /* host [nelem][nelem][2] */, float *kernel_ms /* may be NULL */);
+int gpsiq_array_combine(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* host [nelem] */, int nsamp, int sample_size,
+                        const gpsiq_ctap_t *w /* host [nelem] */, int shift, int out_sample_size, void *dst, void *hip_stream,
+                        uint64_t *clipped, float *kernel_ms);                /* the last two may be NULL */
+int gpsiq_array_steer(const double *pos /* [nelem][3] */, int nelem, double az_rad, double el_rad, double *phase_cycles);   /* host arithmetic */
+int gpsiq_array_weights(const int64_t *cov /* [nelem][nelem][2] */, int nelem, uint64_t nsamp, const double *steer_cycles /* may be NULL */,
+                        double loading, int shift, gpsiq_ctap_t *w /* [nelem] */);                                         /* host arithmetic */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

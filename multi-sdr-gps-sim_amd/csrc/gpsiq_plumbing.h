@@ -35,7 +35,8 @@ void *gpsiq_plumbing(const char *name);
  * "generate_batch_mixed" are gpsiq_mix and gpsiq_generate_batch_mixed (ibid., "Mix"; csrc/gpsiq_mix.cpp).  "resample" and
  * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp).  "agc" and
  * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp).  "cfilter" is
- * gpsiq_cfilter (ibid., "Complex filter and notch"; csrc/gpsiq_cfilter.cpp). */
+ * gpsiq_cfilter (ibid., "Complex filter and notch"; csrc/gpsiq_cfilter.cpp).  "array_cov" and "array_combine" are gpsiq_array_cov and
+ * gpsiq_array_combine (ibid., "Array"; csrc/gpsiq_array.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -235,6 +236,11 @@ int gpsiq_agc_last_ms(const gpsiq_ctx_t *ctx, float out[3]);
  * planes, 2 cfilter_mfma16; -1: nothing was launched, or no call yet), out[1] the grid, out[2] the outputs of a workgroup's run, out[3]
  * the k-steps of a tile (0 for the generic kernel). */
 int gpsiq_cfilter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
+/* What the context's last gpsiq_array_cov / gpsiq_array_combine took (csrc/gpsiq_array_plan.h): out[0] the kernel (0 array_cov_generic,
+ * 1 array_cov_mfma, 2 array_combine; -1: nothing was launched, or no call yet), out[1] the grid, out[2] the run of a workgroup (samples
+ * for the generic covariance kernel, k-steps of 64 samples for the matrix kernel) or the samples of a combiner lane's slot, out[3] the
+ * elements. */
+int gpsiq_array_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
 
 #ifdef __cplusplus
 }

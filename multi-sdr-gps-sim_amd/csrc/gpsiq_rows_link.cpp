@@ -227,3 +227,20 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_cfilter(gpsiq_ctx_t 
     static const auto f = gpsiq::core<decltype(&gpsiq_cfilter)>("cfilter");
     return f(ctx, nsamp, sample_size, src, head, taps, ntaps, shift, decim, phase, out_sample_size, dst, hip_stream, nout, clipped, kernel_ms);
 }
+
+// The array stage runs on the context's device (csrc/gpsiq_array.cpp) and is exported here like the filter (include/gpsiq_rows.h,
+// "Array"); gpsiq_array_steer and gpsiq_array_weights, plain arithmetic, are in gpsiq_stage_math.cpp.
+extern "C" __attribute__((visibility("default"))) int gpsiq_array_cov(gpsiq_ctx_t *ctx, int nelem, const void *const *src, int nsamp, int sample_size,
+                                                                      void *hip_stream, int64_t *cov, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_array_cov)>("array_cov");
+    return f(ctx, nelem, src, nsamp, sample_size, hip_stream, cov, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_array_combine(gpsiq_ctx_t *ctx, int nelem, const void *const *src, int nsamp, int sample_size,
+                                                                          const gpsiq_ctap_t *w, int shift, int out_sample_size, void *dst,
+                                                                          void *hip_stream, uint64_t *clipped, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_array_combine)>("array_combine");
+    return f(ctx, nelem, src, nsamp, sample_size, w, shift, out_sample_size, dst, hip_stream, clipped, kernel_ms);
+}

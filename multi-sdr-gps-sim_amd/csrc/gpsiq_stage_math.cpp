@@ -12,6 +12,7 @@
 #include "gpsiq_resample_plan.h"
 #include "gpsiq_agc_plan.h"
 #include "gpsiq_cfilter_geometry.h"
+#include "gpsiq_array_geometry.h"
 
 #include <algorithm>
 #include <cmath>
@@ -492,6 +493,89 @@ int gpsiq_notch_design(double fs, const double *f_hz, int nlines, double width_h
         taps[mid + d].im = (int16_t) q[d][1];
         taps[mid - d].im = (int16_t) -q[d][1];
     }
+    return GPSIQ_OK;
+}
+
+// include/gpsiq_rows.h, "Array": the phase advance, in cycles in [0, 1), of a plane wave from (az, el) at every element
+int gpsiq_array_steer(const double *pos, int nelem, double az_rad, double el_rad, double *phase_cycles)
+{
+    if (!pos || !phase_cycles) return fail(GPSIQ_E_ARG, "null argument");
+    if (nelem < 1 || nelem > kArrMaxElem) return fail(GPSIQ_E_ARG, "nelem %d outside 1..%d", nelem, kArrMaxElem);
+    if (!std::isfinite(az_rad) || !std::isfinite(el_rad)) return fail(GPSIQ_E_ARG, "direction (%g, %g) not finite", az_rad, el_rad);
+    const double u[3] = {std::cos(el_rad) * std::sin(az_rad), std::cos(el_rad) * std::cos(az_rad), std::sin(el_rad)};
+    for (int e = 0; e < nelem; ++e) {
+        const double d = pos[3 * e] * u[0] + pos[3 * e + 1] * u[1] + pos[3 * e + 2] * u[2];
+        if (!std::isfinite(d)) return fail(GPSIQ_E_ARG, "element %d: position not finite", e);
+        double f = d - std::floor(d);
+        if (!(f < 1.0)) f = 0.0;                                       // (a tiny negative d rounds up to 1)
+        phase_cycles[e] = f;
+    }
+    return GPSIQ_OK;
+}
+
+// ibid.: v = Rn^-1 c / (c^H Rn^-1 c) with Rn = cov / nsamp + loading (trace / nelem) I, through the Cholesky factor Rn = L L^H in
+// long double (L lower triangular with a real positive diagonal: a pivot that is not positive says Rn is not positive definite):
+// L y = c forwards, L^H z = y backwards, z = Rn^-1 c, and c^H z = |y|^2 is real.  w_e = rint(2^shift conj(v_e)).
+int gpsiq_array_weights(const int64_t *cov, int nelem, uint64_t nsamp, const double *steer_cycles, double loading, int shift, gpsiq_ctap_t *w)
+{
+    if (!cov || !w) return fail(GPSIQ_E_ARG, "null argument");
+    if (nelem < 1 || nelem > kArrMaxElem) return fail(GPSIQ_E_ARG, "nelem %d outside 1..%d", nelem, kArrMaxElem);
+    if (nsamp == 0) return fail(GPSIQ_E_ARG, "a covariance of no samples");
+    if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(GPSIQ_E_ARG, "loading %g: finite and not negative", loading);
+    if (shift < 0 || shift > kArrMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kArrMaxShift);
+    typedef long double ld;
+    const ld two_pi = 6.283185307179586476925286766559L;
+    ld lr[kArrMaxElem][kArrMaxElem], li[kArrMaxElem][kArrMaxElem], cr[kArrMaxElem], ci[kArrMaxElem];
+    ld trace = 0.0L;
+    for (int a = 0; a < nelem; ++a) trace += (ld) cov[2 * (a * nelem + a)] / (ld) nsamp;
+    const ld load = (ld) loading * trace / (ld) nelem;
+    for (int a = 0; a < nelem; ++a) {
+        if (steer_cycles) {
+            if (!std::isfinite(steer_cycles[a])) return fail(GPSIQ_E_ARG, "steering phase %d not finite", a);
+            cr[a] = std::cos(two_pi * (ld) steer_cycles[a]);
+            ci[a] = std::sin(two_pi * (ld) steer_cycles[a]);
+        } else { cr[a] = a ? 0.0L : 1.0L; ci[a] = 0.0L; }
+    }
+    // Cholesky, from the lower triangle of cov
+    for (int j = 0; j < nelem; ++j) {
+        ld d = (ld) cov[2 * (j * nelem + j)] / (ld) nsamp + load;
+        for (int k = 0; k < j; ++k) d -= lr[j][k] * lr[j][k] + li[j][k] * li[j][k];
+        if (!(d > 0.0L) || !std::isfinite((double) d)) return fail(GPSIQ_E_ARG, "the covariance is not positive definite at element %d (loading %g)", j, loading);
+        const ld piv = std::sqrt(d);
+        lr[j][j] = piv; li[j][j] = 0.0L;
+        for (int i = j + 1; i < nelem; ++i) {
+            ld sr = (ld) cov[2 * (i * nelem + j)] / (ld) nsamp, si = (ld) cov[2 * (i * nelem + j) + 1] / (ld) nsamp;
+            for (int k = 0; k < j; ++k) {                              // - L[i][k] conj(L[j][k])
+                sr -= lr[i][k] * lr[j][k] + li[i][k] * li[j][k];
+                si -= li[i][k] * lr[j][k] - lr[i][k] * li[j][k];
+            }
+            lr[i][j] = sr / piv; li[i][j] = si / piv;
+        }
+    }
+    ld yr[kArrMaxElem], yi[kArrMaxElem], zr[kArrMaxElem], zi[kArrMaxElem], denom = 0.0L;
+    for (int i = 0; i < nelem; ++i) {                                  // L y = c
+        ld sr = cr[i], si = ci[i];
+        for (int k = 0; k < i; ++k) { sr -= lr[i][k] * yr[k] - li[i][k] * yi[k]; si -= lr[i][k] * yi[k] + li[i][k] * yr[k]; }
+        yr[i] = sr / lr[i][i]; yi[i] = si / lr[i][i];
+        denom += yr[i] * yr[i] + yi[i] * yi[i];
+    }
+    for (int i = nelem - 1; i >= 0; --i) {                             // L^H z = y: (L^H)[i][k] = conj(L[k][i])
+        ld sr = yr[i], si = yi[i];
+        for (int k = i + 1; k < nelem; ++k) { sr -= lr[k][i] * zr[k] + li[k][i] * zi[k]; si -= lr[k][i] * zi[k] - li[k][i] * zr[k]; }
+        zr[i] = sr / lr[i][i]; zi[i] = si / lr[i][i];
+    }
+    if (!(denom > 0.0L)) return fail(GPSIQ_E_ARG, "the constraint has no solution");
+    const ld scale = std::ldexp(1.0L, shift);
+    long q[kArrMaxElem][2], mag = 0;
+    for (int e = 0; e < nelem; ++e) {
+        const ld re = scale * zr[e] / denom, im = -scale * zi[e] / denom;      // conj(v_e)
+        if (!(std::fabs(re) < 65536.0L) || !(std::fabs(im) < 65536.0L)) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
+        q[e][0] = std::lrint(re); q[e][1] = std::lrint(im);
+        if (q[e][0] > 32767 || q[e][0] < -32768 || q[e][1] > 32767 || q[e][1] < -32768) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
+        mag += std::labs(q[e][0]) + std::labs(q[e][1]);
+    }
+    if (mag > kArrWeightSum) return fail(GPSIQ_E_RANGE, "sum |re| + |im| %ld above %ld at shift %d", mag, kArrWeightSum, shift);
+    for (int e = 0; e < nelem; ++e) { w[e].re = (int16_t) q[e][0]; w[e].im = (int16_t) q[e][1]; }
     return GPSIQ_OK;
 }
 

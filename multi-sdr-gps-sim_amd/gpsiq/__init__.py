@@ -204,6 +204,12 @@ _cfilter = _sig("gpsiq_cfilter", _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
 _cfilter_last_plan = _sig("gpsiq_cfilter_last_plan", _i, _vp, _vp)
 _notch_find = _sig("gpsiq_notch_find", _i, _vp, _i, _d, _d, _i, _vp, _vp, C.POINTER(_i))
 _notch_design = _sig("gpsiq_notch_design", _i, _d, _vp, _i, _d, _i, _i, _vp)
+_array_cov = _sig("gpsiq_array_cov", _i, _vp, _i, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_float))
+_array_combine = _sig("gpsiq_array_combine", _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_array_steer = _sig("gpsiq_array_steer", _i, _vp, _i, _d, _d, _vp)
+_array_weights = _sig("gpsiq_array_weights", _i, _vp, _i, C.c_uint64, _vp, _d, _i, _vp)
+_array_last_plan = _sig("gpsiq_array_last_plan", _i, _vp, _vp)
+ARRAY_MAX_ELEM = 8
 
 
 class CTap(C.Structure):
@@ -879,6 +885,52 @@ def notch_design(fs, f_hz, width_hz, ntaps, shift=12):
     return taps
 
 
+def array_steer(pos, az_rad, el_rad):
+    """gpsiq_array_steer: the phase advance, in cycles in [0, 1), of a plane wave from azimuth az_rad (from north towards east) and
+    elevation el_rad at the elements at pos [nelem, 3] (east, north, up in wavelengths) -> float64 [nelem]."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise GpsiqError(-1, f"element positions are [nelem, 3] (east, north, up), not an array of shape {pos.shape}")
+    out = np.zeros(max(len(pos), 1), dtype=np.float64)
+    _check(_array_steer(_p(pos) if len(pos) else None, len(pos), float(az_rad), float(el_rad), _p(out)))
+    return out[:len(pos)].copy()
+
+
+def array_weights(cov, nsamp, steer=None, loading=0.0, shift=12):
+    """gpsiq_array_weights: the combiner's weights int16 [nelem, 2] (re, im) over 2**shift from a covariance int64 [nelem, nelem, 2] of
+    nsamp samples: power inversion with element 0 the reference (steer None), or minimum variance towards the steering phases `steer`
+    (cycles, from array_steer); `loading` adds that fraction of the mean diagonal to the diagonal."""
+    cov = np.ascontiguousarray(cov, dtype=np.int64)
+    if cov.ndim != 3 or cov.shape[0] != cov.shape[1] or cov.shape[2] != 2:
+        raise GpsiqError(-1, f"a covariance is [nelem, nelem, 2] (re, im), not an array of shape {cov.shape}")
+    nelem = cov.shape[0]
+    st = None
+    if steer is not None:
+        st = np.ascontiguousarray(steer, dtype=np.float64).ravel()
+        if len(st) != nelem:
+            raise GpsiqError(-1, f"{len(st)} steering phases for {nelem} elements")
+    w = np.zeros((max(nelem, 1), 2), dtype=np.int16)
+    _check(_array_weights(_p(cov) if cov.size else None, nelem, _u64_arg(nsamp, "nsamp"), None if st is None else _p(st), float(loading), int(shift),
+                          _p(w)))
+    return w[:nelem].copy()
+
+
+def array_element(desc, phases):
+    """The descriptor timeline of one array element: a copy of desc (CHAN_DTYPE [nblocks, nchan]) with phases[channel] (cycles) added
+    to every row's carr_phase, modulo 1.  gpsiq_generate_batch reads carr_phase only in block 0 and where a slot is re-allocated, so
+    this is the same timeline seen through the element's geometric phase."""
+    out = np.array(desc, dtype=CHAN_DTYPE, copy=True)
+    if out.ndim != 2:
+        raise GpsiqError(-1, f"a descriptor timeline is [nblocks, nchan], not an array of shape {out.shape}")
+    ph = np.ascontiguousarray(phases, dtype=np.float64).ravel()
+    if len(ph) != out.shape[1]:
+        raise GpsiqError(-1, f"{len(ph)} phases for {out.shape[1]} channels")
+    cp = np.mod(out["carr_phase"] + ph[None, :], 1.0)
+    cp[cp >= 1.0] = 0.0                                      # (a tiny negative sum rounds up to 1)
+    out["carr_phase"] = cp
+    return out
+
+
 def resample_step(fs_in, fs_out, ppb=0.0):
     """gpsiq_resample_step: the step from a stream at fs_in to a receiver at fs_out whose clock runs ppb parts per billion fast."""
     step = _u64(0)
@@ -1236,6 +1288,35 @@ class Context:
         out = (C.c_long * 4)()
         _check(_cfilter_last_plan(self._h, out))
         return {0: "generic", 1: "mfma", 2: "mfma16"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    def array_cov(self, ptrs, nsamp, sample_size, stream=None):
+        """gpsiq_array_cov: the exact covariance of the streams at `ptrs` (device or page-locked addresses, one per element), nsamp
+        complex samples each -> (int64 [nelem, nelem, 2] (re, im) of sum x_a conj(x_b), kernel milliseconds)."""
+        ptrs = [int(p or 0) for p in ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        cov = np.zeros((len(ptrs), len(ptrs), 2), dtype=np.int64)
+        ms = C.c_float(0.0)
+        _check(_array_cov(self._h, len(ptrs), arr, int(nsamp), int(sample_size), _vp(stream or 0), _p(cov) if cov.size else None, C.byref(ms)))
+        return cov, float(ms.value)
+
+    def array_combine(self, ptrs, nsamp, sample_size, weights, shift, out_sample_size, dst_device_ptr, stream=None):
+        """gpsiq_array_combine: sum over the elements of weights[e] * stream e ([nelem, 2] int16 (re, im), or CTap: ctaps()), rounded by
+        `shift`, clamped into out_sample_size at dst_device_ptr -> (elements the clamp changed, kernel milliseconds)."""
+        ptrs = [int(p or 0) for p in ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        w = ctaps(weights)
+        if len(w) != len(ptrs):
+            raise GpsiqError(-1, f"{len(w)} weights for {len(ptrs)} elements")
+        clipped, ms = C.c_uint64(0), C.c_float(0.0)
+        _check(_array_combine(self._h, len(ptrs), arr, int(nsamp), int(sample_size), _p(w) if len(w) else None, int(shift), int(out_sample_size),
+                              _vp(dst_device_ptr), _vp(stream or 0), C.byref(clipped), C.byref(ms)))
+        return int(clipped.value), float(ms.value)
+
+    def array_last_plan(self):
+        """What the last array_cov() / array_combine() took: (kernel name or None, grid, run of a workgroup or samples of a slot, elements)."""
+        out = (C.c_long * 4)()
+        _check(_array_last_plan(self._h, out))
+        return {0: "generic", 1: "mfma", 2: "combine"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
 
     def generate_batch_filtered(self, desc, nsamp, fs, sample_size, taps, shift, decim, out_sample_size, host_ptr=None, block_stride=None,
                                 carr_out=None):
