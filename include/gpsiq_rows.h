@@ -888,6 +888,58 @@ int gpsiq_array_steer(const double *pos /* [nelem][3] */, int nelem, double az_r
 int gpsiq_array_weights(const int64_t *cov /* [nelem][nelem][2] */, int nelem, uint64_t nsamp, const double *steer_cycles /* may be NULL */,
                         double loading, int shift, gpsiq_ctap_t *w /* [nelem] */);                                         /* host arithmetic */
 
+/* ---- Space-time array: covariance, weights and a combiner over elements and taps ------------------------------------------------------
+ * Spatial weights have nelem - 1 degrees of freedom, and one reflection uses them up: a broadband jammer that reaches the elements
+ * directly from one direction and again d samples later from another has a different spatial signature at every frequency, and two
+ * elements cannot null it.  A tapped combiner can: W_0(z) = a_1 + b_1 z^-d, W_1(z) = -(a_0 + b_0 z^-d) is an exact null of
+ * x_e = a_e j(n) + b_e j(n - d) with d + 1 taps.  These calls are the array's with a delay line behind every element.
+ * Sizes: 1 <= nelem <= GPSIQ_ARRAY_MAX_ELEM, 1 <= ntaps <= GPSIQ_STAP_MAX_TAPS and K = nelem * ntaps <= GPSIQ_STAP_MAX_ROWS, else
+ * GPSIQ_E_ARG.  Row k = e * ntaps + t of the space-time snapshot is  z_k(n) = x_e(n - t).
+ * Samples before the span: for -(ntaps-1) <= m < 0, x_e(m) is sample ntaps-1+m of head[e]: ntaps-1 samples of the same format, 4-byte
+ * aligned, in device or page-locked memory -- gpsiq_filter's head, one per element.  head == NULL or head[e] == NULL: zeros.  head is a
+ * HOST array [nelem]; with ntaps == 1 it is not read.  Sources: as gpsiq_array_* has them (see "Array").
+ *
+ * gpsiq_stap_cov writes the exact covariance  R[k][l] = sum over 0 <= n < nsamp of z_k(n) * conj(z_l(n))  to cov[k][l][0..1] (host,
+ * int64), real and imaginary parts as gpsiq_array_cov states them.  The full Hermitian matrix is written; the wrap bound is the
+ * array's (|R| < 2^62); nsamp == 0 launches nothing and writes zeros.  Continuation: a span taken in pieces, each piece given head =
+ * the last ntaps-1 samples before it (the first piece the span's own head), gives covariances that add up to one call's, word for word.
+ * GPSIQ_STAP_KERNEL=generic|mfma in the environment, read per call, forces a kernel where it can serve (the matrix kernel serves int8
+ * input); the numbers never depend on it.  Stream order and return: as gpsiq_array_cov.
+ *
+ * gpsiq_stap_combine is the tapped beamformer  y(n) = sum over e, t of w[e][t] * x_e(n - t),  w = re + j im:
+ *   accI = sum over e, t of re[e][t] * I_e(n - t) - im[e][t] * Q_e(n - t)
+ *   accQ = sum over e, t of re[e][t] * Q_e(n - t) + im[e][t] * I_e(n - t)
+ * and each component goes through gpsiq_cfilter's finish (round-half-up shift, symmetric clamp, *clipped); 0 <= shift <= 24 and the
+ * four format pairs, else GPSIQ_E_ARG.  The bound: sum over all K weights of (|re| + |im|) <= 65535, else GPSIQ_E_RANGE; with it
+ * |acc| < 2^31 for both input formats.  dst holds nsamp samples, 4-byte aligned, device or page-locked memory, and overlaps no source
+ * and no head (GPSIQ_E_ARG).  nsamp == 0 launches nothing.  Pieces with heads, sources and dst advanced alike, give the bytes of one
+ * call, and their counts add up to its count.  Stream order and return: as gpsiq_array_combine.
+ * Identities:  with ntaps == 1 both calls give the words and bytes of gpsiq_array_cov and gpsiq_array_combine;  the sub-matrix of the
+ * rows with t == 0 is gpsiq_array_cov's result whatever head holds;  with nelem == 1 gpsiq_stap_combine writes the bytes and the count
+ * of gpsiq_cfilter with taps = w[0], decim 1, phase 0 and the same head;  with shift 0 and nothing clamped,
+ * sum |y(n)|^2 = sum over k, l of w_k conj(w_l) R[k][l]  exactly.
+ *
+ * gpsiq_stap_weights is gpsiq_array_weights over the K rows, through the same long double Cholesky factorisation:
+ * Rn = cov / nsamp + loading * (trace(cov / nsamp) / K) * I;  the constraint is  c_(e,t) = [t == ref_tap] * (steer_cycles ?
+ * exp(j 2 pi steer_cycles[e]) : [e == 0]);  v = Rn^-1 c / (c^H Rn^-1 c);  w[e][t] = rint(2^shift * conj(v_(e,t))).  Refusals as
+ * gpsiq_array_weights (with the sizes above), and ref_tap outside 0..ntaps-1 is GPSIQ_E_ARG.  Only the lower triangle of cov is read.
+ * Properties are contract, bits are not: the three of gpsiq_array_weights hold with K for nelem in property 2 and, in property 3, the
+ * diagonal entry of row (0, ref_tap) for Rn[0][0]: v^H Rn v <= Rn[ref_tap][ref_tap] for power inversion, that row itself meeting the
+ * constraint; and
+ *   4. for the same covariance, v^H Rn v is at most that of the spatial solution (gpsiq_array_weights with the same loaded matrix) on
+ *      the sub-matrix of the rows with t == ref_tap: a subspace cannot do better. */
+#define GPSIQ_STAP_MAX_TAPS 8
+#define GPSIQ_STAP_MAX_ROWS 32          /* nelem * ntaps */
+
+int gpsiq_stap_cov(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* host [nelem] stream pointers */,
+                   const void *const *head /* host [nelem], may be NULL, entries may be NULL */, int nsamp, int sample_size, int ntaps,
+                   void *hip_stream, int64_t *cov /* host [K][K][2] */, float *kernel_ms /* may be NULL */);
+int gpsiq_stap_combine(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* host [nelem] */, const void *const *head /* as above */,
+                       int nsamp, int sample_size, const gpsiq_ctap_t *w /* host [nelem][ntaps] */, int ntaps, int shift,
+                       int out_sample_size, void *dst, void *hip_stream, uint64_t *clipped, float *kernel_ms);   /* the last two may be NULL */
+int gpsiq_stap_weights(const int64_t *cov /* [K][K][2] */, int nelem, int ntaps, uint64_t nsamp, const double *steer_cycles /* [nelem] or NULL */,
+                       int ref_tap, double loading, int shift, gpsiq_ctap_t *w /* [nelem][ntaps] */);             /* host arithmetic */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

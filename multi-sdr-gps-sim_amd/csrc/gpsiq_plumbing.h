@@ -36,7 +36,8 @@ void *gpsiq_plumbing(const char *name);
  * "generate_batch_resampled" are gpsiq_resample and gpsiq_generate_batch_resampled (ibid., "Resample"; csrc/gpsiq_resample.cpp).  "agc" and
  * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp).  "cfilter" is
  * gpsiq_cfilter (ibid., "Complex filter and notch"; csrc/gpsiq_cfilter.cpp).  "array_cov" and "array_combine" are gpsiq_array_cov and
- * gpsiq_array_combine (ibid., "Array"; csrc/gpsiq_array.cpp). */
+ * gpsiq_array_combine (ibid., "Array"; csrc/gpsiq_array.cpp).  "stap_cov" and "stap_combine" are gpsiq_stap_cov and gpsiq_stap_combine
+ * (ibid., "Space-time array"; csrc/gpsiq_stap.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -241,6 +242,11 @@ int gpsiq_cfilter_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
  * for the generic covariance kernel, k-steps of 64 samples for the matrix kernel) or the samples of a combiner lane's slot, out[3] the
  * elements. */
 int gpsiq_array_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
+/* What the context's last gpsiq_stap_cov / gpsiq_stap_combine took (csrc/gpsiq_stap_plan.h): out[0] the kernel (0 stap_cov_generic,
+ * 1 stap_cov_mfma, 2 stap_combine; -1: nothing was launched, or no call yet), out[1] the grid, out[2] the run of a workgroup (samples
+ * for the generic covariance kernel, k-steps of 64 samples for the matrix kernel) or the samples of a combiner lane's slot, out[3] the
+ * elements, out[4] the taps. */
+int gpsiq_stap_last_plan(const gpsiq_ctx_t *ctx, long out[5]);
 
 #ifdef __cplusplus
 }

@@ -244,3 +244,21 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_array_combine(gpsiq_
     static const auto f = gpsiq::core<decltype(&gpsiq_array_combine)>("array_combine");
     return f(ctx, nelem, src, nsamp, sample_size, w, shift, out_sample_size, dst, hip_stream, clipped, kernel_ms);
 }
+
+// The space-time array stage runs on the context's device (csrc/gpsiq_stap.cpp) and is exported here like the array's (include/gpsiq_rows.h,
+// "Space-time array"); gpsiq_stap_weights, plain arithmetic, is in gpsiq_stage_math.cpp beside gpsiq_array_weights.
+extern "C" __attribute__((visibility("default"))) int gpsiq_stap_cov(gpsiq_ctx_t *ctx, int nelem, const void *const *src, const void *const *head, int nsamp,
+                                                                     int sample_size, int ntaps, void *hip_stream, int64_t *cov, float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_stap_cov)>("stap_cov");
+    return f(ctx, nelem, src, head, nsamp, sample_size, ntaps, hip_stream, cov, kernel_ms);
+}
+
+extern "C" __attribute__((visibility("default"))) int gpsiq_stap_combine(gpsiq_ctx_t *ctx, int nelem, const void *const *src, const void *const *head,
+                                                                         int nsamp, int sample_size, const gpsiq_ctap_t *w, int ntaps, int shift,
+                                                                         int out_sample_size, void *dst, void *hip_stream, uint64_t *clipped,
+                                                                         float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_stap_combine)>("stap_combine");
+    return f(ctx, nelem, src, head, nsamp, sample_size, w, ntaps, shift, out_sample_size, dst, hip_stream, clipped, kernel_ms);
+}

@@ -3,7 +3,7 @@
 // C/N0 estimate of the correlator's sums, the steps and the decision of a search, the gains and the bits of a follow, the output count
 // and the taps of a filter, the segments, the shift and the scale of a spectrum, the steps, the gains and the continuation of a mix, the
 // output count, the step and the tap table of a resampler, the gain rule and the windows of a gain control, the lines of a spectrum
-// and the taps of a notch.  Host code of libgpsiq_rows.so; nothing here touches a context or the
+// and the taps of a notch, the steering and the weights of an array with and without taps.  Host code of libgpsiq_rows.so; nothing here touches a context or the
 // device (the calls themselves: gpsiq_rows_link.cpp).
 #include "gpsiq_internal.h"
 #include "gpsiq_filter_plan.h"
@@ -13,11 +13,88 @@
 #include "gpsiq_agc_plan.h"
 #include "gpsiq_cfilter_geometry.h"
 #include "gpsiq_array_geometry.h"
+#include "gpsiq_stap_geometry.h"
 
 #include <algorithm>
 #include <cmath>
 
 using namespace gpsiq;
+
+namespace {
+
+constexpr int kWeightRows = kStapMaxRows;                              // the largest system constrained_weights solves
+static_assert(kWeightRows >= kArrMaxElem && kStapWeightSum == kArrWeightSum, "one solver and one bound serve the array and the space-time array");
+
+// c_e = exp(j 2 pi steer_cycles[e]), or e_0 where there is no steering (power inversion, element 0 the reference)
+int steering_constraint(const double *steer_cycles, int nelem, long double *cr, long double *ci)
+{
+    typedef long double ld;
+    const ld two_pi = 6.283185307179586476925286766559L;
+    for (int a = 0; a < nelem; ++a) {
+        if (steer_cycles) {
+            if (!std::isfinite(steer_cycles[a])) return fail(GPSIQ_E_ARG, "steering phase %d not finite", a);
+            cr[a] = std::cos(two_pi * (ld) steer_cycles[a]);
+            ci[a] = std::sin(two_pi * (ld) steer_cycles[a]);
+        } else { cr[a] = a ? 0.0L : 1.0L; ci[a] = 0.0L; }
+    }
+    return GPSIQ_OK;
+}
+
+// w = rint(2^shift conj(v)), v = Rn^-1 c / (c^H Rn^-1 c), Rn = cov / nsamp + loading (trace / n) I of n rows (n <= kWeightRows, the
+// caller has checked every argument): the long double Cholesky of gpsiq_array_weights and gpsiq_stap_weights, the order of every sum
+// the one gpsiq_array_weights has always had.  `what` names a row in the refusals
+int constrained_weights(const int64_t *cov, int n, uint64_t nsamp, const long double *cr, const long double *ci, double loading, int shift, const char *what,
+                        gpsiq_ctap_t *w)
+{
+    typedef long double ld;
+    static thread_local ld lr[kWeightRows][kWeightRows], li[kWeightRows][kWeightRows];
+    ld trace = 0.0L;
+    for (int a = 0; a < n; ++a) trace += (ld) cov[2 * (a * n + a)] / (ld) nsamp;
+    const ld load = (ld) loading * trace / (ld) n;
+    // Cholesky, from the lower triangle of cov
+    for (int j = 0; j < n; ++j) {
+        ld d = (ld) cov[2 * (j * n + j)] / (ld) nsamp + load;
+        for (int k = 0; k < j; ++k) d -= lr[j][k] * lr[j][k] + li[j][k] * li[j][k];
+        if (!(d > 0.0L) || !std::isfinite((double) d)) return fail(GPSIQ_E_ARG, "the covariance is not positive definite at %s %d (loading %g)", what, j, loading);
+        const ld piv = std::sqrt(d);
+        lr[j][j] = piv; li[j][j] = 0.0L;
+        for (int i = j + 1; i < n; ++i) {
+            ld sr = (ld) cov[2 * (i * n + j)] / (ld) nsamp, si = (ld) cov[2 * (i * n + j) + 1] / (ld) nsamp;
+            for (int k = 0; k < j; ++k) {                              // - L[i][k] conj(L[j][k])
+                sr -= lr[i][k] * lr[j][k] + li[i][k] * li[j][k];
+                si -= li[i][k] * lr[j][k] - lr[i][k] * li[j][k];
+            }
+            lr[i][j] = sr / piv; li[i][j] = si / piv;
+        }
+    }
+    ld yr[kWeightRows], yi[kWeightRows], zr[kWeightRows], zi[kWeightRows], denom = 0.0L;
+    for (int i = 0; i < n; ++i) {                                      // L y = c
+        ld sr = cr[i], si = ci[i];
+        for (int k = 0; k < i; ++k) { sr -= lr[i][k] * yr[k] - li[i][k] * yi[k]; si -= lr[i][k] * yi[k] + li[i][k] * yr[k]; }
+        yr[i] = sr / lr[i][i]; yi[i] = si / lr[i][i];
+        denom += yr[i] * yr[i] + yi[i] * yi[i];
+    }
+    for (int i = n - 1; i >= 0; --i) {                                 // L^H z = y: (L^H)[i][k] = conj(L[k][i])
+        ld sr = yr[i], si = yi[i];
+        for (int k = i + 1; k < n; ++k) { sr -= lr[k][i] * zr[k] + li[k][i] * zi[k]; si -= lr[k][i] * zi[k] - li[k][i] * zr[k]; }
+        zr[i] = sr / lr[i][i]; zi[i] = si / lr[i][i];
+    }
+    if (!(denom > 0.0L)) return fail(GPSIQ_E_ARG, "the constraint has no solution");
+    const ld scale = std::ldexp(1.0L, shift);
+    long q[kWeightRows][2], mag = 0;
+    for (int e = 0; e < n; ++e) {
+        const ld re = scale * zr[e] / denom, im = -scale * zi[e] / denom;      // conj(v_e)
+        if (!(std::fabs(re) < 65536.0L) || !(std::fabs(im) < 65536.0L)) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
+        q[e][0] = std::lrint(re); q[e][1] = std::lrint(im);
+        if (q[e][0] > 32767 || q[e][0] < -32768 || q[e][1] > 32767 || q[e][1] < -32768) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
+        mag += std::labs(q[e][0]) + std::labs(q[e][1]);
+    }
+    if (mag > kArrWeightSum) return fail(GPSIQ_E_RANGE, "sum |re| + |im| %ld above %ld at shift %d", mag, kArrWeightSum, shift);
+    for (int e = 0; e < n; ++e) { w[e].re = (int16_t) q[e][0]; w[e].im = (int16_t) q[e][1]; }
+    return GPSIQ_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -516,6 +593,7 @@ int gpsiq_array_steer(const double *pos, int nelem, double az_rad, double el_rad
 // ibid.: v = Rn^-1 c / (c^H Rn^-1 c) with Rn = cov / nsamp + loading (trace / nelem) I, through the Cholesky factor Rn = L L^H in
 // long double (L lower triangular with a real positive diagonal: a pivot that is not positive says Rn is not positive definite):
 // L y = c forwards, L^H z = y backwards, z = Rn^-1 c, and c^H z = |y|^2 is real.  w_e = rint(2^shift conj(v_e)).
+// (constrained_weights below: the arithmetic, shared with gpsiq_stap_weights, where the rows are elements times taps)
 int gpsiq_array_weights(const int64_t *cov, int nelem, uint64_t nsamp, const double *steer_cycles, double loading, int shift, gpsiq_ctap_t *w)
 {
     if (!cov || !w) return fail(GPSIQ_E_ARG, "null argument");
@@ -523,60 +601,32 @@ int gpsiq_array_weights(const int64_t *cov, int nelem, uint64_t nsamp, const dou
     if (nsamp == 0) return fail(GPSIQ_E_ARG, "a covariance of no samples");
     if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(GPSIQ_E_ARG, "loading %g: finite and not negative", loading);
     if (shift < 0 || shift > kArrMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kArrMaxShift);
-    typedef long double ld;
-    const ld two_pi = 6.283185307179586476925286766559L;
-    ld lr[kArrMaxElem][kArrMaxElem], li[kArrMaxElem][kArrMaxElem], cr[kArrMaxElem], ci[kArrMaxElem];
-    ld trace = 0.0L;
-    for (int a = 0; a < nelem; ++a) trace += (ld) cov[2 * (a * nelem + a)] / (ld) nsamp;
-    const ld load = (ld) loading * trace / (ld) nelem;
-    for (int a = 0; a < nelem; ++a) {
-        if (steer_cycles) {
-            if (!std::isfinite(steer_cycles[a])) return fail(GPSIQ_E_ARG, "steering phase %d not finite", a);
-            cr[a] = std::cos(two_pi * (ld) steer_cycles[a]);
-            ci[a] = std::sin(two_pi * (ld) steer_cycles[a]);
-        } else { cr[a] = a ? 0.0L : 1.0L; ci[a] = 0.0L; }
-    }
-    // Cholesky, from the lower triangle of cov
-    for (int j = 0; j < nelem; ++j) {
-        ld d = (ld) cov[2 * (j * nelem + j)] / (ld) nsamp + load;
-        for (int k = 0; k < j; ++k) d -= lr[j][k] * lr[j][k] + li[j][k] * li[j][k];
-        if (!(d > 0.0L) || !std::isfinite((double) d)) return fail(GPSIQ_E_ARG, "the covariance is not positive definite at element %d (loading %g)", j, loading);
-        const ld piv = std::sqrt(d);
-        lr[j][j] = piv; li[j][j] = 0.0L;
-        for (int i = j + 1; i < nelem; ++i) {
-            ld sr = (ld) cov[2 * (i * nelem + j)] / (ld) nsamp, si = (ld) cov[2 * (i * nelem + j) + 1] / (ld) nsamp;
-            for (int k = 0; k < j; ++k) {                              // - L[i][k] conj(L[j][k])
-                sr -= lr[i][k] * lr[j][k] + li[i][k] * li[j][k];
-                si -= li[i][k] * lr[j][k] - lr[i][k] * li[j][k];
-            }
-            lr[i][j] = sr / piv; li[i][j] = si / piv;
+    long double cr[kArrMaxElem], ci[kArrMaxElem];
+    if (int rc = steering_constraint(steer_cycles, nelem, cr, ci)) return rc;
+    return constrained_weights(cov, nelem, nsamp, cr, ci, loading, shift, "element", w);
+}
+
+// include/gpsiq_rows.h, "Space-time array": gpsiq_array_weights over the K = nelem ntaps rows k = e ntaps + t, the constraint on the
+// rows of tap ref_tap alone
+int gpsiq_stap_weights(const int64_t *cov, int nelem, int ntaps, uint64_t nsamp, const double *steer_cycles, int ref_tap, double loading, int shift,
+                       gpsiq_ctap_t *w)
+{
+    if (!cov || !w) return fail(GPSIQ_E_ARG, "null argument");
+    if (nelem < 1 || nelem > kStapMaxElem) return fail(GPSIQ_E_ARG, "nelem %d outside 1..%d", nelem, kStapMaxElem);
+    if (ntaps < 1 || ntaps > kStapMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kStapMaxTaps);
+    if (nelem * ntaps > kStapMaxRows) return fail(GPSIQ_E_ARG, "nelem %d * ntaps %d above %d rows", nelem, ntaps, kStapMaxRows);
+    if (ref_tap < 0 || ref_tap >= ntaps) return fail(GPSIQ_E_ARG, "ref_tap %d outside 0..%d", ref_tap, ntaps - 1);
+    if (nsamp == 0) return fail(GPSIQ_E_ARG, "a covariance of no samples");
+    if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(GPSIQ_E_ARG, "loading %g: finite and not negative", loading);
+    if (shift < 0 || shift > kStapMaxShift) return fail(GPSIQ_E_ARG, "shift %d outside 0..%d", shift, kStapMaxShift);
+    long double er[kStapMaxElem], ei[kStapMaxElem], cr[kStapMaxRows], ci[kStapMaxRows];
+    if (int rc = steering_constraint(steer_cycles, nelem, er, ei)) return rc;
+    for (int e = 0; e < nelem; ++e)
+        for (int t = 0; t < ntaps; ++t) {
+            cr[e * ntaps + t] = t == ref_tap ? er[e] : 0.0L;
+            ci[e * ntaps + t] = t == ref_tap ? ei[e] : 0.0L;
         }
-    }
-    ld yr[kArrMaxElem], yi[kArrMaxElem], zr[kArrMaxElem], zi[kArrMaxElem], denom = 0.0L;
-    for (int i = 0; i < nelem; ++i) {                                  // L y = c
-        ld sr = cr[i], si = ci[i];
-        for (int k = 0; k < i; ++k) { sr -= lr[i][k] * yr[k] - li[i][k] * yi[k]; si -= lr[i][k] * yi[k] + li[i][k] * yr[k]; }
-        yr[i] = sr / lr[i][i]; yi[i] = si / lr[i][i];
-        denom += yr[i] * yr[i] + yi[i] * yi[i];
-    }
-    for (int i = nelem - 1; i >= 0; --i) {                             // L^H z = y: (L^H)[i][k] = conj(L[k][i])
-        ld sr = yr[i], si = yi[i];
-        for (int k = i + 1; k < nelem; ++k) { sr -= lr[k][i] * zr[k] + li[k][i] * zi[k]; si -= lr[k][i] * zi[k] - li[k][i] * zr[k]; }
-        zr[i] = sr / lr[i][i]; zi[i] = si / lr[i][i];
-    }
-    if (!(denom > 0.0L)) return fail(GPSIQ_E_ARG, "the constraint has no solution");
-    const ld scale = std::ldexp(1.0L, shift);
-    long q[kArrMaxElem][2], mag = 0;
-    for (int e = 0; e < nelem; ++e) {
-        const ld re = scale * zr[e] / denom, im = -scale * zi[e] / denom;      // conj(v_e)
-        if (!(std::fabs(re) < 65536.0L) || !(std::fabs(im) < 65536.0L)) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
-        q[e][0] = std::lrint(re); q[e][1] = std::lrint(im);
-        if (q[e][0] > 32767 || q[e][0] < -32768 || q[e][1] > 32767 || q[e][1] < -32768) return fail(GPSIQ_E_RANGE, "weight %d leaves int16 at shift %d", e, shift);
-        mag += std::labs(q[e][0]) + std::labs(q[e][1]);
-    }
-    if (mag > kArrWeightSum) return fail(GPSIQ_E_RANGE, "sum |re| + |im| %ld above %ld at shift %d", mag, kArrWeightSum, shift);
-    for (int e = 0; e < nelem; ++e) { w[e].re = (int16_t) q[e][0]; w[e].im = (int16_t) q[e][1]; }
-    return GPSIQ_OK;
+    return constrained_weights(cov, nelem * ntaps, nsamp, cr, ci, loading, shift, "row", w);
 }
 
 }  // extern "C"

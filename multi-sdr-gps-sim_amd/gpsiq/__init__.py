@@ -210,6 +210,12 @@ _array_steer = _sig("gpsiq_array_steer", _i, _vp, _i, _d, _d, _vp)
 _array_weights = _sig("gpsiq_array_weights", _i, _vp, _i, C.c_uint64, _vp, _d, _i, _vp)
 _array_last_plan = _sig("gpsiq_array_last_plan", _i, _vp, _vp)
 ARRAY_MAX_ELEM = 8
+_stap_cov = _sig("gpsiq_stap_cov", _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float))
+_stap_combine = _sig("gpsiq_stap_combine", _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float))
+_stap_weights = _sig("gpsiq_stap_weights", _i, _vp, _i, _i, C.c_uint64, _vp, _i, _d, _i, _vp)
+_stap_last_plan = _sig("gpsiq_stap_last_plan", _i, _vp, _vp)
+STAP_MAX_TAPS = 8
+STAP_MAX_ROWS = 32
 
 
 class CTap(C.Structure):
@@ -915,6 +921,25 @@ def array_weights(cov, nsamp, steer=None, loading=0.0, shift=12):
     return w[:nelem].copy()
 
 
+def stap_weights(cov, nsamp, nelem, ntaps, steer=None, ref_tap=0, loading=0.0, shift=12):
+    """gpsiq_stap_weights: the tapped combiner's weights int16 [nelem, ntaps, 2] (re, im) over 2**shift from a space-time covariance
+    int64 [K, K, 2], K = nelem * ntaps, of nsamp samples: the constraint sits on the rows of tap ref_tap -- element 0 alone (steer
+    None: power inversion) or the steering phases `steer` (cycles, from array_steer); `loading` as array_weights."""
+    cov = np.ascontiguousarray(cov, dtype=np.int64)
+    nelem, ntaps = int(nelem), int(ntaps)
+    if cov.ndim != 3 or cov.shape[0] != cov.shape[1] or cov.shape[2] != 2 or cov.shape[0] != nelem * ntaps:
+        raise GpsiqError(-1, f"a space-time covariance of {nelem} elements and {ntaps} taps is [{nelem * ntaps}, {nelem * ntaps}, 2], not {cov.shape}")
+    st = None
+    if steer is not None:
+        st = np.ascontiguousarray(steer, dtype=np.float64).ravel()
+        if len(st) != nelem:
+            raise GpsiqError(-1, f"{len(st)} steering phases for {nelem} elements")
+    w = np.zeros((max(nelem * ntaps, 1), 2), dtype=np.int16)
+    _check(_stap_weights(_p(cov) if cov.size else None, nelem, ntaps, _u64_arg(nsamp, "nsamp"), None if st is None else _p(st), int(ref_tap),
+                         float(loading), int(shift), _p(w)))
+    return w[:nelem * ntaps].reshape(nelem, ntaps, 2).copy()
+
+
 def array_element(desc, phases):
     """The descriptor timeline of one array element: a copy of desc (CHAN_DTYPE [nblocks, nchan]) with phases[channel] (cycles) added
     to every row's carr_phase, modulo 1.  gpsiq_generate_batch reads carr_phase only in block 0 and where a slot is re-allocated, so
@@ -1317,6 +1342,50 @@ class Context:
         out = (C.c_long * 4)()
         _check(_array_last_plan(self._h, out))
         return {0: "generic", 1: "mfma", 2: "combine"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3])
+
+    @staticmethod
+    def _stap_pointers(ptrs, heads):
+        ptrs = [int(p or 0) for p in ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        if heads is None:
+            return ptrs, arr, None
+        heads = [int(h or 0) for h in heads]
+        if len(heads) != len(ptrs):
+            raise GpsiqError(-1, f"{len(heads)} heads for {len(ptrs)} elements")
+        return ptrs, arr, (C.c_void_p * max(len(heads), 1))(*heads)
+
+    def stap_cov(self, ptrs, nsamp, sample_size, ntaps, heads=None, stream=None):
+        """gpsiq_stap_cov: the exact covariance of the rows z[e * ntaps + t](n) = x_e(n - t) of the streams at `ptrs` (device or
+        page-locked addresses, one per element), nsamp complex samples each; heads: None, or per element the address of the ntaps - 1
+        samples before the span (None or 0: zeros) -> (int64 [K, K, 2] (re, im), K = len(ptrs) * ntaps, kernel milliseconds)."""
+        ptrs, arr, harr = self._stap_pointers(ptrs, heads)
+        rows = len(ptrs) * max(int(ntaps), 0)
+        cov = np.zeros((rows, rows, 2), dtype=np.int64)
+        ms = C.c_float(0.0)
+        _check(_stap_cov(self._h, len(ptrs), arr, harr, int(nsamp), int(sample_size), int(ntaps), _vp(stream or 0),
+                         _p(cov) if cov.size else None, C.byref(ms)))
+        return cov, float(ms.value)
+
+    def stap_combine(self, ptrs, nsamp, sample_size, weights, shift, out_sample_size, dst_device_ptr, heads=None, stream=None):
+        """gpsiq_stap_combine: sum over elements and taps of weights[e][t] * x_e(n - t) (int16 [nelem, ntaps, 2] (re, im)), rounded by
+        `shift`, clamped into out_sample_size at dst_device_ptr; heads as stap_cov -> (elements the clamp changed, kernel milliseconds)."""
+        ptrs, arr, harr = self._stap_pointers(ptrs, heads)
+        w = np.asarray(weights)
+        if w.ndim != 3 or w.shape[0] != len(ptrs) or w.shape[2] != 2:
+            raise GpsiqError(-1, f"tapped weights are [nelem, ntaps, 2] (re, im) for {len(ptrs)} elements, not an array of shape {w.shape}")
+        ntaps = w.shape[1]
+        w = ctaps(w.reshape(-1, 2))
+        clipped, ms = C.c_uint64(0), C.c_float(0.0)
+        _check(_stap_combine(self._h, len(ptrs), arr, harr, int(nsamp), int(sample_size), _p(w) if len(w) else None, int(ntaps), int(shift),
+                             int(out_sample_size), _vp(dst_device_ptr), _vp(stream or 0), C.byref(clipped), C.byref(ms)))
+        return int(clipped.value), float(ms.value)
+
+    def stap_last_plan(self):
+        """What the last stap_cov() / stap_combine() took: (kernel name or None, grid, run of a workgroup or samples of a slot, elements,
+        taps)."""
+        out = (C.c_long * 5)()
+        _check(_stap_last_plan(self._h, out))
+        return {0: "generic", 1: "mfma", 2: "combine"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3]), int(out[4])
 
     def generate_batch_filtered(self, desc, nsamp, fs, sample_size, taps, shift, decim, out_sample_size, host_ptr=None, block_stride=None,
                                 carr_out=None):
