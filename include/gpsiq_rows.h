@@ -940,6 +940,36 @@ int gpsiq_stap_combine(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* ho
 int gpsiq_stap_weights(const int64_t *cov /* [K][K][2] */, int nelem, int ntaps, uint64_t nsamp, const double *steer_cycles /* [nelem] or NULL */,
                        int ref_tap, double loading, int shift, gpsiq_ctap_t *w /* [nelem][ntaps] */);             /* host arithmetic */
 
+/* Several beams from one pass.  A steered beam protects the one satellite it is steered at, so a receiver forms one beam per satellite
+ * in view: 1 <= nbeams <= GPSIQ_STAP_MAX_BEAMS beams of the same sources, heads, ntaps, shift and formats, the element streams read
+ * once.  w is [nbeams][nelem][ntaps], dst a HOST array [nbeams] of stream pointers, clipped a host array [nbeams] (may be NULL).
+ *
+ * gpsiq_stap_beams: for every beam b, dst[b] receives exactly the bytes gpsiq_stap_combine writes with w[b] and the same sources,
+ * heads, ntaps, shift and formats, and clipped[b] is that call's count.  Rows, heads, the finish (round-half-up shift, symmetric
+ * clamp), 0 <= shift <= 24 and the four format pairs are gpsiq_stap_combine's, and so are its refusals; nbeams outside 1 ..
+ * GPSIQ_STAP_MAX_BEAMS is GPSIQ_E_ARG.  The bound holds per beam: sum over the K weights of beam b of (|re| + |im|) <= 65535, else
+ * GPSIQ_E_RANGE.  Every dst[b] is non-null where nsamp > 0, 4-byte aligned, in device or page-locked memory, and overlaps no source,
+ * no head and no other destination, else GPSIQ_E_ARG.  nsamp == 0 launches nothing and writes zero counts.  Pieces with heads, sources
+ * and every dst advanced alike give the bytes of one call, and their counts add up per beam.  Stream order and return: as
+ * gpsiq_stap_combine.  GPSIQ_STAP_BEAMS_KERNEL=generic|mfma in the environment, read per call, forces a kernel where it can serve (the
+ * matrix kernel serves both input formats where nelem times ntaps rounded up to a power of two does not pass GPSIQ_STAP_MAX_ROWS and
+ * every weight component lies in -32639 .. 32639, re also down to -32768); the bytes never depend on it.
+ *
+ * gpsiq_stap_beam_weights: beam b is what gpsiq_stap_weights returns for steer_cycles[b] (non-null: [nbeams][nelem]) with the same
+ * remaining arguments, bit for bit.  The beams are solved in order; the first beam that is refused decides the return value, and
+ * nothing is written for that beam or any beam after it.  nbeams outside 1 .. GPSIQ_STAP_MAX_BEAMS is GPSIQ_E_ARG. */
+#define GPSIQ_STAP_MAX_BEAMS 8
+
+int gpsiq_stap_beams(gpsiq_ctx_t *ctx, int nelem, const void *const *src /* host [nelem] */,
+                     const void *const *head /* host [nelem], may be NULL, entries may be NULL */,
+                     int nsamp, int sample_size,
+                     const gpsiq_ctap_t *w /* host [nbeams][nelem][ntaps] */, int ntaps, int nbeams, int shift,
+                     int out_sample_size, void *const *dst /* host [nbeams] stream pointers */, void *hip_stream,
+                     uint64_t *clipped /* host [nbeams], may be NULL */, float *kernel_ms /* may be NULL */);
+int gpsiq_stap_beam_weights(const int64_t *cov /* [K][K][2] */, int nelem, int ntaps, uint64_t nsamp,
+                            const double *steer_cycles /* [nbeams][nelem] */, int nbeams, int ref_tap,
+                            double loading, int shift, gpsiq_ctap_t *w /* [nbeams][nelem][ntaps] */);   /* host arithmetic */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

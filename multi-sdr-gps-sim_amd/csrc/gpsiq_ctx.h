@@ -7,7 +7,8 @@
 // and the piece loop) is in gpsiq_stage_batch.h, what a stage's single call does around its kernel in gpsiq_stage_call.h; HIP_TRY
 // is in gpsiq_own.h.
 //
-// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample, agc, cfilter, array, stap):
+// The files of a stream stage <s> (despread, pack, acquire, follow, filter, spectrum, mix, resample, agc, cfilter, array, stap,
+// stap_beams):
 //   include/gpsiq_rows.h        the public prototype, and the only place its signature is written outside the definition
 //   gpsiq_<s>.h                 the stage's member of gpsiq_ctx (resources, reserve()), its kernels by type and their look-ups,
 //                               and `decltype(gpsiq_<s>) gpsiq_<s>_impl;`
@@ -50,6 +51,7 @@
 #include "gpsiq_cfilter.h"
 #include "gpsiq_array.h"
 #include "gpsiq_stap.h"
+#include "gpsiq_stap_beams.h"
 
 struct gpsiq_ctx {
     template <typename T> using DevBuf = gpsiq::DevBuf<T>;
@@ -185,7 +187,8 @@ struct gpsiq_ctx {
     // the stream stages, each in the header of its name: gpsiq_despread; gpsiq_pack / gpsiq_unpack / gpsiq_generate_batch_packed;
     // gpsiq_acquire; gpsiq_follow; gpsiq_filter / gpsiq_generate_batch_filtered; gpsiq_spectrum;
     // gpsiq_mix / gpsiq_generate_batch_mixed; gpsiq_resample / gpsiq_generate_batch_resampled; gpsiq_agc / gpsiq_generate_batch_agc;
-    // gpsiq_cfilter; gpsiq_array_cov / gpsiq_array_combine; gpsiq_stap_cov / gpsiq_stap_combine
+    // gpsiq_cfilter; gpsiq_array_cov / gpsiq_array_combine; gpsiq_stap_cov / gpsiq_stap_combine;
+    // gpsiq_stap_beams
     gpsiq::DespreadSet dsp;
     gpsiq::PackSet     pack;
     gpsiq::AcquireSet  acq;
@@ -198,6 +201,7 @@ struct gpsiq_ctx {
     gpsiq::FirSet      cfilt;               // (its own: nothing is shared between the two filters at run time)
     gpsiq::ArraySet    array;
     gpsiq::StapSet     stap;
+    gpsiq::BeamsSet    beams;
     // the staging the five staged batch calls (_packed, _filtered, _mixed, _resampled, _agc) work through their pieces with: one ring for
     // all of them -- calls on a context are serial and every one ends with the ring's streams drained (gpsiq_stage_batch.h)
     gpsiq::PieceRing   ring;

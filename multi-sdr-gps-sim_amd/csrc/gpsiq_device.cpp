@@ -489,7 +489,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         GPSIQ_P(gpsiq_despread_last_plan), GPSIQ_P(gpsiq_pack_last_plan), GPSIQ_P(gpsiq_acquire_last_plan), GPSIQ_P(gpsiq_follow_last_plan),
         GPSIQ_P(gpsiq_filter_last_plan), GPSIQ_P(gpsiq_spectrum_last_plan), GPSIQ_P(gpsiq_mix_last_plan),
         GPSIQ_P(gpsiq_resample_last_plan), GPSIQ_P(gpsiq_agc_last_plan), GPSIQ_P(gpsiq_agc_last_ms), GPSIQ_P(gpsiq_cfilter_last_plan),
-        GPSIQ_P(gpsiq_array_last_plan), GPSIQ_P(gpsiq_stap_last_plan),
+        GPSIQ_P(gpsiq_array_last_plan), GPSIQ_P(gpsiq_stap_last_plan), GPSIQ_P(gpsiq_stap_beams_last_plan),
 #undef GPSIQ_P
         // the internals libgpsiq_rows.so runs on (gpsiq_rows_link.cpp): one pool, one quantiser, one error text per thread
         {"set_error", reinterpret_cast<void *>(&gpsiq::set_error)}, {"parallel_for", reinterpret_cast<void *>(&gpsiq::parallel_for)},
@@ -515,6 +515,7 @@ extern "C" void *gpsiq_plumbing(const char *name)
         {"array_combine", reinterpret_cast<void *>(&gpsiq_array_combine_impl)},                          // (ibid., "Array"; gpsiq_array.cpp)
         {"stap_cov", reinterpret_cast<void *>(&gpsiq_stap_cov_impl)},      // gpsiq_stap_cov and gpsiq_stap_combine of libgpsiq_rows.so
         {"stap_combine", reinterpret_cast<void *>(&gpsiq_stap_combine_impl)},                            // (ibid., "Space-time array"; gpsiq_stap.cpp)
+        {"stap_beams", reinterpret_cast<void *>(&gpsiq_stap_beams_impl)},  // gpsiq_stap_beams of libgpsiq_rows.so (ibid.; gpsiq_stap_beams.cpp)
     };
     if (!name) return nullptr;
     for (const auto &e : table)

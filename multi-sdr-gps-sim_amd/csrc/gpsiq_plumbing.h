@@ -37,7 +37,7 @@ void *gpsiq_plumbing(const char *name);
  * "generate_batch_agc" are gpsiq_agc and gpsiq_generate_batch_agc (ibid., "AGC"; csrc/gpsiq_agc.cpp).  "cfilter" is
  * gpsiq_cfilter (ibid., "Complex filter and notch"; csrc/gpsiq_cfilter.cpp).  "array_cov" and "array_combine" are gpsiq_array_cov and
  * gpsiq_array_combine (ibid., "Array"; csrc/gpsiq_array.cpp).  "stap_cov" and "stap_combine" are gpsiq_stap_cov and gpsiq_stap_combine
- * (ibid., "Space-time array"; csrc/gpsiq_stap.cpp). */
+ * (ibid., "Space-time array"; csrc/gpsiq_stap.cpp), and "stap_beams" is gpsiq_stap_beams (ibid.; csrc/gpsiq_stap_beams.cpp). */
 
 /* The tables the library builds in place of the reference's, read back (tests hold them against the oracle's).
  * C/A code of one PRN as 0/1 chips (codegen() gps.c:272-309); the carrier LUTs (cosTable512 / sinTable512 gps.c:145-213). */
@@ -247,6 +247,10 @@ int gpsiq_array_last_plan(const gpsiq_ctx_t *ctx, long out[4]);
  * for the generic covariance kernel, k-steps of 64 samples for the matrix kernel) or the samples of a combiner lane's slot, out[3] the
  * elements, out[4] the taps. */
 int gpsiq_stap_last_plan(const gpsiq_ctx_t *ctx, long out[5]);
+/* What the context's last gpsiq_stap_beams took (csrc/gpsiq_stap_beams_plan.h): out[0] the kernel (0 stap_beams_generic, 1 stap_beams_mfma;
+ * -1: nothing was launched, or no call yet), out[1] the grid, out[2] the samples of a workgroup's run, out[3] the elements, out[4] the
+ * taps, out[5] the beams, out[6] the taps an element is padded to in the matrix kernel's operand (0 for the generic kernel). */
+int gpsiq_stap_beams_last_plan(const gpsiq_ctx_t *ctx, long out[7]);
 
 #ifdef __cplusplus
 }

@@ -262,3 +262,14 @@ extern "C" __attribute__((visibility("default"))) int gpsiq_stap_combine(gpsiq_c
     static const auto f = gpsiq::core<decltype(&gpsiq_stap_combine)>("stap_combine");
     return f(ctx, nelem, src, head, nsamp, sample_size, w, ntaps, shift, out_sample_size, dst, hip_stream, clipped, kernel_ms);
 }
+
+// Several beams from one pass (csrc/gpsiq_stap_beams.cpp), exported here like the combiner; gpsiq_stap_beam_weights, plain arithmetic, is
+// in gpsiq_stage_math.cpp beside gpsiq_stap_weights.
+extern "C" __attribute__((visibility("default"))) int gpsiq_stap_beams(gpsiq_ctx_t *ctx, int nelem, const void *const *src, const void *const *head,
+                                                                       int nsamp, int sample_size, const gpsiq_ctap_t *w, int ntaps, int nbeams, int shift,
+                                                                       int out_sample_size, void *const *dst, void *hip_stream, uint64_t *clipped,
+                                                                       float *kernel_ms)
+{
+    static const auto f = gpsiq::core<decltype(&gpsiq_stap_beams)>("stap_beams");
+    return f(ctx, nelem, src, head, nsamp, sample_size, w, ntaps, nbeams, shift, out_sample_size, dst, hip_stream, clipped, kernel_ms);
+}

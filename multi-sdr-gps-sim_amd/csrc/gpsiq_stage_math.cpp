@@ -629,4 +629,22 @@ int gpsiq_stap_weights(const int64_t *cov, int nelem, int ntaps, uint64_t nsamp,
     return constrained_weights(cov, nelem * ntaps, nsamp, cr, ci, loading, shift, "row", w);
 }
 
+// ibid.: one gpsiq_stap_weights per beam, in order -- the same constrained_weights with every sum in its order, so beam b is that
+// call's result bit for bit (the factorisation is repeated per beam: sharing it would be a second statement of the arithmetic to
+// hold equal).  A refusal ends the call; constrained_weights writes a beam only once it has passed every check, so nothing is written
+// for the refused beam or any after it.
+int gpsiq_stap_beam_weights(const int64_t *cov, int nelem, int ntaps, uint64_t nsamp, const double *steer_cycles, int nbeams, int ref_tap, double loading,
+                            int shift, gpsiq_ctap_t *w)
+{
+    if (!cov || !w || !steer_cycles) return fail(GPSIQ_E_ARG, "null argument");
+    if (nbeams < 1 || nbeams > GPSIQ_STAP_MAX_BEAMS) return fail(GPSIQ_E_ARG, "nbeams %d outside 1..%d", nbeams, GPSIQ_STAP_MAX_BEAMS);
+    if (nelem < 1 || nelem > kStapMaxElem) return fail(GPSIQ_E_ARG, "nelem %d outside 1..%d", nelem, kStapMaxElem);
+    if (ntaps < 1 || ntaps > kStapMaxTaps) return fail(GPSIQ_E_ARG, "ntaps %d outside 1..%d", ntaps, kStapMaxTaps);
+    for (int b = 0; b < nbeams; ++b)
+        if (int rc = gpsiq_stap_weights(cov, nelem, ntaps, nsamp, steer_cycles + (size_t) b * (size_t) nelem, ref_tap, loading, shift,
+                                        w + (size_t) b * (size_t) nelem * (size_t) ntaps))
+            return rc;
+    return GPSIQ_OK;
+}
+
 }  // extern "C"

@@ -216,6 +216,10 @@ _stap_weights = _sig("gpsiq_stap_weights", _i, _vp, _i, _i, C.c_uint64, _vp, _i,
 _stap_last_plan = _sig("gpsiq_stap_last_plan", _i, _vp, _vp)
 STAP_MAX_TAPS = 8
 STAP_MAX_ROWS = 32
+_stap_beams = _sig("gpsiq_stap_beams", _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_float))
+_stap_beam_weights = _sig("gpsiq_stap_beam_weights", _i, _vp, _i, _i, C.c_uint64, _vp, _i, _i, _d, _i, _vp)
+_stap_beams_last_plan = _sig("gpsiq_stap_beams_last_plan", _i, _vp, _vp)
+STAP_MAX_BEAMS = 8
 
 
 class CTap(C.Structure):
@@ -940,6 +944,23 @@ def stap_weights(cov, nsamp, nelem, ntaps, steer=None, ref_tap=0, loading=0.0, s
     return w[:nelem * ntaps].reshape(nelem, ntaps, 2).copy()
 
 
+def stap_beam_weights(cov, nsamp, nelem, ntaps, steers, ref_tap=0, loading=0.0, shift=12):
+    """gpsiq_stap_beam_weights: one set of stap_weights per row of `steers` (cycles, [nbeams, nelem], from array_steer) from the same
+    space-time covariance -> int16 [nbeams, nelem, ntaps, 2] (re, im); beam b is stap_weights(..., steer=steers[b]) bit for bit."""
+    cov = np.ascontiguousarray(cov, dtype=np.int64)
+    nelem, ntaps = int(nelem), int(ntaps)
+    if cov.ndim != 3 or cov.shape[0] != cov.shape[1] or cov.shape[2] != 2 or cov.shape[0] != nelem * ntaps:
+        raise GpsiqError(-1, f"a space-time covariance of {nelem} elements and {ntaps} taps is [{nelem * ntaps}, {nelem * ntaps}, 2], not {cov.shape}")
+    st = np.ascontiguousarray(steers, dtype=np.float64)
+    if st.ndim != 2 or st.shape[1] != nelem:
+        raise GpsiqError(-1, f"steering phases are [nbeams, {nelem}], not an array of shape {st.shape}")
+    nbeams = st.shape[0]
+    w = np.zeros((max(nbeams * nelem * ntaps, 1), 2), dtype=np.int16)
+    _check(_stap_beam_weights(_p(cov) if cov.size else None, nelem, ntaps, _u64_arg(nsamp, "nsamp"), _p(st) if st.size else None, nbeams, int(ref_tap),
+                              float(loading), int(shift), _p(w)))
+    return w[:nbeams * nelem * ntaps].reshape(nbeams, nelem, ntaps, 2).copy()
+
+
 def array_element(desc, phases):
     """The descriptor timeline of one array element: a copy of desc (CHAN_DTYPE [nblocks, nchan]) with phases[channel] (cycles) added
     to every row's carr_phase, modulo 1.  gpsiq_generate_batch reads carr_phase only in block 0 and where a slot is re-allocated, so
@@ -1386,6 +1407,32 @@ class Context:
         out = (C.c_long * 5)()
         _check(_stap_last_plan(self._h, out))
         return {0: "generic", 1: "mfma", 2: "combine"}.get(int(out[0])), int(out[1]), int(out[2]), int(out[3]), int(out[4])
+
+    def stap_beams(self, ptrs, nsamp, sample_size, weights, shift, out_sample_size, dst_ptrs, heads=None, stream=None):
+        """gpsiq_stap_beams: len(dst_ptrs) beams of the same element streams in one pass; beam b is stap_combine with weights[b] (int16
+        [nbeams, nelem, ntaps, 2] (re, im)) written at dst_ptrs[b]; heads as stap_cov -> (elements the clamp changed per beam, uint64
+        [nbeams], kernel milliseconds)."""
+        ptrs, arr, harr = self._stap_pointers(ptrs, heads)
+        w = np.asarray(weights)
+        dsts = [int(d or 0) for d in dst_ptrs]
+        if w.ndim != 4 or w.shape[0] != len(dsts) or w.shape[1] != len(ptrs) or w.shape[3] != 2:
+            raise GpsiqError(-1, f"beam weights are [nbeams, nelem, ntaps, 2] (re, im) for {len(dsts)} beams of {len(ptrs)} elements, not an array of "
+                                 f"shape {w.shape}")
+        ntaps = w.shape[2]
+        w = ctaps(w.reshape(-1, 2))
+        darr = (C.c_void_p * max(len(dsts), 1))(*dsts)
+        clipped = np.zeros(max(len(dsts), 1), dtype=np.uint64)
+        ms = C.c_float(0.0)
+        _check(_stap_beams(self._h, len(ptrs), arr, harr, int(nsamp), int(sample_size), _p(w) if len(w) else None, int(ntaps), len(dsts), int(shift),
+                           int(out_sample_size), darr, _vp(stream or 0), _p(clipped), C.byref(ms)))
+        return clipped[:len(dsts)].copy(), float(ms.value)
+
+    def stap_beams_last_plan(self):
+        """What the last stap_beams() took: (kernel name or None, grid, samples of a workgroup's run, elements, taps, beams, the taps an
+        element is padded to in the matrix kernel's operand)."""
+        out = (C.c_long * 7)()
+        _check(_stap_beams_last_plan(self._h, out))
+        return ({0: "generic", 1: "mfma"}.get(int(out[0])),) + tuple(int(v) for v in out[1:])
 
     def generate_batch_filtered(self, desc, nsamp, fs, sample_size, taps, shift, decim, out_sample_size, host_ptr=None, block_stride=None,
                                 carr_out=None):
